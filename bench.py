@@ -18,7 +18,9 @@ this process has touched the GPU -- otherwise (torchrun / torch.distributed.run)
       the extra field `rollout_sharded`: table replicated, R/N seeds per GPU (primary axis).
   --scaling weak: every rank owns its own 10 M-transition log (N x 10 M in total), all R seeds on each.
 
-Prints ONE JSON line on rank 0; see DESIGN.md section 5 for `roofline`, `cpu_baseline`, `parity_check`.
+Prints ONE JSON line on rank 0; see DESIGN.md section 5 for `roofline`, `cpu_baseline`, `parity_check`.  A plain run sets up,
+warms up, times the passes, writes the last pass's per-seed results (`--dump-outputs DIR`) and prints the line; `--full` adds
+everything else: oracle parity check, CPU baseline, the extra configurations, the kernel clock pass, the multi-rank extras.
 """
 import argparse
 import hashlib
@@ -81,9 +83,18 @@ def parse():
                                                               "rank (legal for RCCL): the only way a one-GPU box executes the collective leg")
     ap.add_argument("--no-configs", action="store_true", help="skip the extra BASELINE configurations (C2 CartPole 1 M x 4096, C3 continuous_grid 10 M x 4096 "
                                                               "with the MLP encoder, one GPU's shard of C4 12.5 M x 4096, one GPU's shard of C5 6.25 M x 4096 "
-                                                              "with 128-d fp16 observations) that the default single-GPU headline run appends under \"configs\"")
+                                                              "with 128-d fp16 observations) that the single-GPU headline run with --full appends under \"configs\"")
     ap.add_argument("--print-csrc-digest", action="store_true", help="print the digest of the kernel sources (recorded by tools/profile_bench.sh) and exit")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: the oracle parity check, "
+                                                        "the CPU baseline, the extra configurations, the kernel clock read-out (one more untimed "
+                                                        "pass), the rollout-sharded and collective measurements of a multi-rank run, the PMC "
+                                                        "traffic of a committed profile")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step returned per seed "
+                                                          "(rank 0) as DIR/<name>.npy, float64")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def csrc_digest():
@@ -384,6 +395,28 @@ def make_obs128_log(a, N, seed, dev):
     return e, f", encoder forward {a.encode_s * 1e3:.1f} ms for 2 x {N} rows"
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(d, m):
+    """What the last timed pass returned per seed on this rank -- eval_mc's sum_g, n_ep, steps, cand -- and the per-seed value
+    estimate sum G / n episodes after the all-reduce, as float64 .npy files.  Above DUMP_BYTES in all, a fixed seeded sample of the
+    seeds is written, with their indices in seed_index.npy."""
+    arrs = {k: np.asarray(v, dtype=np.float64) for k, v in m["acc"].items()}
+    est = m["est"].cpu().numpy()
+    with np.errstate(invalid="ignore", divide="ignore"):
+        arrs["value_estimate"] = est[:, 0] / est[:, 1]
+    n = len(arrs["value_estimate"])
+    keep = (DUMP_BYTES - 4096) // (8 * (len(arrs) + 1))  # (+ seed_index; 4 KiB for the .npy headers)
+    if n * 8 * len(arrs) > DUMP_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrs = {k: v[idx] for k, v in arrs.items()}
+        arrs["seed_index"] = idx.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrs.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+
+
 def take_rows(e, mask):
     return {k: (v[mask] if isinstance(v, np.ndarray) and v.shape[:1] == mask.shape else v) for k, v in e.items()}
 
@@ -423,7 +456,7 @@ def run(a):
 
     R = a.rollouts
     strong = a.scaling == "strong"
-    # the default single-GPU headline command also reports the other BASELINE configurations that fit one GPU (C2, C3)
+    # the single-GPU headline command with --full also reports the other BASELINE configurations that fit one GPU (C2, C3)
     headline = (a.workload == "iid" and a.transitions == 10_000_000 and R == 4096 and a.n_states == 162 and a.n_actions == 2 and
                 a.shuffle == "per_rollout" and a.rng == "pcg64" and world == 1)
     # OFFSIM_BENCH_TEST_SCALE = k (tests only): the same code path with every log k times shorter; the line says so (`test_scale`)
@@ -439,7 +472,7 @@ def run(a):
         e = e_full
     pi = synth.dirichlet_policy(a.n_states, a.n_actions)
     seeds = np.arange(R, dtype=np.uint64)
-    want_parity = rank == 0 and not a.no_parity_check and a.shuffle != "table_order"  # (the reference has no unshuffled mode)
+    want_parity = a.full and rank == 0 and not a.no_parity_check and a.shuffle != "table_order"  # (the reference has no unshuffled mode)
     ora_main = OracleRun(e, pi, a.gamma, [s for s in PARITY_SEEDS if s < R], a.shuffle, 1234, rng=a.rng) if want_parity else None
 
     def barrier():
@@ -576,9 +609,11 @@ def run(a):
         torch.cuda.empty_cache()
         return res
 
-    m = measure(e, 0, R, a.warmup, a.steps, False, diag=True)
+    m = measure(e, 0, R, a.warmup, a.steps, False, diag=a.full)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, m)
     extra = None
-    if strong and world > 1 and not a.no_rollout_sharded:
+    if a.full and strong and world > 1 and not a.no_rollout_sharded:
         lo, hi = shard_rollouts(R, rank, world)
         x = measure(e_full, lo, hi, 1, 1, True)
         extra = {"value": x["steps_pass"] / x["elapsed"], "unit": "simulated steps/s", "ms_per_step": x["elapsed"] * 1e3,
@@ -588,7 +623,7 @@ def run(a):
                          "all-reduce assembles the [R,2] table"}
 
     coll = None
-    if use_pg:  # the collective alone: the [R,2] f64 all-reduce on the device tensor, HIP events around 20 of them
+    if a.full and use_pg:  # the collective alone: the [R,2] f64 all-reduce on the device tensor, HIP events around 20 of them
         x = m["est"].clone()
         allreduce_estimates(x)
         c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -683,7 +718,7 @@ def run(a):
         return out_c
 
     configs = None
-    if headline and not a.no_configs:
+    if a.full and headline and not a.no_configs:
         configs = {"C2": extra_config("C2", "cartpole", 1_000_000 // test_scale), "C3": extra_config("C3", "grid", 10_000_000 // test_scale),
                    # one GPU's shard of C4 (100 M transitions over 8 GPUs: 12.5 M rows x all 4096 seeds), evaluated as two episode-disjoint
                    # halves (round 6: their ~38 k-row states shuffle LDS-resident; `--workload iid --transitions 12500000` alone is the
@@ -702,7 +737,7 @@ def run(a):
         est = m["est"]
         vest = (est[:, 0] / est[:, 1]).cpu().numpy()
         kernel = m["variant"]
-        traffic, traffic_src = pmc_traffic(a, kernel, world)
+        traffic, traffic_src = pmc_traffic(a, kernel, world) if a.full else (None, "looked up by --full runs")
         n_rank = int(m["rows"])
         shard_txt = ("one GPU" if world == 1 else
                      f"the {a.transitions}-transition log split into {world} episode-disjoint shards ({n_rank} rows on rank 0), all {R} seeds on every shard, "
@@ -773,7 +808,7 @@ def run(a):
             if not out["parity_check"]["ok"]:
                 sys.stderr.write(json.dumps(out["parity_check"]) + "\n")
                 raise SystemExit("bench.py: the GPU results differ from the oracle on this table -- no number is reported")
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(base or oracle_for(e), pi, a.gamma, a.cpu_sample_seconds, a.cpu_threads_cap)
         _phase("CPU baseline done")
         _REAL_STDOUT.write(json.dumps(out) + "\n")

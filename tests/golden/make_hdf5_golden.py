@@ -183,6 +183,40 @@ def main():
     with h5py.File(os.path.join(OUT, "coverage_latest_chunked.hdf5"), "w", libver="latest") as f:
         f.create_dataset("x", data=np.arange(100), chunks=(10,))  # the reader must refuse this with a clear message
     np.savez_compressed(os.path.join(OUT, "coverage.expected.npz"), **{k: np.asarray(v) for k, (v, _) in cover.items()})
+    write_fuzz()
+
+
+def write_fuzz():
+    """4. straight h5py: fuzz{0,1,2}.hdf5 -- random shapes, dtypes, chunk shapes and filter stacks -- and what was written into each
+    (fuzz{seed}.expected.npz), for test_random_files_from_a_real_h5py_read_back_equal."""
+    dts = ['f4', 'f8', 'f2', 'i8', 'i4', 'i2', 'i1', 'u1', 'u2', 'u4', 'u8', '?', '>f8', '>i2']
+    for seed in range(3):
+        rng = np.random.default_rng(seed)
+        exp = {}
+        with h5py.File(os.path.join(OUT, f"fuzz{seed}.hdf5"), "w") as f:
+            for i in range(24):
+                rank = int(rng.integers(1, 4))
+                shape = tuple(int(x) for x in rng.integers(0 if i % 7 == 0 else 1, [400, 9, 4][:rank]))
+                dt = np.dtype(dts[int(rng.integers(len(dts)))])
+                a = (rng.random(shape) < 0.5) if dt.kind == 'b' else (rng.integers(0, 100, shape).astype(dt))
+                kw = {}
+                mode = int(rng.integers(4))
+                if mode and a.size:
+                    kw['chunks'] = tuple(int(rng.integers(1, max(2, s // 2 + 2))) for s in shape)
+                    if mode >= 2:
+                        kw['compression'] = 'gzip'
+                        kw['compression_opts'] = int(rng.integers(1, 10))
+                    if mode == 3:
+                        kw['shuffle'] = True
+                        kw['fletcher32'] = bool(rng.integers(2))
+                g = f if i % 3 else f.require_group('sub/g%d' % (i % 2))
+                g.create_dataset('d%d' % i, data=a, **kw)
+                exp[(g.name.strip('/') + '/' if g.name != '/' else '') + 'd%d' % i] = a
+            d = f.create_dataset('unwritten', shape=(50, 3), dtype='f4', chunks=(8, 3), fillvalue=1.5)
+            d[8:16] = 2.0
+            exp['unwritten'] = d[:]
+        np.savez_compressed(os.path.join(OUT, f"fuzz{seed}.expected.npz"), **{k.replace('/', '__'): v for k, v in exp.items()})
+        print(f"fuzz{seed}.hdf5", os.path.getsize(os.path.join(OUT, f"fuzz{seed}.hdf5")), "bytes")
 
 
 if __name__ == "__main__":

@@ -209,7 +209,7 @@ def test_bench_two_ranks_on_one_device(gpu):
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--all-ranks-on-device0", "--dist-backend", "gloo",
-                        "--transitions", "2000000", "--rollouts", "256", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"],
+                        "--transitions", "2000000", "--rollouts", "256", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=900, env={k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

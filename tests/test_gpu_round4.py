@@ -72,7 +72,7 @@ def test_rccl_executes_the_allreduce_of_the_estimates_on_one_rank(gpu):
     "nccl" (= RCCL) for its ONE rank (device_id = cuda:0) and runs measure()'s all-reduce of the [R,2] f64 device tensor in every
     pass; a one-rank SUM leaves the table as it was, librccl is mapped into the process, and the line still passes its parity check
     against the oracle.  (Child process: nothing here re-execs after the GPU is initialised.)"""
-    out = _bench(["--transitions", "300000", "--rollouts", "64", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--force-dist"])
+    out = _bench(["--transitions", "300000", "--rollouts", "64", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--force-dist", "--full"])
     c = out["collective"]
     assert c["backend"] == "nccl" and c["world"] == 1 and c["device_tensor"] and c["librccl_mapped"], c
     assert c["unchanged_at_one_rank"] is True and c["bytes"] == 64 * 2 * 8 and c["allreduce_us"] > 0
@@ -110,7 +110,7 @@ def test_bench_line_carries_the_extra_configurations(gpu):
     """bench.py appends C2 (CartPole, box encoder) and C3 (continuous_grid, MLP encoder on MFMA) to the headline line, each with its
     own oracle parity check.  Exercised here at a reduced headline size through the same code (the default sizes run in the driver's
     own bench call): OFFSIM_BENCH_CONFIG_SCALE shrinks the two logs."""
-    out = _bench(["--steps", "1", "--warmup", "0", "--no-cpu-baseline"], env_extra={"OFFSIM_BENCH_TEST_SCALE": "50"}, timeout=900)
+    out = _bench(["--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--full"], env_extra={"OFFSIM_BENCH_TEST_SCALE": "50"}, timeout=900)
     cfg = out["configs"]
     assert set(cfg) == {"C2", "C3", "C4_shard", "C5_shard"}  # (round 5: one GPU's shard of C4 and of C5 are driver-timed lines too)
     for k in cfg:

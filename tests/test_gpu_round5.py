@@ -115,7 +115,7 @@ def test_bench_plumbing_at_world_size_8_on_one_device(gpu):
     episode-disjoint shards with all 4096 seeds on each, the extra rollout-sharded measurement gives every rank 512 seeds of the whole
     log, rank 0 alone prints the line and checks four seeds of ITS shard against the oracle while the others wait in the barrier.
     No scaling number is expected from this -- the plumbing is: shard arithmetic, tile sizing, the [R,2] all-reduce at world 8."""
-    out = _bench(["--gpus", "8", "--all-ranks-on-device0", "--dist-backend", "gloo", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"],
+    out = _bench(["--gpus", "8", "--all-ranks-on-device0", "--dist-backend", "gloo", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--full"],
                  env_extra={"OFFSIM_BENCH_TEST_SCALE": "200"}, timeout=1200)
     assert out["n_gpus"] == 8 and out["scaling"] == "strong" and out["test_scale"] == 200
     c = out["collective"]
@@ -132,7 +132,7 @@ def test_bench_plumbing_at_world_size_8_on_one_device(gpu):
 def test_bench_obs128_workload_alone(gpu):
     """`bench.py --workload obs128` (config C5's shape as its own command): device-generated 128-d fp16 observations, the encoder
     forward on MFMA, an fp16 p_log table, reset + scan with its oracle parity check and the encoder's own roofline object."""
-    out = _bench(["--workload", "obs128", "--transitions", "200000", "--rollouts", "256", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"])
+    out = _bench(["--workload", "obs128", "--transitions", "200000", "--rollouts", "256", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--full"])
     assert out["parity_check"]["ok"] and out["config"]["p_log"] == "float16"
     assert out["roofline"]["bytes_per_candidate"] == 16 and out["encoder"]["argmax_equals_oracle_mlp"] is True
 
@@ -152,7 +152,7 @@ def test_bench_under_torch_distributed_run(gpu):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--all-ranks-on-device0", "--dist-backend", "gloo"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--all-ranks-on-device0", "--dist-backend", "gloo", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]

@@ -221,10 +221,10 @@ def _bench(args, env_extra=None, timeout=900):
 def test_bench_philox_runs_the_row_packed_scan_with_its_own_parity_check(gpu):
     """`bench.py --rng philox`: rocRAND's stream in k_eval_mc_rows (not the generic kernel), checked on four seeds against the oracle fed
     the replayed stream."""
-    out, _ = _bench(["--rng", "philox", "--transitions", "400000", "--rollouts", "256", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"])
+    out, _ = _bench(["--rng", "philox", "--transitions", "400000", "--rollouts", "256", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--full"])
     assert out["config"]["rng"] == "philox" and out["roofline"]["kernel"] == "k_eval_mc_rows"
     assert out["parity_check"]["ok"] and out["parity_check"]["seeds"] == [0, 1]
-    pcg, _ = _bench(["--transitions", "400000", "--rollouts", "256", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-configs"])
+    pcg, _ = _bench(["--transitions", "400000", "--rollouts", "256", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-configs", "--full"])
     assert pcg["parity_check"]["ok"] and pcg["value_estimate_mean"] != out["value_estimate_mean"]  # another sample path
 
 
@@ -232,9 +232,34 @@ def test_bench_philox_runs_the_row_packed_scan_with_its_own_parity_check(gpu):
 def test_bench_c4_shard_as_two_episode_disjoint_parts_and_the_phase_trace(gpu):
     """The default line's C4 shard is evaluated as two episode-disjoint halves (each with its own oracle check, run on host threads beside
     the timed passes); OFFSIM_BENCH_TRACE stamps the command's phases on stderr."""
-    out, err = _bench(["--steps", "1", "--warmup", "0", "--cpu-sample-seconds", "1"], env_extra={"OFFSIM_BENCH_TEST_SCALE": "50", "OFFSIM_BENCH_TRACE": "1"})
+    out, err = _bench(["--steps", "1", "--warmup", "0", "--cpu-sample-seconds", "1", "--full"], env_extra={"OFFSIM_BENCH_TEST_SCALE": "50", "OFFSIM_BENCH_TRACE": "1"})
     c4 = out["configs"]["C4_shard"]
     assert c4["parity_ok"] is True and "2 episode-disjoint parts" in c4["sharding"] and c4["kernel"] == "k_eval_mc_rows"
     assert c4["segment_rows_min_max"][1] <= 65536 and c4["reset_s"] > 0 and c4["scan_s"] > 0
     assert "estimator" not in out and out["cpu_baseline"]["value"] > 0 and "the timed passes" in out["parity_check"]["checked"]
     assert "configuration C4_shard: parity checked" in err and "CPU baseline done" in err
+
+
+@pytest.mark.timeout(900)
+def test_plain_bench_line_is_the_headline_alone_and_dumps_what_the_full_run_checks(gpu, tmp_path):
+    """A plain `bench.py` run reports the headline and what its timed passes measured, nothing of what --full adds; --dump-outputs
+    writes the last timed pass's per-seed results as float64, the same in a plain and a --full run of the same arguments, and equal
+    to the oracle on the seeds the --full run's parity check replays."""
+    args = ["--transitions", "400000", "--rollouts", "256", "--steps", "2", "--warmup", "1"]
+    plain, _ = _bench(args + ["--dump-outputs", str(tmp_path / "plain")])
+    assert plain["steps"] == 2 and plain["warmup"] == 1 and plain["ms_per_step"] > 0 and plain["value"] > 0
+    assert plain["unit"] == "simulated steps/s" and plain["higher_is_better"] is True and plain["dtype"] == "f64"
+    assert not {"parity_check", "cpu_baseline", "configs", "collective", "rollout_sharded"} & set(plain) and "chain" not in plain["roofline"]
+    full, _ = _bench(args + ["--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full")])
+    assert full["parity_check"]["ok"]
+    names = ("sum_g", "n_ep", "steps", "cand", "value_estimate")
+    assert sorted(os.listdir(tmp_path / "plain")) == sorted(k + ".npy" for k in names)
+    got = {}
+    for k in names:
+        got[k] = np.load(tmp_path / "plain" / f"{k}.npy")
+        assert got[k].dtype == np.float64 and got[k].shape == (256,), k
+        assert np.array_equal(got[k], np.load(tmp_path / "full" / f"{k}.npy"), equal_nan=True), k
+    for row in full["parity_check"]["oracle"]:
+        s = row["seed"]
+        assert (got["steps"][s], got["cand"][s], got["n_ep"][s]) == (row["steps"], row["candidates"], row["episodes"]), s
+        assert abs(got["value_estimate"][s] - row["value"]) <= 1e-5, s

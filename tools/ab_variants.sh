@@ -7,7 +7,7 @@ for v in "$@"; do
   if [ "$v" = default ]; then unset OFFSIM_LIB; else export OFFSIM_LIB=$PWD/rl-offline-simulation_amd/csrc/variants/$v; fi
   case "$v" in
     *prof*) timeout 600 python tools/prof_rows.py 10000000 4096 > "$out/$v.prof.txt" 2> "$out/$v.err" ;;
-    *) timeout 900 python bench.py --steps 2 --warmup 1 --no-cpu-baseline > "$out/$v.json" 2> "$out/$v.err" ;;
+    *) timeout 900 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --full > "$out/$v.json" 2> "$out/$v.err" ;;
   esac
   echo "$v rc=$?"
 done

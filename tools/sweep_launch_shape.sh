@@ -4,7 +4,7 @@
 #   tools/sweep_launch_shape.sh OUTFILE ["R waves rows" ...]  -> one line per (rollouts, shape)
 out=$1; shift
 : > "$out"
-B="--steps 2 --warmup 1 --no-cpu-baseline --no-configs"
+B="--steps 2 --warmup 1 --no-cpu-baseline --no-configs --full"
 if [ $# -eq 0 ]; then
   set -- "128 auto auto" "256 auto auto" "256 4 4" "512 auto auto" "512 1 4" "512 4 4" "1024 auto auto" "1024 1 4" "1024 4 4" "2048 auto auto" "2048 4 2" "2048 4 4" "3072 auto auto" "3072 4 4" "4096 auto auto"
 fi
