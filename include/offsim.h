@@ -275,6 +275,19 @@ int offsim_eval_mc(const offsim_table *t, offsim_rollouts *ro, const void *pi, i
                    double gamma, const double *gamma_pow, int64_t n_gamma_pow, int64_t max_episodes,
                    const offsim_evalmc_out *out, void *stream);
 
+/* evalMC_psrs for a policy over OBSERVATIONS (offsim4rl/evaluators/psrs.py:241-271, where p = pi[S] with S the observation, :255;
+ * the policy people evaluate is the PPO actor of offsim4rl/agents/ppo.py:18-27).  Such a policy is asked at two kinds of observation only:
+ * next_obs of the row just accepted (psrs.py:49-51) and obs of the initial row just popped (psrs.py:32-37), so it is two per-row tables:
+ *   p_next [N,nA]  the policy at next_obs of GROUPED row g (table order: caller row orig_idx[g]),
+ *   p_init [N0,nA] the policy at obs of initial row k (caller row init_orig[k]).
+ * The loop is offsim_eval_mc's (same queues, streams, reject rule, prob modes, outputs and status codes) with p_new = p_next[g] of the
+ * previous accepted row, or p_init[k] right after a reset.  Element type: f32 for OFFSIM_PROB_F32 (f32 p_log), f64 otherwise.
+ * out_obs_row [R] (optional): where env.s comes from when the loop stops -- i >= 0: next_obs of caller row i; -2 - i: obs of caller
+ * row i (an initial row, no step accepted since); -1: None (no initial row left).  Left unwritten when the loop ran no reset. */
+int offsim_eval_mc_rows_policy(const offsim_table *t, offsim_rollouts *ro, const void *p_next, const void *p_init, int32_t prob_mode,
+                               int32_t reject_mode, double gamma, const double *gamma_pow, int64_t n_gamma_pow, int64_t max_episodes,
+                               const offsim_evalmc_out *out, int32_t *out_obs_row, void *stream);
+
 /* PSRS_Exo.step (offsim4rl/evaluators/psrs.py:99-117): endogenous state s and exogenous state x have their own queue
  * families; every candidate pops the head of both, the accept/reject test reads the s-row, the accepted s-row gives
  * (r, s', done) and the accepted x-row gives x'.  ts / rs: table grouped by s and its rollout state (rng, cursors,
@@ -442,6 +455,27 @@ int offsim_encode_box(const float *obs, int64_t N, int32_t *out_z, void *stream)
  * out_logits may be NULL. */
 int offsim_encode_mlp(const void *x, int32_t x_dtype, int64_t N, int32_t dO, const float *W1, const float *b1,
                       int32_t H, const float *W2, const float *b2, int32_t nZ, int32_t *out_z, float *out_logits,
+                      void *stream);
+
+/* The policy network of a row-policy evaluation (offsim4rl/agents/ppo.py:18-27, spinup's MLPCategoricalActor: logits_net =
+ * Linear -> act -> ... -> Linear, probs = Categorical(logits=...).probs, a max-subtracted softmax):
+ *   out_probs[m] = softmax(L_n(act(... act(L_1(x[rows[m]])))))   m < M, f32 [M, nA] with nA = the last layer's `out`.
+ * x [n_x, dO] f32 or f16 (x_dtype); rows [M] i32 gather index into x (NULL: row m), an index outside [0, n_x) gives NaN;
+ * layers_host: a HOST array of n_layers (1..4) layers, W [out,in] f32 and b [out] f32 (may be NULL) device pointers in state_dict
+ * layout; the activation sits between layers, not after the last.  f32 arithmetic throughout (fmaf in k order per output).
+ * Supported: dO <= 128, hidden widths <= 256, nA <= 16; anything else is OFFSIM_EINVAL. */
+#define OFFSIM_ACT_IDENTITY 0
+#define OFFSIM_ACT_TANH 1
+#define OFFSIM_ACT_RELU 2
+#define OFFSIM_ACT_LEAKY_RELU 3 /* slope: the negative slope */
+typedef struct offsim_mlp_layer {
+    const float *W; /* [out, in] */
+    const float *b; /* [out] or NULL */
+    int32_t in;
+    int32_t out;
+} offsim_mlp_layer;
+int offsim_policy_mlp(const void *x, int32_t x_dtype, int64_t n_x, int32_t dO, const int32_t *rows, int64_t M,
+                      const offsim_mlp_layer *layers_host, int32_t n_layers, int32_t activation, float slope, float *out_probs,
                       void *stream);
 
 #ifdef __cplusplus

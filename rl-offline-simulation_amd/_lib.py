@@ -59,6 +59,15 @@ class TD(C.Structure):
                 ("tie_mt", _vp), ("beh_arg", _vp)]
 
 
+ACT_IDENTITY, ACT_TANH, ACT_RELU, ACT_LEAKY_RELU = 0, 1, 2, 3
+POLICY_MLP_MAX_LAYERS, POLICY_MLP_MAX_IN, POLICY_MLP_MAX_HIDDEN, POLICY_MLP_MAX_ACTIONS = 4, 128, 256, 16
+
+
+class MLPLayer(C.Structure):
+    """struct offsim_mlp_layer"""
+    _fields_ = [("W", _vp), ("b", _vp), ("in", _i32), ("out", _i32)]
+
+
 MAILBOX_MAX_ACTIONS = 24
 SERVER_CMD_STEP, SERVER_CMD_POP_ONE, SERVER_CMD_EXIT, SERVER_CMD_RESET = 1, 2, 3, 4
 SERVER_STARTING, SERVER_RUNNING, SERVER_EXITED = 1, 2, 3
@@ -118,6 +127,9 @@ SIGNATURES = {
     "offsim_async_faults": (C.c_int, []),
     "offsim_encode_box": (C.c_int, [_vp, _i64, _vp, _vp]),
     "offsim_encode_mlp": (C.c_int, [_vp, _i32, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "offsim_eval_mc_rows_policy": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), _vp, _vp, _i32, _i32, C.c_double, _vp, _i64, _i64,
+                                             C.POINTER(EvalMCOut), _vp, _vp]),
+    "offsim_policy_mlp": (C.c_int, [_vp, _i32, _i64, _i32, _vp, _i64, C.POINTER(MLPLayer), _i32, _i32, C.c_float, _vp, _vp]),
 }
 
 _lib = None

@@ -877,10 +877,21 @@ __device__ __forceinline__ uint32_t mt_bounded(volatile uint32_t *mt, uint32_t &
     return v;
 }
 
-template <typename PL, typename PROB, bool TD>
+// ROWP = true: the row-policy mode (offsim_eval_mc_rows_policy) -- p_new is not pi[slot] but a per-row table: rp.p_next[g] after the
+// accepted grouped row g, rp.p_init[k] right after the reset that popped initial row k (a policy over observations asked at next_obs of
+// the accepted row, psrs.py:49-51, or at obs of the popped initial row, :32-37).  No pi block in LDS; rp.obs_row gets which row the
+// environment's observation comes from when the loop stops.
+struct RowPolicyArgs {
+    const void *p_next, *p_init;
+    int32_t *obs_row;
+};
+
+template <typename PL, typename PROB, bool TD, bool ROWP = false>
 __global__ void __launch_bounds__(256, 4) k_eval_mc(offsim_table t, offsim_rollouts ro, const PROB *__restrict__ pi,
                                                  int reject_mode, double gamma, const double *__restrict__ gamma_pow,
-                                                 int64_t n_gamma_pow, int64_t max_episodes, offsim_evalmc_out out, offsim_td td) {
+                                                 int64_t n_gamma_pow, int64_t max_episodes, offsim_evalmc_out out, offsim_td td,
+                                                 RowPolicyArgs rp) {
+    static_assert(!(TD && ROWP), "the learner drivers index their tables by state");
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const int waves = blockDim.x / WAVE;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE), lane = threadIdx.x & (WAVE - 1);  // uniform -> SGPR
@@ -889,13 +900,14 @@ __global__ void __launch_bounds__(256, 4) k_eval_mc(offsim_table t, offsim_rollo
     Jump *tables = (Jump *)lds_raw;
     double *q_lds = (double *)(tables + waves * (WAVE + 1)) + (TD ? (size_t)wave * n_slots * nA : 0);
     PROB *pi_lds = (PROB *)((double *)(tables + waves * (WAVE + 1)) + (TD ? (size_t)waves * n_slots * nA : 0));
-    uint32_t *seg_lds = (uint32_t *)(pi_lds + (size_t)n_slots * nA);
+    uint32_t *seg_lds = (uint32_t *)(pi_lds + (ROWP ? 0 : (size_t)n_slots * nA));
     uint32_t *cur_lds = seg_lds + (n_slots + 1) + (size_t)wave * n_slots;
     // TD with an epsilon-greedy behaviour policy: this rollout's action distribution in its current state, rebuilt from its Q row before every step
     double *beh_lds = (double *)(((uintptr_t)(seg_lds + (n_slots + 1) + (size_t)waves * n_slots) + 7) & ~(uintptr_t)7) + (size_t)wave * nA;
     // TD: this rollout's copy of the tie-breaking MT19937 stream (624 words; the position is kept in a register)
     volatile uint32_t *mt_lds = (volatile uint32_t *)(((double *)(((uintptr_t)(seg_lds + (n_slots + 1) + (size_t)waves * n_slots) + 7) & ~(uintptr_t)7)) + (size_t)waves * nA) + (size_t)wave * 624;
-    for (int i = threadIdx.x; i < n_slots * nA; i += blockDim.x) pi_lds[i] = pi[i];
+    if (!ROWP)
+        for (int i = threadIdx.x; i < n_slots * nA; i += blockDim.x) pi_lds[i] = pi[i];
     for (int i = threadIdx.x; i <= n_slots; i += blockDim.x) seg_lds[i] = t.seg_off[i];
     __syncthreads();
     const int r = blockIdx.x * waves + wave;
@@ -926,22 +938,31 @@ __global__ void __launch_bounds__(256, 4) k_eval_mc(offsim_table t, offsim_rollo
     double sum_g = 0.0;
     int status = OFFSIM_ST_OK;
     bool terminate = false;
+    // ROWP: the row whose probabilities the next step uses (grouped row of the last accepted step, or -1: the initial row k_init)
+    const PROB *__restrict__ p_next = (const PROB *)rp.p_next;
+    const PROB *__restrict__ p_init = (const PROB *)rp.p_init;
+    int32_t g_prev = -1;
+    uint32_t k_init = 0;
+    bool no_init = false;
     while (ep < max_episodes && !terminate) {
         // env.reset()  (psrs.py:32-37, :249-252)
         if ((int64_t)ic >= t.N0) {
             status = OFFSIM_ST_NO_INIT;
             slot = -1;
+            no_init = true;
             break;
         }
         uint32_t k = init_row ? init_row[ic] : ic;
         ic++;
         slot = t.init_slot[k];
+        g_prev = -1;
+        k_init = k;
         double G = 0.0;
         int64_t tt = 0;
         bool done = false;
         while (!done) {
             const double gp = discount_at(gamma_pow, (uint64_t)n_gamma_pow, gamma, (uint64_t)tt);  // issued ahead of the step
-            const PROB *p_step = pi_lds + (size_t)slot * nA;
+            const PROB *p_step = ROWP ? (g_prev >= 0 ? p_next + (int64_t)g_prev * nA : p_init + (int64_t)k_init * nA) : pi_lds + (size_t)slot * nA;
             if (TD && td.behaviour != OFFSIM_BEHAVIOUR_FIXED) {
                 // the learner's own behaviour policy on its Q row (offsim4rl/agents/tabular.py), rebuilt in LDS before every step
                 const double *qs = q_lds + (size_t)slot * nA;
@@ -1017,6 +1038,7 @@ __global__ void __launch_bounds__(256, 4) k_eval_mc(offsim_table t, offsim_rollo
             tt++;
             steps++;
             slot = s.z_next;
+            g_prev = s.g;
             done = s.done;
         }
         if (status == OFFSIM_ST_KEYERROR) break;  // the reference raises out of evalMC_psrs here
@@ -1045,6 +1067,11 @@ __global__ void __launch_bounds__(256, 4) k_eval_mc(offsim_table t, offsim_rollo
     if (lane == 0) {
         ro.init_cursor[r] = ic;
         ro.cur_slot[r] = slot;
+        if (ROWP && rp.obs_row) {  // env.s: next_obs of the last accepted row, obs of the initial row when none was accepted since, None
+            // (left as the caller filled it when the loop never reached a reset: max_episodes <= 0)
+            if (no_init) rp.obs_row[r] = -1;
+            else if (n_len > 0 || g_prev >= 0 || status != OFFSIM_ST_OK) rp.obs_row[r] = g_prev >= 0 ? t.orig_idx[g_prev] : -2 - t.init_orig[k_init];
+        }
         if (consumed && ro.rng_kind == OFFSIM_STREAM_PHILOX) {
             ro.rng[4 * r + 1] = base.lo + consumed;
         } else if (consumed) {
@@ -1366,7 +1393,48 @@ extern "C" int offsim_eval_mc(const offsim_table *t, offsim_rollouts *ro, const 
         if (lds > 64 * 1024)                                                                                         \
             HIP_TRY(allow_big_lds((k_eval_mc<PL, PROB, false>), (int)lds)); \
         hipLaunchKernelGGL((k_eval_mc<PL, PROB, false>), grid, block, lds, st, *t, *ro, (const PROB *)pi, reject_mode, gamma, \
-                           gamma_pow, n_gamma_pow, max_episodes, *out, offsim_td{});                                 \
+                           gamma_pow, n_gamma_pow, max_episodes, *out, offsim_td{}, RowPolicyArgs{});                \
+    } while (0)
+    if (prob_mode == OFFSIM_PROB_F32) LAUNCH_MC(float, float);
+    else if (t->plog_dtype == OFFSIM_F32) LAUNCH_MC(float, double);
+    else if (t->plog_dtype == OFFSIM_F64) LAUNCH_MC(double, double);
+    else LAUNCH_MC(__half, double);
+#undef LAUNCH_MC
+    LAUNCH_CHECK();
+    return OFFSIM_OK;
+}
+
+// ---- evalMC_psrs for a policy over observations (psrs.py:241-271 with pi[S] at S = the observation, psrs.py:255): the loop of
+// offsim_eval_mc with p_new taken from per-row tables instead of pi[slot] (k_eval_mc<..., ROWP = true>).
+extern "C" int offsim_eval_mc_rows_policy(const offsim_table *t, offsim_rollouts *ro, const void *p_next, const void *p_init,
+                                          int32_t prob_mode, int32_t reject_mode, double gamma, const double *gamma_pow,
+                                          int64_t n_gamma_pow, int64_t max_episodes, const offsim_evalmc_out *out, int32_t *out_obs_row,
+                                          void *stream) {
+    int rc = check_table(t);
+    if (rc) return rc;
+    if (!ro || ro->R < 0 || !out) return fail(OFFSIM_EINVAL, "eval_mc_rows_policy: bad argument%s");
+    if ((t->N > 0 && !p_next) || (t->N0 > 0 && !p_init)) return fail(OFFSIM_EINVAL, "eval_mc_rows_policy: p_next / p_init is NULL%s");
+    if (t->N0 > 0 && (!t->init_slot || !t->init_orig)) return fail(OFFSIM_EINVAL, "eval_mc_rows_policy: table has no init rows%s");
+    if (!out->sum_g || !out->n_ep || !out->steps || !out->cand || !out->n_len || !out->status)
+        return fail(OFFSIM_EINVAL, "eval_mc_rows_policy: required output is NULL%s");
+    if (ro->R == 0) return OFFSIM_OK;
+    if (prob_mode != OFFSIM_PROB_F32 && prob_mode != OFFSIM_PROB_F64) return fail(OFFSIM_EINVAL, "eval_mc_rows_policy: bad prob_mode%s");
+    if (prob_mode == OFFSIM_PROB_F32 && t->plog_dtype != OFFSIM_F32)
+        return fail(OFFSIM_EINVAL, "eval_mc_rows_policy: OFFSIM_PROB_F32 needs an f32 p_log%s");
+    if (n_gamma_pow > 0 && !gamma_pow) return fail(OFFSIM_EINVAL, "eval_mc_rows_policy: gamma_pow is NULL%s");
+    hipStream_t st = (hipStream_t)stream;
+    int waves = 4;
+    while (waves > 1 && evalmc_lds_bytes(waves, t->n_slots, t->nA, 0) > 64 * 1024) waves >>= 1;
+    size_t lds = evalmc_lds_bytes(waves, t->n_slots, t->nA, 0);  // (no pi block)
+    if (lds > 160 * 1024) return fail(OFFSIM_EUNSUPPORTED, "eval_mc_rows_policy: per-state cursors exceed 160 KiB of LDS%s");
+    dim3 grid((ro->R + waves - 1) / waves), block(waves * WAVE);
+    const RowPolicyArgs rp{p_next, p_init, out_obs_row};
+#define LAUNCH_MC(PL, PROB)                                                                                          \
+    do {                                                                                                             \
+        if (lds > 64 * 1024)                                                                                         \
+            HIP_TRY(allow_big_lds((k_eval_mc<PL, PROB, false, true>), (int)lds));                                     \
+        hipLaunchKernelGGL((k_eval_mc<PL, PROB, false, true>), grid, block, lds, st, *t, *ro, (const PROB *)nullptr, \
+                           reject_mode, gamma, gamma_pow, n_gamma_pow, max_episodes, *out, offsim_td{}, rp);          \
     } while (0)
     if (prob_mode == OFFSIM_PROB_F32) LAUNCH_MC(float, float);
     else if (t->plog_dtype == OFFSIM_F32) LAUNCH_MC(float, double);
@@ -1640,7 +1708,7 @@ extern "C" int offsim_eval_td(const offsim_table *t, offsim_rollouts *ro, const 
         if (lds > 64 * 1024)                                                                                            \
             HIP_TRY(allow_big_lds((k_eval_mc<PL, double, true>), (int)lds)); \
         hipLaunchKernelGGL((k_eval_mc<PL, double, true>), grid, block, lds, st, *t, *ro, pi, reject_mode, gamma, gamma_pow, \
-                           n_gamma_pow, max_episodes, *out, *td);                                                       \
+                           n_gamma_pow, max_episodes, *out, *td, RowPolicyArgs{});                                      \
     } while (0)
     if (t->plog_dtype == OFFSIM_F32) LAUNCH_TD(float);
     else if (t->plog_dtype == OFFSIM_F64) LAUNCH_TD(double);
@@ -2151,6 +2219,56 @@ extern "C" int offsim_encode_mlp(const void *x, int32_t x_dtype, int64_t N, int3
         if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_encode_mlp<__half>), (int)lds));
         hipLaunchKernelGGL(k_encode_mlp<__half>, dim3(nb), dim3(256), lds, st, (const __half *)x, N, dO, W1, b1, H, W2, b2, nZ, out_z, out_logits);
     } else return fail(OFFSIM_EINVAL, "encode_mlp: x_dtype must be OFFSIM_F32 or OFFSIM_F16%s");
+    LAUNCH_CHECK();
+    return OFFSIM_OK;
+}
+
+// ---- the policy network of a row-policy evalMC: probs = softmax(MLP(x[rows])) (csrc/policy_mlp.hpp) ----
+#include "policy_mlp.hpp"
+
+extern "C" int offsim_policy_mlp(const void *x, int32_t x_dtype, int64_t n_x, int32_t dO, const int32_t *rows, int64_t M,
+                                 const offsim_mlp_layer *layers_host, int32_t n_layers, int32_t activation, float slope, float *out_probs,
+                                 void *stream) {
+    if (M < 0 || n_x < 0 || dO <= 0 || !layers_host) return fail(OFFSIM_EINVAL, "policy_mlp: bad argument%s");
+    if (x_dtype != OFFSIM_F32 && x_dtype != OFFSIM_F16) return fail(OFFSIM_EINVAL, "policy_mlp: x_dtype must be OFFSIM_F32 or OFFSIM_F16%s");
+    if (n_layers < 1 || n_layers > PMLP_MAX_LAYERS) return fail(OFFSIM_EINVAL, "policy_mlp: 1 to 4 Linear layers%s");
+    if (activation != OFFSIM_ACT_IDENTITY && activation != OFFSIM_ACT_TANH && activation != OFFSIM_ACT_RELU && activation != OFFSIM_ACT_LEAKY_RELU)
+        return fail(OFFSIM_EINVAL, "policy_mlp: unknown activation%s");
+    if (dO > PMLP_MAX_IN) return fail(OFFSIM_EINVAL, "policy_mlp: observation width above 128%s");
+    PmlpLayers L{};
+    L.n = n_layers;
+    L.w_max = dO;
+    L.w_floats = 0;
+    for (int l = 0; l < n_layers; l++) {
+        const offsim_mlp_layer &y = layers_host[l];
+        if (!y.W) return fail(OFFSIM_EINVAL, "policy_mlp: a layer's W is NULL%s");
+        if (y.in != (l == 0 ? dO : layers_host[l - 1].out)) return fail(OFFSIM_EINVAL, "policy_mlp: layer widths do not chain%s");
+        const bool last = l == n_layers - 1;
+        if (y.out < 1 || y.out > (last ? PMLP_MAX_ACTIONS : PMLP_MAX_HIDDEN))
+            return fail(OFFSIM_EINVAL, last ? "policy_mlp: more than 16 actions%s" : "policy_mlp: hidden width above 256%s");
+        L.W[l] = y.W;
+        L.b[l] = y.b;
+        L.in[l] = y.in;
+        L.out[l] = y.out;
+        if (y.out > L.w_max) L.w_max = y.out;
+        const int chunk = y.out * (y.in + 1);
+        const int need = chunk < PMLP_W_FLOATS ? chunk : PMLP_W_FLOATS;
+        if (need > L.w_floats) L.w_floats = need;
+    }
+    if (M == 0) return OFFSIM_OK;
+    if (!x || !out_probs) return fail(OFFSIM_EINVAL, "policy_mlp: x / out_probs is NULL%s");
+    const size_t lds = policy_mlp_lds_bytes(L);
+    const uint64_t nb = (uint64_t)((M + PMLP_TM - 1) / PMLP_TM);
+    if (nb > 0x7fffffffull) return fail(OFFSIM_EINVAL, "policy_mlp: too many rows%s");
+    hipStream_t st = (hipStream_t)stream;
+    const float sl = slope;
+    if (x_dtype == OFFSIM_F32) {
+        if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_policy_mlp<float>), (int)lds));
+        hipLaunchKernelGGL(k_policy_mlp<float>, dim3((unsigned)nb), dim3(256), lds, st, (const float *)x, n_x, dO, rows, M, L, activation, sl, out_probs);
+    } else {
+        if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_policy_mlp<__half>), (int)lds));
+        hipLaunchKernelGGL(k_policy_mlp<__half>, dim3((unsigned)nb), dim3(256), lds, st, (const __half *)x, n_x, dO, rows, M, L, activation, sl, out_probs);
+    }
     LAUNCH_CHECK();
     return OFFSIM_OK;
 }

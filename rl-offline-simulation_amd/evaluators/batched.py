@@ -631,6 +631,41 @@ class BatchedPSRS:
             o["_kernel"] = "k_eval_mc"
         return o
 
+    # -- evalMC_psrs for a policy over observations (psrs.py:241-271, p = pi[S] at the observation S) for all rollouts in one launch --
+    def eval_mc_rows_policy(self, p_next, p_init, gamma, n_episodes=None, ep_cap=0, trace_cap=0, n_gamma_pow=4096):
+        """p_next [N,nA]: the policy at next_obs of every GROUPED row (table order); p_init [N0,nA]: at obs of every initial row
+        (table.init_orig order) -- what obs_policy.*Policy.row_tables returns.  f32 tables with an f32 p_log run the f32 mode, anything
+        else is widened exactly to f64.  Returns the dict of eval_mc plus obs_row [R] (include/offsim.h, offsim_eval_mc_rows_policy:
+        where each rollout's observation comes from when its loop stopped)."""
+        self._quiesce()
+        self._orders_for_generic()
+        t, dev, R = self.table, self.table.device, self.R
+        mode = _prob_mode(t, p_next.dtype if p_next.dtype == p_init.dtype else torch.float64)
+        dt = torch.float32 if mode == L.PROB_F32 else torch.float64
+        pn = p_next.to(device=dev, dtype=dt).reshape(t.N, t.nA).contiguous()
+        p0 = p_init.to(device=dev, dtype=dt).reshape(t.N0, t.nA).contiguous()
+        if n_episodes is None:
+            n_episodes = 1 << 62
+        o = {k: torch.empty(R, dtype=dt_, device=dev) for k, dt_ in (("sum_g", torch.float64), ("n_ep", torch.int64), ("steps", torch.int64),
+                                                                    ("cand", torch.int64), ("n_len", torch.int64), ("status", torch.int32))}
+        o["obs_row"] = torch.full((R,), -(1 << 31), dtype=torch.int32, device=dev)
+        if ep_cap:
+            o["ep_g"] = torch.zeros((R, ep_cap), dtype=torch.float64, device=dev)
+            o["ep_len"] = torch.zeros((R, ep_cap + 1), dtype=torch.int32, device=dev)
+        if trace_cap:
+            o["trace_row"] = torch.full((R, trace_cap), -1, dtype=torch.int32, device=dev)
+            o["trace_pop"] = torch.zeros((R, trace_cap), dtype=torch.int32, device=dev)
+        gp = _gamma_pow(gamma, n_gamma_pow, dev, cap=t.N + 2)
+        oc = L.EvalMCOut(sum_g=L.ptr(o["sum_g"]), n_ep=L.ptr(o["n_ep"]), steps=L.ptr(o["steps"]), cand=L.ptr(o["cand"]),
+                         n_len=L.ptr(o["n_len"]), status=L.ptr(o["status"]), ep_g=L.ptr(o.get("ep_g")), ep_len=L.ptr(o.get("ep_len")),
+                         ep_cap=ep_cap, trace_row=L.ptr(o.get("trace_row")), trace_pop=L.ptr(o.get("trace_pop")), trace_cap=trace_cap)
+        L.check(L.load().offsim_eval_mc_rows_policy(C.byref(t.c), C.byref(self.state.c), L.ptr(pn) if t.N else None, L.ptr(p0) if t.N0 else None,
+                                                    mode, self.reject_mode, float(gamma), L.ptr(gp), gp.numel(), int(n_episodes), C.byref(oc),
+                                                    L.ptr(o["obs_row"]), L.stream_ptr()))
+        o["_keepalive"] = (pn, p0, gp)
+        o["_kernel"] = "k_eval_mc_rows_policy"
+        return o
+
     # -- qlearn_psrs / expSARSA_psrs (psrs.py:119-239) with a Q-independent behaviour policy, all rollouts in one launch --
     def eval_td(self, pi_slots, gamma, mode, alpha, q_slots=None, n_episodes=None, ep_cap=0, trace_cap=0, n_gamma_pow=4096,
                 behaviour=L.BEHAVIOUR_FIXED, epsilon=0.0, alpha_ep=None, epsilon_ep=None, snap_cap=0, snap_stride=1, tie_mt=None):
@@ -748,12 +783,18 @@ def resident_rollouts(table, keyed=True, free_bytes=None):
 
 
 def evalmc_rollouts(table, seeds, pi, gamma, shuffle=SHUFFLE_PER_ROLLOUT, shuffle_seed=None, tile=None,
-                    reject_mode=L.REJECT_DEFAULT, n_episodes=None):
+                    reject_mode=L.REJECT_DEFAULT, n_episodes=None, obs=None, next_obs=None):
     """evalMC_psrs for many sampler seeds.  Rollouts are processed in tiles of `tile` seeds so that the per-rollout queue orders
     (rollout_resident_bytes each) fit the device's free memory.  Returns host arrays: sum_g, n_ep, steps, cand, status
-    and value = sum_g / n_ep (the per-seed value estimate, Gs.mean())."""
+    and value = sum_g / n_ep (the per-seed value estimate, Gs.mean()).
+    `pi` may also be a policy over observations (evaluators/obs_policy.py: MLPPolicy, RowPolicy, CallablePolicy), with the log's
+    observations `obs` / `next_obs` [N, dO] in caller order: its per-row tables are computed once and every tile runs the row-policy
+    scan (offsim_eval_mc_rows_policy) on permutations."""
     seeds = np.asarray(seeds, dtype=np.uint64)
     R = len(seeds)
+    from .obs_policy import ObsPolicy
+    if isinstance(pi, ObsPolicy):
+        return _evalmc_rollouts_rows_policy(table, seeds, pi, gamma, shuffle, shuffle_seed, tile, reject_mode, n_episodes, obs, next_obs)
     if tile is None:
         tile = R if shuffle != SHUFFLE_PER_ROLLOUT else int(max(1, min(R, resident_rollouts(table, keyed=True)[0])))
     pi_slots = table.policy_slots(pi)
@@ -765,6 +806,31 @@ def evalmc_rollouts(table, seeds, pi, gamma, shuffle=SHUFFLE_PER_ROLLOUT, shuffl
             env = BatchedPSRS(table, len(sd), reject_mode)
         env.reset_sampler(sd, shuffle, shuffle_seed, policy=pi_slots)
         o = env.eval_mc(pi_slots, gamma, n_episodes)
+        for k in outs:
+            outs[k].append(o[k].cpu().numpy())
+        L.check_async_faults()  # (the copies above synchronised the stream)
+    res = {k: np.concatenate(v) for k, v in outs.items()}
+    with np.errstate(invalid="ignore", divide="ignore"):
+        res["value"] = res["sum_g"] / res["n_ep"]
+    return res
+
+
+def _evalmc_rollouts_rows_policy(table, seeds, pi, gamma, shuffle, shuffle_seed, tile, reject_mode, n_episodes, obs, next_obs):
+    R = len(seeds)
+    if (obs is None or next_obs is None) and not hasattr(pi, "p_next"):
+        raise ValueError("evalmc_rollouts: a policy over observations needs the log's obs= and next_obs=")
+    p_next, p_init = pi.row_tables(table, obs, next_obs)
+    if tile is None:
+        tile = R if shuffle != SHUFFLE_PER_ROLLOUT else int(max(1, min(R, resident_rollouts(table, keyed=False)[0])))
+    outs = {k: [] for k in ("sum_g", "n_ep", "steps", "cand", "status")}
+    env = None
+    for b in range(0, R, tile):
+        sd = seeds[b:b + tile]
+        if env is None or env.R != len(sd):
+            env = BatchedPSRS(table, len(sd), reject_mode)
+        env.reset_sampler(sd, shuffle, shuffle_seed)
+        env._orders_for_generic()
+        o = env.eval_mc_rows_policy(p_next, p_init, gamma, n_episodes)
         for k in outs:
             outs[k].append(o[k].cpu().numpy())
         L.check_async_faults()  # (the copies above synchronised the stream)

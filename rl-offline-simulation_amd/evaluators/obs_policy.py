@@ -1,0 +1,194 @@
+"""Policies over observations for evalMC_psrs (offsim4rl/evaluators/psrs.py:241-271 with p = pi[S], S the observation, :255).
+
+The reference indexes any `pi` by the observation, so the policy people evaluate there is the PPO actor it trains inside PSRS
+(offsim4rl/agents/ppo.py:18-27: spinup's MLPCategoricalActor, probs = softmax(logits_net(obs))).  Inside evalMC the policy is only
+ever asked at two kinds of observation -- next_obs of the row just accepted (psrs.py:49-51) and obs of the initial row just popped
+(psrs.py:32-37) -- so a policy over observations is exactly two per-row probability tables, computed once, up front:
+
+  P_next[g]  the policy at next_obs of GROUPED row g (the table's order, caller row table.order[g])
+  P_init[k]  the policy at obs of the k-th initial row (caller row table.init_orig[k])
+
+and the scan (offsim_eval_mc_rows_policy) takes p_new from them instead of pi[slot].  Every policy class here produces that pair on the
+device (`row_tables`):
+
+  MLPPolicy        Linear / activation stacks, forward by the HIP kernel offsim_policy_mlp, written straight in grouped order
+                   (its `rows` gather index is table.order for P_next and table.init_orig for P_init: no second gather pass)
+  RowPolicy        per-row probabilities the caller already has, in caller order (gathered into the two tables on the device)
+  CallablePolicy   any fn(obs_tensor) -> probs, run by torch on the device in chunks (plumbing: the scan is still the HIP kernel)
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from .. import _lib as L
+from ..table import gather_rows
+
+_ACT = {"tanh": L.ACT_TANH, "relu": L.ACT_RELU, "leaky_relu": L.ACT_LEAKY_RELU, "identity": L.ACT_IDENTITY}
+
+
+def obs_tensor(obs, device):
+    """Observations [N, dO] as one contiguous device tensor (f16 kept, anything else f32)."""
+    if isinstance(obs, torch.Tensor):
+        t = obs.to(device)
+    else:
+        a = np.asarray(obs) if not isinstance(obs, (list, tuple)) else np.stack([np.asarray(o) for o in obs]) if len(obs) else np.zeros((0, 1))
+        t = torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    if t.dtype not in (torch.float32, torch.float16):
+        t = t.to(torch.float32)
+    return t.reshape(t.shape[0], -1).contiguous()
+
+
+class ObsPolicy:
+    """Base: a policy over observations, turned into (P_next grouped [N, nA], P_init [N0, nA]) device tensors for a table."""
+
+    def row_tables(self, table, obs, next_obs):
+        raise NotImplementedError
+
+
+class MLPPolicy(ObsPolicy):
+    """probs = softmax(L_n(act(... act(L_1(obs))))) -- spinup's MLPCategoricalActor (ppo.py:18-27) -- on the HIP forward.
+
+    weights: list of (W [out, in], b [out] or None), state_dict layout; activation: 'tanh' | 'relu' | 'leaky_relu' | 'identity' between
+    layers (slope: leaky_relu's negative slope).  1-4 layers, observation width <= 128, hidden widths <= 256, <= 16 actions."""
+
+    def __init__(self, weights, activation="tanh", slope=0.01):
+        if activation not in _ACT:
+            raise ValueError(f"MLPPolicy: activation must be one of {sorted(_ACT)}, got {activation!r}")
+        if not 1 <= len(weights) <= L.POLICY_MLP_MAX_LAYERS:
+            raise ValueError(f"MLPPolicy: 1 to {L.POLICY_MLP_MAX_LAYERS} Linear layers, got {len(weights)}")
+        self.weights = []
+        for W, b in weights:
+            W = torch.as_tensor(W.detach() if isinstance(W, torch.Tensor) else np.asarray(W)).to(torch.float32).contiguous()
+            b = None if b is None else torch.as_tensor(b.detach() if isinstance(b, torch.Tensor) else np.asarray(b)).to(torch.float32).contiguous()
+            if W.dim() != 2 or (b is not None and b.shape != (W.shape[0],)):
+                raise ValueError("MLPPolicy: every layer is (W [out, in], b [out] or None)")
+            self.weights.append((W, b))
+        for (W0, _), (W1, _) in zip(self.weights, self.weights[1:]):
+            if W1.shape[1] != W0.shape[0]:
+                raise ValueError("MLPPolicy: layer widths do not chain")
+        self.activation, self.slope = activation, float(slope)
+        self.nA = int(self.weights[-1][0].shape[0])
+        self.dO = int(self.weights[0][0].shape[1])
+        self._dev = {}
+
+    @classmethod
+    def from_torch(cls, m):
+        """An nn.Sequential of Linear and Tanh | ReLU | LeakyReLU | Identity (one activation kind, between the Linear layers), or any object
+        with such a `.logits_net` (spinup's MLPCategoricalActor).  Anything else is refused."""
+        net = m.logits_net if hasattr(m, "logits_net") else m
+        if not isinstance(net, torch.nn.Sequential):
+            raise TypeError(f"MLPPolicy.from_torch: needs an nn.Sequential (or an object with .logits_net), got {type(m).__name__}")
+        kinds = {torch.nn.Tanh: "tanh", torch.nn.ReLU: "relu", torch.nn.LeakyReLU: "leaky_relu", torch.nn.Identity: "identity"}
+        layers, acts, slope, expect_linear = [], [], 0.01, True
+        for mod in net:
+            if isinstance(mod, torch.nn.Linear):
+                if not expect_linear and layers:
+                    raise TypeError("MLPPolicy.from_torch: two Linear layers without an activation between them")
+                layers.append((mod.weight, mod.bias))
+                expect_linear = False
+            elif type(mod) in kinds:
+                if expect_linear:
+                    raise TypeError("MLPPolicy.from_torch: an activation must follow a Linear layer")
+                acts.append(kinds[type(mod)])
+                if isinstance(mod, torch.nn.LeakyReLU):
+                    slope = float(mod.negative_slope)
+                expect_linear = True
+            else:
+                raise TypeError(f"MLPPolicy.from_torch: unsupported module {type(mod).__name__} (Linear, Tanh, ReLU, LeakyReLU, Identity only)")
+        if not layers or expect_linear:
+            raise TypeError("MLPPolicy.from_torch: the network must end with a Linear layer (its outputs are the logits)")
+        if len(set(acts)) > 1:
+            raise TypeError(f"MLPPolicy.from_torch: one activation kind between all layers, got {acts}")
+        if acts and acts[0] == "leaky_relu" and len({float(x.negative_slope) for x in net if isinstance(x, torch.nn.LeakyReLU)}) > 1:
+            raise TypeError("MLPPolicy.from_torch: LeakyReLU layers with different slopes")
+        return cls(layers, acts[0] if acts else "identity", slope)
+
+    def _device_weights(self, device):
+        key = str(device)
+        if key not in self._dev:
+            ws = [(W.to(device), None if b is None else b.to(device)) for W, b in self.weights]
+            arr = (L.MLPLayer * len(ws))()
+            for i, (W, b) in enumerate(ws):
+                arr[i].W, arr[i].b = L.ptr(W), L.ptr(b)
+                setattr(arr[i], "in", int(W.shape[1]))
+                arr[i].out = int(W.shape[0])
+            self._dev[key] = (ws, arr)
+        return self._dev[key]
+
+    def forward(self, x, rows=None, out=None):
+        """probs [M, nA] f32 on x's device: x [n, dO] f32 / f16 device tensor, rows (optional) [M] int32 gather index into x."""
+        if x.dim() != 2 or x.shape[1] != self.dO:
+            raise ValueError(f"MLPPolicy: observations of width {self.dO} expected, got shape {tuple(x.shape)}")
+        if x.dtype not in (torch.float32, torch.float16):
+            x = x.to(torch.float32)
+        x = x.contiguous()
+        if rows is not None:
+            rows = rows.to(device=x.device, dtype=torch.int32).contiguous()
+        M = int(x.shape[0]) if rows is None else int(rows.numel())
+        if out is None:
+            out = torch.empty((M, self.nA), dtype=torch.float32, device=x.device)
+        ws, arr = self._device_weights(x.device)
+        L.check(L.load().offsim_policy_mlp(L.ptr(x) if x.numel() else None, L.F32 if x.dtype == torch.float32 else L.F16, int(x.shape[0]),
+                                           self.dO, L.ptr(rows) if rows is not None and M else None, M, arr, len(ws), _ACT[self.activation],
+                                           self.slope, L.ptr(out) if M else None, L.stream_ptr()))
+        return out
+
+    def row_tables(self, table, obs, next_obs):
+        xn, x0 = obs_tensor(next_obs, table.device), obs_tensor(obs, table.device)
+        return self.forward(xn, table.order), self.forward(x0, table.init_orig)
+
+
+class RowPolicy(ObsPolicy):
+    """Per-row probabilities in caller order: p_next[i] = the policy at next_obs[i], p_init[i] = the policy at obs[i] (only the rows with
+    t == 0 are read).  f32 tables with an f32 p_log run the scan's f32 mode, anything else is widened exactly to f64."""
+
+    def __init__(self, p_next, p_init):
+        self.p_next, self.p_init = p_next, p_init
+
+    @staticmethod
+    def _dev(p, device):
+        t = p.to(device) if isinstance(p, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(p)).to(device)
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.to(torch.float64)
+        return t.contiguous()
+
+    def row_tables(self, table, obs=None, next_obs=None):
+        pn, p0 = self._dev(self.p_next, table.device), self._dev(self.p_init, table.device)
+        if pn.dtype != p0.dtype:
+            pn, p0 = pn.to(torch.float64), p0.to(torch.float64)
+        for name, p in (("p_next", pn), ("p_init", p0)):
+            if p.dim() != 2 or p.shape[0] != table.N or p.shape[1] != table.nA:
+                raise ValueError(f"RowPolicy: {name} must be [{table.N}, {table.nA}] (one row per logged transition), got {tuple(p.shape)}")
+        return gather_rows(pn, table.order), gather_rows(p0, table.init_orig)
+
+
+class CallablePolicy(ObsPolicy):
+    """fn(obs [m, dO] device tensor) -> probs [m, nA], evaluated by torch on the device in chunks of `chunk` rows (under no_grad)."""
+
+    def __init__(self, fn, chunk=1 << 16):
+        self.fn, self.chunk = fn, int(chunk)
+
+    def _run(self, x):
+        outs = []
+        with torch.no_grad():
+            for b in range(0, int(x.shape[0]), self.chunk):
+                p = self.fn(x[b:b + self.chunk])
+                if hasattr(p, "probs") and not isinstance(p, torch.Tensor):  # a torch Distribution (Categorical)
+                    p = p.probs
+                outs.append(torch.as_tensor(p, device=x.device))
+        if not outs:
+            return None
+        p = torch.cat(outs)
+        return p if p.dtype in (torch.float32, torch.float64) else p.to(torch.float64)
+
+    def row_tables(self, table, obs, next_obs):
+        xn, x0 = obs_tensor(next_obs, table.device), obs_tensor(obs, table.device)
+        pn = self._run(xn[table.order.to(torch.int64)])
+        p0 = self._run(x0[table.init_orig.to(torch.int64)])
+        empty = torch.zeros((0, table.nA), dtype=(pn if pn is not None else p0 if p0 is not None else torch.zeros(0)).dtype, device=table.device)
+        pn = empty if pn is None else pn
+        p0 = empty if p0 is None else p0
+        if pn.dtype != p0.dtype:
+            pn, p0 = pn.to(torch.float64), p0.to(torch.float64)
+        return pn.reshape(-1, table.nA).contiguous(), p0.reshape(-1, table.nA).contiguous()

@@ -217,7 +217,12 @@ def _require_device_env(env, what):
 
 
 def evalMC_psrs(env, n_episodes, pi, gamma):
-    """psrs.py:241-271: the whole loop -- env.reset(), env.step(pi[S]) until exhaustion, discounted returns -- in one kernel launch."""
+    """psrs.py:241-271: the whole loop -- env.reset(), env.step(pi[S]) until exhaustion, discounted returns -- in one kernel launch.
+    `pi`: a [nS, nA] table indexed by the latent state (observations == states), or a policy over observations (obs_policy.py:
+    MLPPolicy, RowPolicy, CallablePolicy), which also runs on a PSRS whose observations are not its states."""
+    from .obs_policy import ObsPolicy
+    if isinstance(pi, ObsPolicy):
+        return _evalmc_obs_policy(env, n_episodes, pi, gamma)
     _require_device_env(env, "evalMC_psrs")
     pi = np.asarray(pi)
     if pi.ndim != 2:
@@ -237,6 +242,35 @@ def evalMC_psrs(env, n_episodes, pi, gamma):
     env.z = t.z_of(cs) if cs >= 0 else env.z
     if cs < 0:
         env.s = None
+    return o["ep_g"].cpu().numpy()[0, :ne].copy(), o["ep_len"].cpu().numpy()[0, :nl].astype(np.int64)
+
+
+def _evalmc_obs_policy(env, n_episodes, pi, gamma):
+    """evalMC_psrs with a policy over observations: its per-row tables (P_next at next_obs of every grouped row, P_init at obs of every
+    initial row) are computed once, then the row-policy scan runs the loop (offsim_eval_mc_rows_policy)."""
+    if not isinstance(env, PSRS):
+        raise TypeError(f"evalMC_psrs: `env` must be the device-backed PSRS of this package, got {type(env).__name__}")
+    if env._reject_func is not None:
+        raise NotImplementedError("evalMC_psrs: a Python reject hook decides every candidate on the host; drive env.step yourself")
+    t = env.table
+    p_next, p_init = pi.row_tables(t, env._obs, env._next_obs)
+    n_ep = int(min(n_episodes, t.N0 + 1))
+    o = env._env.eval_mc_rows_policy(p_next, p_init, gamma, n_ep, ep_cap=max(n_ep, 1))
+    status = int(o["status"].cpu()[0])
+    env._fault_check = False
+    L.check_async_faults()  # (the copy above synchronised the stream)
+    cs = int(env._env.state.cur_slot.cpu()[0])
+    row = int(o["obs_row"].cpu()[0])
+    if status == L.ST_KEYERROR:
+        raise KeyError(t.z_of(cs))
+    ne, nl = int(o["n_ep"].cpu()[0]), int(o["n_len"].cpu()[0])
+    env.z = t.z_of(cs) if cs >= 0 else env.z
+    if row == -1:
+        env.s = None
+    elif row >= 0:
+        env.s = env._next_obs[row]
+    elif row > -(1 << 31):
+        env.s = env._obs[-2 - row]
     return o["ep_g"].cpu().numpy()[0, :ne].copy(), o["ep_len"].cpu().numpy()[0, :nl].astype(np.int64)
 
 
