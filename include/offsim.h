@@ -478,6 +478,84 @@ int offsim_policy_mlp(const void *x, int32_t x_dtype, int64_t n_x, int32_t dO, c
                       const offsim_mlp_layer *layers_host, int32_t n_layers, int32_t activation, float slope, float *out_probs,
                       void *stream);
 
+/* ---- a learner's data collection (VectorPSRS.collect) ------------------------------------------------------------------------
+ * The loop a neural learner runs against the log (examples/cartpole/psrs_from_expert_heuristic.py:59-80, with the network fixed for
+ * an epoch of steps_per_epoch steps, offsim4rl/agents/ppo.py:122-160): at every step the policy is asked at the current observation,
+ * PSRS.step_dist serves a logged transition, and the environment is reset when the transition terminates the episode or when the
+ * episode reaches max_episode_steps (:76-78).  offsim_vector_collect advances every environment of `ro` by T such steps in ONE launch
+ * (one wavefront per environment) and records each step.  Per step, for an environment with a current state (cur_slot >= 0):
+ *   1. p_new = the policy at the current observation (pol->form, below);
+ *   2. PSRS.step(p_new) as offsim_step_batch (advance = 1): same queues, streams, reject and prob modes;
+ *   3. served:  ep_t += 1; terminated = done of the served row; truncated = max_episode_steps > 0 && ep_t >= max_episode_steps
+ *      (as the example, both may be set); on either, PSRS.reset (offsim_env_reset) and ep_t = 0;
+ *      not served (None or KeyError): the environment stops for the rest of the launch, state and observation as they were.
+ *   A reset that finds the init queue empty leaves cur_slot = -1 (and the observation at next_obs of the served row).
+ * alive[r] (in/out) is cleared where a step is not served or a reset finds no initial row, as offsim_vector_step does.
+ * Policy forms (pol->form):
+ *   OFFSIM_COLLECT_MLP   the network of offsim_policy_mlp (same layers, activations and limits), evaluated by the environment's
+ *                        wavefront: every output is the same fmaf chain and softmax as offsim_policy_mlp's, so p_new equals its output
+ *                        bit for bit; widened to f64 for OFFSIM_PROB_F64.  The weights are staged into LDS once per workgroup: all
+ *                        layers' W and b together at most OFFSIM_COLLECT_MLP_MAX_FLOATS floats (64 KiB, which leaves room for two
+ *                        further workgroups of the C2 network per CU), otherwise OFFSIM_EUNSUPPORTED -- there is no L2 path.
+ *                        Observations: x_start [R,dO] (the environments' current ones at the call), x_next / x_init [N,dO] (caller
+ *                        rows' next_obs / obs), f32 or f16 (x_dtype).
+ *   OFFSIM_COLLECT_ROWS  per-row probability tables in CALLER row order, p_next[i] = the policy at next_obs of row i and p_init[i] = the
+ *                        policy at obs of row i (only initial rows are read), element type as offsim_eval_mc_rows_policy's; the
+ *                        current observation is st->obs_row (below), which must be valid for every environment with a state.
+ *   OFFSIM_COLLECT_TABULAR  pi [n_slots,nA] indexed by the state slot (observations are states), element type as offsim_eval_mc's;
+ *                        in LDS, at most 160 KiB with the per-wavefront scratch, otherwise OFFSIM_EUNSUPPORTED.
+ * State carried between calls (besides ro): ep_t [R] i32 steps of the current episode; obs_row [R] i32 where the observation comes
+ * from, encoded as out_obs_row of offsim_eval_mc_rows_policy (i >= 0: next_obs of caller row i; -2 - i: obs of caller row i; -1: None
+ * or unknown), rewritten where the observation changed; obs [R] rows of obs_bytes bytes, the environments' observation buffer (gets
+ * next_obs / obs rows of obs_next / obs_init as the observation changes).
+ * Records [T,R] (step-major): row = served caller row or -1; flags = OFFSIM_COLLECT_* bits; optional obs [T,R] rows of obs_bytes (the
+ * observation the policy was asked at) and probs [T,R,nA] f32 (p_new).  Steps of an environment without a state are -1 / 0 / zeros.
+ * status [R] (optional): OFFSIM_ST_OK, or why the environment stopped (EXHAUSTED, KEYERROR, NO_INIT, INACTIVE).
+ * Argument validation happens before any HIP call; T = 0 launches nothing (row / flags may then be NULL). */
+#define OFFSIM_COLLECT_MLP 0
+#define OFFSIM_COLLECT_ROWS 1
+#define OFFSIM_COLLECT_TABULAR 2
+#define OFFSIM_COLLECT_MLP_MAX_FLOATS 16384
+#define OFFSIM_COLLECT_SERVED 1     /* a transition was served                                     */
+#define OFFSIM_COLLECT_TERMINATED 2 /* its done flag                                                */
+#define OFFSIM_COLLECT_TRUNCATED 4  /* the episode reached max_episode_steps with it                 */
+#define OFFSIM_COLLECT_RESET 8      /* reset after the step: the next observation is an initial one  */
+#define OFFSIM_COLLECT_ALIVE 16     /* alive after the step                                         */
+typedef struct offsim_collect_policy {
+    int32_t form;                      /* OFFSIM_COLLECT_*                                          */
+    int32_t n_layers;                  /* MLP: layers_host[n_layers] as offsim_policy_mlp           */
+    const offsim_mlp_layer *layers_host;
+    int32_t activation;
+    float slope;
+    int32_t x_dtype;                   /* MLP: OFFSIM_F32 | OFFSIM_F16                              */
+    int32_t dO;
+    const void *x_start;               /* MLP: [R,dO]                                               */
+    const void *x_next;                /* MLP: [N,dO]                                               */
+    const void *x_init;                /* MLP: [N,dO]                                               */
+    const void *p_next;                /* ROWS: [N,nA]                                              */
+    const void *p_init;                /* ROWS: [N,nA]                                              */
+    const void *pi;                    /* TABULAR: [n_slots,nA]                                     */
+} offsim_collect_policy;
+typedef struct offsim_collect_state {
+    int32_t *ep_t;                     /* [R] in/out                                                */
+    int32_t *obs_row;                  /* [R] in/out                                                */
+    uint8_t *alive;                    /* [R] in/out                                                */
+    void *obs;                         /* [R] rows of obs_bytes, in/out                             */
+    const void *obs_next;              /* [N] rows: next_observations, caller order                 */
+    const void *obs_init;              /* [N] rows: observations, caller order                      */
+    int64_t obs_bytes;
+} offsim_collect_state;
+typedef struct offsim_collect_out {
+    int32_t *row;                      /* [T,R]                                                     */
+    uint8_t *flags;                    /* [T,R]                                                     */
+    void *obs;                         /* [T,R] rows of obs_bytes, or NULL                          */
+    float *probs;                      /* [T,R,nA], or NULL                                         */
+    int32_t *status;                   /* [R], or NULL                                              */
+} offsim_collect_out;
+int offsim_vector_collect(const offsim_table *t, offsim_rollouts *ro, const offsim_collect_policy *pol, int32_t prob_mode,
+                          int32_t reject_mode, int64_t T, int32_t max_episode_steps, const offsim_collect_state *st,
+                          const offsim_collect_out *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,6 +68,28 @@ class MLPLayer(C.Structure):
     _fields_ = [("W", _vp), ("b", _vp), ("in", _i32), ("out", _i32)]
 
 
+COLLECT_MLP, COLLECT_ROWS, COLLECT_TABULAR = 0, 1, 2
+COLLECT_MLP_MAX_FLOATS = 16384
+COLLECT_SERVED, COLLECT_TERMINATED, COLLECT_TRUNCATED, COLLECT_RESET, COLLECT_ALIVE = 1, 2, 4, 8, 16
+
+
+class CollectPolicy(C.Structure):
+    """struct offsim_collect_policy"""
+    _fields_ = [("form", _i32), ("n_layers", _i32), ("layers_host", C.POINTER(MLPLayer)), ("activation", _i32), ("slope", C.c_float),
+                ("x_dtype", _i32), ("dO", _i32), ("x_start", _vp), ("x_next", _vp), ("x_init", _vp), ("p_next", _vp), ("p_init", _vp),
+                ("pi", _vp)]
+
+
+class CollectState(C.Structure):
+    """struct offsim_collect_state"""
+    _fields_ = [("ep_t", _vp), ("obs_row", _vp), ("alive", _vp), ("obs", _vp), ("obs_next", _vp), ("obs_init", _vp), ("obs_bytes", _i64)]
+
+
+class CollectOut(C.Structure):
+    """struct offsim_collect_out"""
+    _fields_ = [("row", _vp), ("flags", _vp), ("obs", _vp), ("probs", _vp), ("status", _vp)]
+
+
 MAILBOX_MAX_ACTIONS = 24
 SERVER_CMD_STEP, SERVER_CMD_POP_ONE, SERVER_CMD_EXIT, SERVER_CMD_RESET = 1, 2, 3, 4
 SERVER_STARTING, SERVER_RUNNING, SERVER_EXITED = 1, 2, 3
@@ -130,6 +152,8 @@ SIGNATURES = {
     "offsim_eval_mc_rows_policy": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), _vp, _vp, _i32, _i32, C.c_double, _vp, _i64, _i64,
                                              C.POINTER(EvalMCOut), _vp, _vp]),
     "offsim_policy_mlp": (C.c_int, [_vp, _i32, _i64, _i32, _vp, _i64, C.POINTER(MLPLayer), _i32, _i32, C.c_float, _vp, _vp]),
+    "offsim_vector_collect": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), C.POINTER(CollectPolicy), _i32, _i32, _i64, _i32,
+                                        C.POINTER(CollectState), C.POINTER(CollectOut), _vp]),
 }
 
 _lib = None

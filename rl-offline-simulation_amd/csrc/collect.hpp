@@ -1,0 +1,343 @@
+// A learner's data collection in one launch (include/offsim.h: offsim_vector_collect; VectorPSRS.collect).
+//
+// The loop of examples/cartpole/psrs_from_expert_heuristic.py:59-80 -- policy at the current observation, PSRS.step, reset at terminated
+// or at the episode's step cap -- for T steps, one wavefront per environment, as k_vector_step and the generic k_eval_mc.  Each step:
+//   1. p_new at the current observation, in one of three forms (template parameter FORM):
+//        MLP      the network in-wave: the workgroup stages every layer's W^T [in][out] and b into LDS once; the wave reads its
+//                 observation row, lanes run over output units (pmlp_unit: the fmaf chain of k_policy_mlp, so the same bits), lane 0
+//                 runs the softmax (pmlp_softmax);
+//        ROWS     p_next[row] / p_init[row] of the caller's per-row tables (row = the observation's source row);
+//        TABULAR  pi[slot], staged into LDS once per workgroup;
+//   2. psrs_step, unchanged (cursors in global memory, as k_step_batch / k_vector_step keep them);
+//   3. the step's record ([T, R], step-major: a step's stores from all environments are adjacent);
+//   4. reset on done or at max_episode_steps (k_env_reset's logic, as k_vector_step's).
+// The environment's state lives in registers for the launch and is written back once at the end.
+#pragma once
+
+#define COLLECT_WAVES 8  // environments per workgroup: one copy of the weights in LDS serves eight wavefronts
+// candidates a step looks at per round (psrs_step's `width`; the served row and the draws consumed do not depend on it).  Every lane
+// that looks at a candidate gathers its columns from a random line of the log, and a step is usually served by the first or second
+// candidate, so 64 lanes per round made the kernel bound by that traffic.
+#define COLLECT_WIDTH 16
+
+struct CollectMlp {
+    const float *W[PMLP_MAX_LAYERS];
+    const float *b[PMLP_MAX_LAYERS];
+    int in[PMLP_MAX_LAYERS], out[PMLP_MAX_LAYERS];
+    int woff[PMLP_MAX_LAYERS], boff[PMLP_MAX_LAYERS];  // LDS float offsets of W^T [in][out] and b [out] (boff -1: no bias)
+    int n, w_max, floats, act, dO;
+    float slope;
+    const void *x_start, *x_next, *x_init;
+};
+
+struct CollectArgs {
+    CollectMlp mlp;
+    const void *p_next, *p_init, *pi;
+    int reject_mode, max_ep;
+    int64_t T;
+    offsim_collect_state st;
+    offsim_collect_out out;
+    uint32_t off_pn, off_pf, off_act;  // byte offsets of the per-wave p_new (f64 slots), probs (f32) and activation buffers
+};
+
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's LDS writes are done
+    __builtin_amdgcn_wave_barrier();
+}
+
+// nb bytes from s to d (d NULL-free), the lanes of one wave striding; s NULL: zeros
+__device__ __forceinline__ void wave_copy_row(unsigned char *d, const unsigned char *s, int64_t nb, int lane) {
+    if (((nb | (int64_t)(uintptr_t)d | (int64_t)(uintptr_t)s) & 3) == 0) {
+        for (int64_t b = 4 * lane; b < nb; b += 4 * WAVE) *(uint32_t *)(d + b) = s ? *(const uint32_t *)(s + b) : 0u;
+    } else {
+        for (int64_t b = lane; b < nb; b += WAVE) d[b] = s ? s[b] : (unsigned char)0;
+    }
+}
+
+// obs_row encoding (offsim_eval_mc_rows_policy's out_obs_row): i >= 0 next_obs of caller row i, -2 - i obs of caller row i
+__device__ __forceinline__ bool collect_row_ok(int32_t v, int64_t N) { return (v >= 0 && v < N) || (v <= -2 && -2 - (int64_t)v < N); }
+
+template <typename PL, typename PROB, int FORM, typename XT>
+__global__ void __launch_bounds__(COLLECT_WAVES * WAVE) k_collect(offsim_table t, offsim_rollouts ro, CollectArgs A) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    const int waves = blockDim.x / WAVE;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE), lane = threadIdx.x & (WAVE - 1);
+    const int nA = t.nA;
+    Jump *tables = (Jump *)lds_raw;
+    float *w_lds = (float *)(tables + waves * (WAVE + 1));  // MLP: the weights; TABULAR: pi
+    PROB *pi_lds = (PROB *)w_lds;
+    PROB *pn_lds = (PROB *)(lds_raw + A.off_pn) + wave * PMLP_MAX_ACTIONS;
+    float *pf_lds = (float *)(lds_raw + A.off_pf) + wave * PMLP_MAX_ACTIONS;
+    float *act_lds = (float *)(lds_raw + A.off_act) + (size_t)wave * 2 * A.mlp.w_max;
+    if constexpr (FORM == OFFSIM_COLLECT_MLP) {
+        for (int l = 0; l < A.mlp.n; l++) {
+            const int in = A.mlp.in[l], out = A.mlp.out[l];
+            const float *__restrict__ W = A.mlp.W[l];
+            for (int e = threadIdx.x; e < in * out; e += blockDim.x) {  // W [out][in] (coalesced) -> W^T [in][out]
+                const int j = e / in, k = e - j * in;
+                w_lds[A.mlp.woff[l] + k * out + j] = W[e];
+            }
+            if (A.mlp.boff[l] >= 0)
+                for (int j = threadIdx.x; j < out; j += blockDim.x) w_lds[A.mlp.boff[l] + j] = A.mlp.b[l][j];
+        }
+    } else if constexpr (FORM == OFFSIM_COLLECT_TABULAR) {
+        for (int i = threadIdx.x; i < t.n_slots * nA; i += blockDim.x) pi_lds[i] = ((const PROB *)A.pi)[i];
+    }
+    __syncthreads();
+    const int r = blockIdx.x * waves + wave;
+    if (r >= ro.R) return;
+    const int64_t R = ro.R, ob = A.st.obs_bytes;
+
+    int slot = ro.cur_slot[r];
+    uint32_t ic = ro.init_cursor[r];
+    int32_t ep_t = A.st.ep_t[r];
+    int32_t xrow = A.st.obs_row[r];  // where the observation comes from once it has moved (ROWS: from the start)
+    bool alive = A.st.alive[r] != 0, moved = false, none = false;
+    int status = slot < 0 ? OFFSIM_ST_INACTIVE : OFFSIM_ST_OK;
+    if (FORM == OFFSIM_COLLECT_ROWS && status == OFFSIM_ST_OK && !collect_row_ok(xrow, t.N)) status = OFFSIM_ST_INACTIVE;  // (no tables row)
+    bool live = status == OFFSIM_ST_OK;
+
+    WaveRng rng;
+    const U128 base = u128(ro.rng[4 * r + 0], ro.rng[4 * r + 1]), inc = u128(ro.rng[4 * r + 2], ro.rng[4 * r + 3]);
+    rng.kind = ro.rng_kind;
+    if (A.reject_mode != OFFSIM_REJECT_NEVER) wave_rng_init(rng, tables + wave * (WAVE + 1), base, inc, ro.rng_kind);
+    wave_lds_sync();
+    uint64_t consumed = 0;
+    const uint32_t *perm_row = ro.perm ? ro.perm + (int64_t)r * ro.perm_stride : nullptr;
+    const uint32_t *init_row = ro.init_perm ? ro.init_perm + (int64_t)r * ro.init_stride : nullptr;
+    uint32_t *cursor = ro.cursor + (int64_t)r * t.n_slots;
+    const unsigned char *obs_next = (const unsigned char *)A.st.obs_next, *obs_init = (const unsigned char *)A.st.obs_init;
+    unsigned char *obs_cur = (unsigned char *)A.st.obs + r * ob;
+
+    for (int64_t i = 0; i < A.T; i++) {
+        const int64_t o = i * R + r;
+        if (live && (unsigned)slot >= (unsigned)t.n_slots) {  // (a slot outside the table: psrs_step's KeyError, before pi[slot] is read)
+            status = OFFSIM_ST_KEYERROR;
+            live = false;
+            alive = false;
+        }
+        if (!live) {  // no state, or stopped earlier in this launch: nothing asked, nothing served
+            if (lane == 0) {
+                A.out.row[o] = -1;
+                A.out.flags[o] = 0;
+            }
+            if (A.out.probs)
+                for (int a = lane; a < nA; a += WAVE) A.out.probs[o * nA + a] = 0.0f;
+            if (A.out.obs) wave_copy_row((unsigned char *)A.out.obs + o * ob, nullptr, ob, lane);
+            continue;
+        }
+        if (A.out.obs) {
+            const unsigned char *src = !moved ? obs_cur : xrow >= 0 ? obs_next + (int64_t)xrow * ob : obs_init + (-2 - (int64_t)xrow) * ob;
+            wave_copy_row((unsigned char *)A.out.obs + o * ob, src, ob, lane);
+        }
+        // 1. the policy at the current observation
+        const PROB *pn;
+        if constexpr (FORM == OFFSIM_COLLECT_MLP) {
+            const int dO = A.mlp.dO;
+            const XT *x = !moved ? (const XT *)A.mlp.x_start + (int64_t)r * dO
+                          : xrow >= 0 ? (const XT *)A.mlp.x_next + (int64_t)xrow * dO
+                                      : (const XT *)A.mlp.x_init + (-2 - (int64_t)xrow) * dO;
+            float *cur = act_lds, *nxt = act_lds + A.mlp.w_max;
+            for (int k = lane; k < dO; k += WAVE) cur[k] = pmlp_in<XT>(x, k);
+            wave_lds_sync();
+            for (int l = 0; l < A.mlp.n; l++) {
+                const int in = A.mlp.in[l], out = A.mlp.out[l];
+                const float *wt = w_lds + A.mlp.woff[l];
+                const float *bl = A.mlp.boff[l] >= 0 ? w_lds + A.mlp.boff[l] : nullptr;
+                const bool last = l == A.mlp.n - 1;
+                for (int j = lane; j < out; j += WAVE) nxt[j] = pmlp_unit(cur, wt + j, out, in, bl ? bl + j : nullptr, last, A.mlp.act, A.mlp.slope);
+                wave_lds_sync();
+                float *sw = cur;
+                cur = nxt;
+                nxt = sw;
+            }
+            if (lane == 0) pmlp_softmax(cur, nA, pf_lds);
+            wave_lds_sync();
+            if (lane < nA) {
+                const float p = pf_lds[lane];
+                pn_lds[lane] = (PROB)p;
+                if (A.out.probs) A.out.probs[o * nA + lane] = p;
+            }
+            wave_lds_sync();
+            pn = pn_lds;
+        } else {
+            if constexpr (FORM == OFFSIM_COLLECT_ROWS)
+                pn = xrow >= 0 ? (const PROB *)A.p_next + (int64_t)xrow * nA : (const PROB *)A.p_init + (-2 - (int64_t)xrow) * nA;
+            else
+                pn = pi_lds + (size_t)slot * nA;
+            if (A.out.probs)
+                for (int a = lane; a < nA; a += WAVE) A.out.probs[o * nA + a] = (float)pn[a];
+        }
+        // 2. PSRS.step
+        const StepResult s = psrs_step<PL, PROB>(t, t.seg_off, perm_row, slot, cursor, pn, A.reject_mode, 0u, rng, consumed, COLLECT_WIDTH);
+        if (s.status != OFFSIM_ST_OK) {  // None or KeyError: the example's `break`, for this environment (state left as it is)
+            status = s.status;
+            live = false;
+            alive = false;
+            if (lane == 0) {
+                A.out.row[o] = -1;
+                A.out.flags[o] = 0;
+            }
+            continue;
+        }
+        // 3. the record, 4. the reset at terminated / truncated
+        const int32_t row = t.orig_idx[s.g];
+        ep_t++;
+        const bool term = s.done, trunc = A.max_ep > 0 && ep_t >= A.max_ep;
+        uint32_t fl = OFFSIM_COLLECT_SERVED | (term ? OFFSIM_COLLECT_TERMINATED : 0u) | (trunc ? OFFSIM_COLLECT_TRUNCATED : 0u);
+        slot = s.z_next;
+        xrow = row;
+        moved = true;
+        if (term || trunc) {
+            ep_t = 0;
+            if ((int64_t)ic >= t.N0) {  // psrs.py:33-35: reset() returned None; the observation stays next_obs of the row
+                slot = -1;
+                alive = false;
+                live = false;
+                none = true;
+                status = OFFSIM_ST_NO_INIT;
+            } else {
+                const uint32_t k = init_row ? init_row[ic] : ic;
+                ic++;
+                slot = t.init_slot[k];
+                xrow = -2 - t.init_orig[k];
+                fl |= OFFSIM_COLLECT_RESET;
+            }
+        }
+        if (alive) fl |= OFFSIM_COLLECT_ALIVE;
+        if (lane == 0) {
+            A.out.row[o] = row;
+            A.out.flags[o] = (uint8_t)fl;
+        }
+    }
+    // the state, for the next call
+    if (moved) wave_copy_row(obs_cur, xrow >= 0 ? obs_next + (int64_t)xrow * ob : obs_init + (-2 - (int64_t)xrow) * ob, ob, lane);
+    if (lane == 0) {
+        if (consumed && ro.rng_kind == OFFSIM_STREAM_PHILOX) {
+            ro.rng[4 * r + 1] = base.lo + consumed;
+        } else if (consumed) {
+            const U128 nb = pcg_apply(pcg_jump(inc, consumed), base);
+            ro.rng[4 * r + 0] = nb.hi;
+            ro.rng[4 * r + 1] = nb.lo;
+        }
+        ro.cur_slot[r] = slot;
+        ro.init_cursor[r] = ic;
+        A.st.ep_t[r] = ep_t;
+        if (moved) A.st.obs_row[r] = none ? -1 : xrow;
+        A.st.alive[r] = (uint8_t)alive;
+        if (A.out.status) A.out.status[r] = status;
+    }
+}
+
+// LDS of one workgroup: [jump tables][weights | pi][p_new f64 x 16 per wave][probs f32 x 16 per wave][2 activation rows per wave]
+static size_t collect_lds_layout(int waves, size_t shared_bytes, int w_max, CollectArgs &A) {
+    size_t off = (size_t)waves * (WAVE + 1) * sizeof(Jump) + ((shared_bytes + 15) & ~(size_t)15);
+    A.off_pn = (uint32_t)off;
+    off += (size_t)waves * PMLP_MAX_ACTIONS * sizeof(double);
+    A.off_pf = (uint32_t)off;
+    off += (size_t)waves * PMLP_MAX_ACTIONS * sizeof(float);
+    A.off_act = (uint32_t)off;
+    off += (size_t)waves * 2 * w_max * sizeof(float);
+    return off;
+}
+
+extern "C" int offsim_vector_collect(const offsim_table *t, offsim_rollouts *ro, const offsim_collect_policy *pol, int32_t prob_mode,
+                                     int32_t reject_mode, int64_t T, int32_t max_episode_steps, const offsim_collect_state *st,
+                                     const offsim_collect_out *out, void *stream) {
+    int rc = check_table(t);
+    if (rc) return rc;
+    if (!ro || ro->R < 0 || !pol || !st || !out || T < 0 || max_episode_steps < 0) return fail(OFFSIM_EINVAL, "vector_collect: bad argument%s");
+    if (prob_mode != OFFSIM_PROB_F32 && prob_mode != OFFSIM_PROB_F64) return fail(OFFSIM_EINVAL, "vector_collect: bad prob_mode%s");
+    if (prob_mode == OFFSIM_PROB_F32 && t->plog_dtype != OFFSIM_F32) return fail(OFFSIM_EINVAL, "vector_collect: OFFSIM_PROB_F32 needs an f32 p_log%s");
+    if (reject_mode != OFFSIM_REJECT_DEFAULT && reject_mode != OFFSIM_REJECT_NEVER) return fail(OFFSIM_EINVAL, "vector_collect: bad reject_mode%s");
+    if (!st->ep_t || !st->obs_row || !st->alive || !st->obs || st->obs_bytes <= 0 || (t->N > 0 && (!st->obs_next || !st->obs_init)))
+        return fail(OFFSIM_EINVAL, "vector_collect: bad state (ep_t, obs_row, alive, obs, obs_next, obs_init, obs_bytes)%s");
+    if (T > 0 && (!out->row || !out->flags)) return fail(OFFSIM_EINVAL, "vector_collect: out->row / out->flags is NULL%s");
+    if (t->N0 > 0 && (!t->init_slot || !t->init_orig)) return fail(OFFSIM_EINVAL, "vector_collect: table has no init rows%s");
+    CollectArgs A;
+    memset(&A, 0, sizeof(A));
+    A.mlp.w_max = 0;
+    size_t shared = 0;
+    const size_t pb = prob_mode == OFFSIM_PROB_F32 ? 4 : 8;
+    if (pol->form == OFFSIM_COLLECT_MLP) {
+        const int n = pol->n_layers, dO = pol->dO;
+        if (!pol->layers_host || n < 1 || n > PMLP_MAX_LAYERS) return fail(OFFSIM_EINVAL, "vector_collect: 1 to 4 Linear layers%s");
+        if (pol->x_dtype != OFFSIM_F32 && pol->x_dtype != OFFSIM_F16) return fail(OFFSIM_EINVAL, "vector_collect: x_dtype must be OFFSIM_F32 or OFFSIM_F16%s");
+        if (pol->activation != OFFSIM_ACT_IDENTITY && pol->activation != OFFSIM_ACT_TANH && pol->activation != OFFSIM_ACT_RELU &&
+            pol->activation != OFFSIM_ACT_LEAKY_RELU)
+            return fail(OFFSIM_EINVAL, "vector_collect: unknown activation%s");
+        if (dO < 1 || dO > PMLP_MAX_IN) return fail(OFFSIM_EINVAL, "vector_collect: observation width must be 1..128%s");
+        if (!pol->x_start || (t->N > 0 && (!pol->x_next || !pol->x_init))) return fail(OFFSIM_EINVAL, "vector_collect: x_start / x_next / x_init is NULL%s");
+        int floats = 0;
+        A.mlp.w_max = dO;
+        for (int l = 0; l < n; l++) {
+            const offsim_mlp_layer &y = pol->layers_host[l];
+            const bool last = l == n - 1;
+            if (!y.W) return fail(OFFSIM_EINVAL, "vector_collect: a layer's W is NULL%s");
+            if (y.in != (l == 0 ? dO : pol->layers_host[l - 1].out)) return fail(OFFSIM_EINVAL, "vector_collect: layer widths do not chain%s");
+            if (y.out < 1 || y.out > (last ? PMLP_MAX_ACTIONS : PMLP_MAX_HIDDEN))
+                return fail(OFFSIM_EINVAL, last ? "vector_collect: more than 16 actions%s" : "vector_collect: hidden width above 256%s");
+            if (last && y.out != t->nA) return fail(OFFSIM_EINVAL, "vector_collect: the network's outputs differ from the table's nA%s");
+            A.mlp.W[l] = y.W;
+            A.mlp.b[l] = y.b;
+            A.mlp.in[l] = y.in;
+            A.mlp.out[l] = y.out;
+            A.mlp.woff[l] = floats;
+            floats += y.in * y.out;
+            A.mlp.boff[l] = y.b ? floats : -1;
+            floats += y.b ? y.out : 0;
+            if (y.out > A.mlp.w_max) A.mlp.w_max = y.out;
+        }
+        if (floats > OFFSIM_COLLECT_MLP_MAX_FLOATS)
+            return fail(OFFSIM_EUNSUPPORTED, "vector_collect: the network's weights exceed OFFSIM_COLLECT_MLP_MAX_FLOATS (64 KiB of LDS)%s");
+        A.mlp.n = n;
+        A.mlp.floats = floats;
+        A.mlp.act = pol->activation;
+        A.mlp.slope = pol->slope;
+        A.mlp.dO = dO;
+        A.mlp.x_start = pol->x_start;
+        A.mlp.x_next = pol->x_next;
+        A.mlp.x_init = pol->x_init;
+        shared = (size_t)floats * sizeof(float);
+    } else if (pol->form == OFFSIM_COLLECT_ROWS) {
+        if (t->N > 0 && (!pol->p_next || !pol->p_init)) return fail(OFFSIM_EINVAL, "vector_collect: p_next / p_init is NULL%s");
+        A.p_next = pol->p_next;
+        A.p_init = pol->p_init;
+    } else if (pol->form == OFFSIM_COLLECT_TABULAR) {
+        if (!pol->pi) return fail(OFFSIM_EINVAL, "vector_collect: pi is NULL%s");
+        A.pi = pol->pi;
+        shared = (size_t)t->n_slots * t->nA * pb;
+    } else {
+        return fail(OFFSIM_EINVAL, "vector_collect: unknown policy form%s");
+    }
+    const size_t lds = collect_lds_layout(COLLECT_WAVES, shared, A.mlp.w_max, A);
+    if (lds > 160 * 1024) return fail(OFFSIM_EUNSUPPORTED, "vector_collect: the policy table and per-wave scratch exceed 160 KiB of LDS%s");
+    A.reject_mode = reject_mode;
+    A.max_ep = max_episode_steps;
+    A.T = T;
+    A.st = *st;
+    A.out = *out;
+    if (ro->R == 0 || T == 0) return OFFSIM_OK;
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid((unsigned)((ro->R + COLLECT_WAVES - 1) / COLLECT_WAVES)), block(COLLECT_WAVES * WAVE);
+#define LAUNCH_COLLECT(PL, PROB, FORM, XT)                                                               \
+    do {                                                                                                  \
+        if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_collect<PL, PROB, FORM, XT>), (int)lds));          \
+        hipLaunchKernelGGL((k_collect<PL, PROB, FORM, XT>), grid, block, lds, s, *t, *ro, A);             \
+    } while (0)
+#define LAUNCH_FORM(PL, PROB)                                                                                     \
+    do {                                                                                                          \
+        if (pol->form == OFFSIM_COLLECT_MLP && pol->x_dtype == OFFSIM_F32) LAUNCH_COLLECT(PL, PROB, OFFSIM_COLLECT_MLP, float); \
+        else if (pol->form == OFFSIM_COLLECT_MLP) LAUNCH_COLLECT(PL, PROB, OFFSIM_COLLECT_MLP, __half);            \
+        else if (pol->form == OFFSIM_COLLECT_ROWS) LAUNCH_COLLECT(PL, PROB, OFFSIM_COLLECT_ROWS, float);           \
+        else LAUNCH_COLLECT(PL, PROB, OFFSIM_COLLECT_TABULAR, float);                                              \
+    } while (0)
+    if (prob_mode == OFFSIM_PROB_F32) LAUNCH_FORM(float, float);
+    else if (t->plog_dtype == OFFSIM_F32) LAUNCH_FORM(float, double);
+    else if (t->plog_dtype == OFFSIM_F64) LAUNCH_FORM(double, double);
+    else LAUNCH_FORM(__half, double);
+#undef LAUNCH_FORM
+#undef LAUNCH_COLLECT
+    LAUNCH_CHECK();
+    return OFFSIM_OK;
+}

@@ -2272,3 +2272,6 @@ extern "C" int offsim_policy_mlp(const void *x, int32_t x_dtype, int64_t n_x, in
     LAUNCH_CHECK();
     return OFFSIM_OK;
 }
+
+// ---- a learner's data collection: T steps of policy -> PSRS.step -> reset per launch (csrc/collect.hpp) ----
+#include "collect.hpp"

@@ -35,6 +35,32 @@ __device__ __forceinline__ float pmlp_act(float v, int act, float slope) {
     }
 }
 
+// One output unit of a layer: sum_k x[k] * w[k * ws] as ONE fmaf chain in k order, then + bias (b NULL: none), then the activation unless
+// the layer is the last.  Shared by k_policy_mlp (w = a row of W, ws = 1) and the in-wave forward of offsim_vector_collect (w = a column
+// of W^T, ws = out), so both produce the same bits.
+__device__ __forceinline__ float pmlp_unit(const float *x, const float *w, int ws, int in, const float *b, bool last, int act, float slope) {
+    float acc = 0.0f;
+    for (int k = 0; k < in; k++) acc = fmaf(x[k], w[k * ws], acc);
+    if (b) acc = acc + *b;
+    return last ? acc : pmlp_act(acc, act, slope);
+}
+
+// softmax of the logits z[0..nA) (torch.distributions.Categorical(logits=...).probs): max-subtracted, exp, the sum left to right, one
+// division per action.  One thread per row.
+__device__ __forceinline__ void pmlp_softmax(const float *z, int nA, float *o) {
+    float mx = z[0];
+    for (int a = 1; a < nA; a++) mx = z[a] > mx ? z[a] : mx;
+    float e[PMLP_MAX_ACTIONS], s = 0.0f;
+    for (int a = 0; a < PMLP_MAX_ACTIONS; a++) {
+        if (a < nA) {
+            e[a] = expf(z[a] - mx);
+            s = s + e[a];
+        }
+    }
+    for (int a = 0; a < PMLP_MAX_ACTIONS; a++)
+        if (a < nA) o[a] = e[a] / s;
+}
+
 template <typename XT>
 __device__ __forceinline__ float pmlp_in(const XT *x, int64_t i);
 template <>
@@ -73,11 +99,7 @@ __global__ void __launch_bounds__(256) k_policy_mlp(const XT *__restrict__ x, in
             __syncthreads();
             for (int e = threadIdx.x; e < tm * jc; e += blockDim.x) {
                 const int m = e / jc, j = e - m * jc;
-                const float *xr = cur + m * ld, *wr = wl + j * ldw;
-                float acc = 0.0f;
-                for (int k = 0; k < in; k++) acc = fmaf(xr[k], wr[k], acc);
-                if (b) acc = acc + b[j0 + j];
-                nxt[m * ld + j0 + j] = last ? acc : pmlp_act(acc, act, slope);
+                nxt[m * ld + j0 + j] = pmlp_unit(cur + m * ld, wl + j * ldw, 1, in, b ? b + j0 + j : nullptr, last, act, slope);
             }
         }
         __syncthreads();
@@ -87,21 +109,7 @@ __global__ void __launch_bounds__(256) k_policy_mlp(const XT *__restrict__ x, in
     }
     // softmax of the logits (torch.distributions.Categorical(logits=...).probs)
     const int nA = L.out[L.n - 1];
-    for (int m = threadIdx.x; m < tm; m += blockDim.x) {
-        const float *z = cur + m * ld;
-        float mx = z[0];
-        for (int a = 1; a < nA; a++) mx = z[a] > mx ? z[a] : mx;
-        float e[PMLP_MAX_ACTIONS], s = 0.0f;
-        for (int a = 0; a < PMLP_MAX_ACTIONS; a++) {
-            if (a < nA) {
-                e[a] = expf(z[a] - mx);
-                s = s + e[a];
-            }
-        }
-        float *o = probs + (m0 + m) * nA;
-        for (int a = 0; a < PMLP_MAX_ACTIONS; a++)
-            if (a < nA) o[a] = e[a] / s;
-    }
+    for (int m = threadIdx.x; m < tm; m += blockDim.x) pmlp_softmax(cur + m * ld, nA, probs + (m0 + m) * nA);
 }
 
 static size_t policy_mlp_lds_bytes(const PmlpLayers &L) { return sizeof(float) * (2 * (size_t)PMLP_TM * (L.w_max + 1) + (size_t)L.w_floats); }

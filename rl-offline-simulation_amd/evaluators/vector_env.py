@@ -18,6 +18,7 @@ stream, so a whole driver iteration (policy forward -> step_dist_batch -> reset 
 captured once in a HIP graph and replayed (`torch.cuda.graph`, see `graph_iteration`): the loop is launch-bound otherwise.
 """
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -64,7 +65,19 @@ class VectorPSRS:
         self._done = torch.as_tensor(np.asarray(e["terminals"]) != 0).to(dev)
         self.observation_space, self.action_space = dataset.observation_space, dataset.action_space
         self.obs = torch.zeros((self.num_envs,) + tuple(self._obs.shape[1:]), dtype=self._obs.dtype, device=dev)
-        self.alive = torch.zeros(self.num_envs, dtype=torch.bool, device=dev)
+        # alive [E] and the episode step counter of collect, ep_t [E] i32, share one buffer: reset_sampler clears both with one fill
+        ea = (self.num_envs + 3) // 4 * 4
+        self._sbuf = torch.zeros(ea + 4 * self.num_envs, dtype=torch.uint8, device=dev)
+        self.alive = self._sbuf[:self.num_envs].view(torch.bool)
+        self._ep_t = self._sbuf[ea:].view(torch.int32)
+        # where each environment's observation comes from (include/offsim.h: offsim_collect_state.obs_row): kept by reset, step_dist_batch
+        # and step_and_reset through extra gather columns (no extra launch): src_next[i] = i, src_init[i] = -2 - i, zero[i] = 0
+        self._obs_row = torch.full((self.num_envs,), -1, dtype=torch.int32, device=dev)
+        self._src_next = torch.arange(n, dtype=torch.int32, device=dev)
+        self._src_init = -2 - self._src_next
+        self._src_zero = torch.zeros(n, dtype=torch.int32, device=dev)
+        self._encoded = encoder is not None
+        self._x_rows = None
         # outputs of step_dist_batch (overwritten by every call) and the column descriptors of offsim_vector_gather
         self._obs, self._next_obs, self._a, self._r, self._done = (x.contiguous() for x in (self._obs, self._next_obs, self._a, self._r, self._done))
         self.action = torch.zeros(self.num_envs, dtype=self._a.dtype, device=dev)
@@ -79,12 +92,14 @@ class VectorPSRS:
                 c.src, c.dst, c.row_bytes, c.zero_if_not_ok = src.data_ptr(), dst.data_ptr(), nb, int(zero)
             return arr
 
-        self._cols_step = cols((self._next_obs, self.obs, False), (self._a, self.action, False), (self._r, self.reward, False), (self._done, self.done, True))
-        self._cols_reset = cols((self._obs, self.obs, False))
+        self._cols_step = cols((self._next_obs, self.obs, False), (self._a, self.action, False), (self._r, self.reward, False), (self._done, self.done, True),
+                               (self._src_next, self._obs_row, False))
+        self._cols_reset = cols((self._obs, self.obs, False), (self._src_init, self._obs_row, False), (self._src_zero, self._ep_t, False))
 
-    def reset_sampler(self, seeds):
-        self.env.reset_sampler(seeds)
-        self.alive.zero_()
+    def reset_sampler(self, seeds, rejection="pcg64"):
+        """PSRS.reset_sampler(seed_k) for every environment (rejection: BatchedPSRS.reset_sampler's provider of the rejection stream)."""
+        self.env.reset_sampler(seeds, rejection=rejection)
+        self._sbuf.zero_()  # alive and ep_t
         if self.strict:  # (strict mode synchronises with the host anyway: a sampler reset that gave up a bounded wait raises here)
             self.check_faults()
 
@@ -163,3 +178,148 @@ class VectorPSRS:
         with torch.cuda.graph(g), torch.no_grad():
             outs = iteration()
         return g, outs
+
+    # ---- a learner's data collection: T steps in one launch ----------------------------------------------------------------------
+    def collect(self, policy, num_steps, max_episode_steps=None, record_obs=True, record_probs=True, form="auto"):
+        """The loop a learner runs inside PSRS (examples/cartpole/psrs_from_expert_heuristic.py:59-80, an epoch of a fixed network,
+        offsim4rl/agents/ppo.py:122-160) for `num_steps` steps of every environment, in ONE launch (offsim_vector_collect):
+
+            probs = policy(obs); step_and_reset(probs); reset(mask=truncated & ~terminated)     # T times
+
+        with the episode's step counter kept on the device: truncated = ep_t >= max_episode_steps after a served step (None: no limit;
+        terminated and truncated may both be set, as in the example).  An environment whose step returns None (or raises KeyError:
+        strict=True raises it here) or whose reset finds no initial row stops for the rest of the call.
+
+        policy: MLPPolicy (the network runs inside the kernel, p_new bit-equal to MLPPolicy.forward), any other ObsPolicy (its per-row
+        tables), or an [nS, nA] array indexed by the state (only where observations are states, as evalMC_psrs).  form: "auto", or
+        "mlp" / "rows" / "tabular" to pick one ("rows" also takes an MLPPolicy, through its row_tables).  p_new is compared in f32 where
+        the policy's probabilities and p_log are both f32, in f64 otherwise (step_and_reset's rule).
+
+        Returns a Collected of device tensors, step-major [T, E, ...]: obs (the observation the policy was asked at; record_obs),
+        probs (f32; record_probs), row (served caller row, -1 where nothing was served), action / reward / next_obs of the served row
+        (zeros where none), terminated, truncated, reset (an initial observation follows), alive (after the step), final_obs [E, ...]
+        (self.obs after the last step: the bootstrap observation of ppo.py:127-131), status [E] (include/offsim.h: OFFSIM_ST_*).
+        self.obs / self.alive and the sampler state carry over, so collect mixes freely with reset / step_dist_batch / step_and_reset.
+        ep_t counts the steps collect served since the environment's last reset; step_dist_batch / step_and_reset do not advance it
+        (they have no time limit) but their resets clear it, as reset() and reset_sampler() do."""
+        T = int(num_steps)
+        if T < 0:
+            raise ValueError(f"collect: num_steps must be >= 0, got {num_steps}")
+        cap = 0 if max_episode_steps is None else int(max_episode_steps)
+        if cap < 0 or cap >= 1 << 31:
+            raise ValueError(f"collect: max_episode_steps must be None or in [0, 2**31), got {max_episode_steps} (0 = no limit)")
+        from .obs_policy import MLPPolicy, ObsPolicy
+        if form == "auto":
+            form = "mlp" if isinstance(policy, MLPPolicy) else "rows" if isinstance(policy, ObsPolicy) else "tabular"
+        env, t = self.env, self.table
+        env._quiesce()
+        env._orders_for_generic()
+        pol, keep = L.CollectPolicy(), []
+        if form == "mlp":
+            if not isinstance(policy, MLPPolicy):
+                raise TypeError(f"collect: form='mlp' needs an MLPPolicy, got {type(policy).__name__}")
+            x_next, x_init = self._x_tables()
+            if policy.dO != x_next.shape[1]:
+                raise ValueError(f"collect: the network takes observations of width {policy.dO}, the log's have {x_next.shape[1]}")
+            x_start = self.obs.reshape(self.num_envs, -1).to(x_next.dtype).contiguous()
+            ws, arr = policy._device_weights(t.device)
+            pol.form, pol.n_layers, pol.layers_host = L.COLLECT_MLP, len(ws), C.cast(arr, C.POINTER(L.MLPLayer))
+            pol.activation, pol.slope = _mlp_act(policy), policy.slope
+            pol.x_dtype, pol.dO = (L.F32 if x_next.dtype == torch.float32 else L.F16), policy.dO
+            pol.x_start, pol.x_next, pol.x_init = L.ptr(x_start), L.ptr(x_next), L.ptr(x_init)
+            keep += [x_start, x_next, x_init, ws]
+            f32 = t.p_log.dtype == torch.float32
+        elif form == "rows":
+            if not isinstance(policy, ObsPolicy):
+                raise TypeError(f"collect: form='rows' needs an ObsPolicy, got {type(policy).__name__}")
+            pn, p0 = self._caller_tables(policy)
+            f32 = pn.dtype == torch.float32 and t.p_log.dtype == torch.float32
+            pn, p0 = (x.to(torch.float32 if f32 else torch.float64).contiguous() for x in (pn, p0))
+            pol.form, pol.p_next, pol.p_init = L.COLLECT_ROWS, L.ptr(pn), L.ptr(p0)
+            keep += [pn, p0]
+        elif form == "tabular":
+            if isinstance(policy, ObsPolicy):
+                raise TypeError("collect: form='tabular' needs an [nS, nA] array")
+            if self._encoded:
+                raise NotImplementedError("collect: the observations of this environment differ from its latent states, but a tabular policy is "
+                                          "indexed by the observation (psrs.py:158, :255); pass a policy over observations (MLPPolicy, RowPolicy)")
+            pi = policy.detach().cpu().numpy() if isinstance(policy, torch.Tensor) else np.asarray(policy)
+            if pi.ndim != 2 or pi.shape[1] != t.nA:
+                raise ValueError(f"collect: pi must be a [nS, {t.nA}] table, got shape {pi.shape}")
+            if t.N and pi.shape[0] <= int(t.slot_z.max()):
+                raise IndexError("pi has no row for some latent state")
+            f32 = pi.dtype == np.float32 and t.p_log.dtype == torch.float32
+            ps = torch.from_numpy(np.ascontiguousarray(t.policy_slots(pi).astype(np.float32 if f32 else np.float64))).to(t.device)
+            pol.form, pol.pi = L.COLLECT_TABULAR, L.ptr(ps)
+            keep.append(ps)
+        else:
+            raise ValueError(f"collect: form must be 'auto', 'mlp', 'rows' or 'tabular', got {form!r}")
+        E, dev = self.num_envs, t.device
+        row = torch.empty((T, E), dtype=torch.int32, device=dev)
+        flags = torch.empty((T, E), dtype=torch.uint8, device=dev)
+        obs = torch.empty((T,) + tuple(self.obs.shape), dtype=self.obs.dtype, device=dev) if record_obs else None
+        probs = torch.empty((T, E, t.nA), dtype=torch.float32, device=dev) if record_probs else None
+        status = torch.full((E,), L.ST_OK, dtype=torch.int32, device=dev)
+        st = L.CollectState()
+        st.ep_t, st.obs_row, st.alive, st.obs = L.ptr(self._ep_t), L.ptr(self._obs_row), L.ptr(self.alive), L.ptr(self.obs)
+        st.obs_next, st.obs_init = L.ptr(self._next_obs), L.ptr(self._obs)
+        st.obs_bytes = self.obs.element_size() * int(np.prod(self.obs.shape[1:], dtype=np.int64))
+        out = L.CollectOut()
+        out.row, out.flags, out.obs, out.probs, out.status = L.ptr(row), L.ptr(flags), L.ptr(obs), L.ptr(probs), L.ptr(status)
+        L.check(L.load().offsim_vector_collect(C.byref(t.c), C.byref(env.state.c), C.byref(pol), L.PROB_F32 if f32 else L.PROB_F64,
+                                               env.reject_mode, T, cap, C.byref(st), C.byref(out), L.stream_ptr()))
+        self._keep = keep
+        if self.strict and bool((status == L.ST_KEYERROR).any()):
+            k = int(torch.nonzero(status == L.ST_KEYERROR)[0])
+            raise KeyError(self.table.z_of(int(env.state.cur_slot[k])))
+        served = (flags & L.COLLECT_SERVED) != 0
+        rl = row.clamp(min=0).to(torch.int64)
+
+        def take(col):
+            if t.N == 0:
+                return torch.zeros((T, E) + tuple(col.shape[1:]), dtype=col.dtype, device=dev)
+            v = col[rl]
+            return torch.where(served.reshape(served.shape + (1,) * (v.dim() - 2)), v, torch.zeros((), dtype=v.dtype, device=dev))
+
+        return Collected(obs=obs, probs=probs, row=row, action=take(self._a), reward=take(self._r), next_obs=take(self._next_obs),
+                         terminated=(flags & L.COLLECT_TERMINATED) != 0, truncated=(flags & L.COLLECT_TRUNCATED) != 0,
+                         reset=(flags & L.COLLECT_RESET) != 0, alive=(flags & L.COLLECT_ALIVE) != 0, final_obs=self.obs.clone(), status=status)
+
+    def _x_tables(self):
+        """The log's observations as the in-kernel network reads them: next_obs / obs [N, dO], f16 kept, anything else f32 (MLPPolicy.forward's
+        rule), made once."""
+        if self._x_rows is None:
+            from .obs_policy import obs_tensor
+            dev = self.table.device
+            self._x_rows = (obs_tensor(self._next_obs, dev), obs_tensor(self._obs, dev))
+        return self._x_rows
+
+    def _caller_tables(self, policy):
+        """p_next [N, nA] / p_init [N, nA] in CALLER row order: the policy at next_obs / obs of every logged row (offsim_collect_policy's
+        ROWS form; only initial rows of p_init are read)."""
+        from .obs_policy import RowPolicy
+        t = self.table
+        if isinstance(policy, RowPolicy):
+            pn, p0 = policy._dev(policy.p_next, t.device), policy._dev(policy.p_init, t.device)
+            for name, p in (("p_next", pn), ("p_init", p0)):
+                if p.dim() != 2 or p.shape[0] != t.N or p.shape[1] != t.nA:
+                    raise ValueError(f"RowPolicy: {name} must be [{t.N}, {t.nA}] (one row per logged transition), got {tuple(p.shape)}")
+        else:
+            pg, pk = policy.row_tables(t, self._obs, self._next_obs)  # grouped order / initial-row order
+            pn = torch.zeros((t.N, t.nA), dtype=pg.dtype, device=t.device)
+            p0 = torch.zeros((t.N, t.nA), dtype=pk.dtype, device=t.device)
+            if t.N:
+                pn[t.order.to(torch.int64)] = pg
+            if t.N0:
+                p0[t.init_orig.to(torch.int64)] = pk
+        if pn.dtype != p0.dtype:
+            pn, p0 = pn.to(torch.float64), p0.to(torch.float64)
+        return pn.contiguous(), p0.contiguous()
+
+
+Collected = namedtuple("Collected", "obs probs row action reward next_obs terminated truncated reset alive final_obs status")
+
+
+def _mlp_act(policy):
+    from .obs_policy import _ACT
+    return _ACT[policy.activation]
