@@ -556,6 +556,82 @@ int offsim_vector_collect(const offsim_table *t, offsim_rollouts *ro, const offs
                           int32_t reject_mode, int64_t T, int32_t max_episode_steps, const offsim_collect_state *st,
                           const offsim_collect_out *out, void *stream);
 
+/* ---- the PPO buffer of a collect (VectorPSRS.collect_ppo, ppo_advantages) ----------------------------------------------------
+ * The critic spinup's PPO trains beside the actor (offsim4rl/agents/ppo.py:18-27, MLPActorCriticRevealed.step: pi and v(obs)), as
+ * offsim_policy_mlp's network with one output unit and no softmax (spinup's MLPCritic: v = squeeze(v_net(obs), -1)):
+ *   out_v[m] = L_n(act(... act(L_1(x[rows[m]]))))   m < M, f32 [M]; the last layer must have out = 1.
+ * Arguments, limits and arithmetic as offsim_policy_mlp's. */
+int offsim_value_mlp(const void *x, int32_t x_dtype, int64_t n_x, int32_t dO, const int32_t *rows, int64_t M,
+                     const offsim_mlp_layer *layers_host, int32_t n_layers, int32_t activation, float slope, float *out_v, void *stream);
+
+/* offsim_vector_collect_ppo: offsim_vector_collect (same arguments, same trajectory: rows, flags, probabilities and the sampler state are
+ * those of offsim_vector_collect from the same state) plus the per-step records PPOAgentRevealed stores in its buffer
+ * (offsim4rl/agents/ppo.py:106-158: begin_episode / step take v(obs) with pi, commit_action takes logp of the action, end_episode / step
+ * hand a bootstrap value to PPOBuffer.finish_path):
+ *   value [T,R]        v(obs) at the observation the actor is asked at (0 where nothing was served);
+ *   logp [T,R]         log p_new[a] of the served action a: for OFFSIM_COLLECT_MLP from the logits as torch's Categorical.log_prob,
+ *                      z[a] - (max + log(sum(exp(z - max)))); otherwise logf((float)p_new[a]) (0 where nothing was served);
+ *   final_value [R]    v at the observation the environment holds after its last step -- for an environment that stopped (None, KeyError,
+ *                      no initial row), the observation it stopped at; 0 for an environment without a state at the call.  Written
+ *                      only when T > 0;
+ *   v_trunc [T,R]      (optional) at a step that truncates without terminating, v(next_obs) of the served row, before the reset; nothing
+ *                      is written at other steps.
+ * The critic (val->form), whatever the actor's form:
+ *   OFFSIM_VALUE_MLP   layers_host / activation / slope as offsim_value_mlp's, evaluated by the environment's wavefront through the same
+ *                      fmaf chains, so value / final_value / v_trunc equal offsim_value_mlp's output bit for bit.  Its weights are staged
+ *                      into LDS after the actor's: the actor's and the critic's floats together at most OFFSIM_COLLECT_MLP_MAX_FLOATS,
+ *                      otherwise OFFSIM_EUNSUPPORTED.  Observations x_start [R,dO] / x_next / x_init [N,dO] as offsim_collect_policy's
+ *                      (x_dtype must equal the actor's when the actor is OFFSIM_COLLECT_MLP).
+ *   OFFSIM_VALUE_ROWS  per-row f32 tables in caller row order, v_next[i] = v(next_obs of row i), v_init[i] = v(obs of row i), read through
+ *                      st->obs_row (which must be valid for every environment with a state, as for OFFSIM_COLLECT_ROWS). */
+#define OFFSIM_VALUE_MLP 0
+#define OFFSIM_VALUE_ROWS 1
+typedef struct offsim_collect_value {
+    int32_t form;                      /* OFFSIM_VALUE_*                                            */
+    int32_t n_layers;                  /* MLP: layers_host[n_layers] as offsim_value_mlp            */
+    const offsim_mlp_layer *layers_host;
+    int32_t activation;
+    float slope;
+    int32_t x_dtype;                   /* MLP: OFFSIM_F32 | OFFSIM_F16                              */
+    int32_t dO;
+    const void *x_start;               /* MLP: [R,dO]                                               */
+    const void *x_next;                /* MLP: [N,dO]                                               */
+    const void *x_init;                /* MLP: [N,dO]                                               */
+    const float *v_next;               /* ROWS: [N]                                                 */
+    const float *v_init;               /* ROWS: [N]                                                 */
+} offsim_collect_value;
+typedef struct offsim_collect_ppo_out {
+    float *value;                      /* [T,R]                                                     */
+    float *logp;                       /* [T,R]                                                     */
+    float *final_value;                /* [R]                                                       */
+    float *v_trunc;                    /* [T,R], or NULL                                            */
+} offsim_collect_ppo_out;
+int offsim_vector_collect_ppo(const offsim_table *t, offsim_rollouts *ro, const offsim_collect_policy *pol, const offsim_collect_value *val,
+                              int32_t prob_mode, int32_t reject_mode, int64_t T, int32_t max_episode_steps, const offsim_collect_state *st,
+                              const offsim_collect_out *out, const offsim_collect_ppo_out *ppo, void *stream);
+
+/* offsim_ppo_advantages: GAE-lambda advantages and rewards-to-go over step-major [T,E] records, with the path rules of the reference's
+ * agent, and spinup's advantage normalisation (spinup PPOBuffer.finish_path / get, driven by offsim4rl/agents/ppo.py:106-158; E
+ * environments = E MPI processes of local_steps_per_epoch = T).  Per environment e, over its valid steps t (flags & OFFSIM_COLLECT_SERVED):
+ *   a path ends at a step with OFFSIM_COLLECT_TERMINATED | OFFSIM_COLLECT_TRUNCATED (end_episode), with the bootstrap
+ *     OFFSIM_PPO_BOOT_REFERENCE  value[t] (end_episode's prev_v) if truncated or t = T - 1 (the epoch ended), else 0 (ppo.py:116-131);
+ *     OFFSIM_PPO_BOOT_SPINUP     0 if terminated, else v_trunc[t] (the textbook rule; v_trunc is then required);
+ *   a path still open after the last valid step bootstraps with final_value[e] (step's epoch cut, ppo.py:149-158, or a stopped
+ *   environment);
+ *   within a path (finish_path): delta_t = rew[t] + gamma V_next - value[t] (V_next: the path's next value, or the bootstrap),
+ *   adv[t] = sum_k (gamma lam)^k delta_{t+k}, ret[t] = sum_k gamma^k rew[t+k] + gamma^K bootstrap.
+ * Accumulated in f64, stored f32; invalid entries get 0.  adv_norm (optional): (adv - mean) / std over all valid entries of all
+ * environments, mean = sum(adv) / n, std = sqrt(sum((adv - mean)^2) / n) (mpi_statistics_scalar, the population std), reduced in a fixed
+ * order (the same bits every run); stats[0..1] = mean, std.  n = 0 leaves adv_norm = adv (zeros) and reports std = 0; a std of 0 with
+ * n > 0 divides as spinup does.  work: OFFSIM_PPO_WORK_DOUBLES(E) doubles of device scratch (needed with adv_norm).  One launch, three
+ * with adv_norm.  Argument validation happens before any HIP call. */
+#define OFFSIM_PPO_BOOT_REFERENCE 0
+#define OFFSIM_PPO_BOOT_SPINUP 1
+#define OFFSIM_PPO_WORK_DOUBLES(E) (3 * (((E) + 255) / 256))
+int offsim_ppo_advantages(const float *rew, const float *value, const uint8_t *flags, const float *final_value, const float *v_trunc,
+                          int64_t T, int64_t E, double gamma, double lam, int32_t bootstrap, float *adv, float *ret, float *adv_norm,
+                          double *stats, double *work, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

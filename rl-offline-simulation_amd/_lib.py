@@ -90,6 +90,26 @@ class CollectOut(C.Structure):
     _fields_ = [("row", _vp), ("flags", _vp), ("obs", _vp), ("probs", _vp), ("status", _vp)]
 
 
+VALUE_MLP, VALUE_ROWS = 0, 1
+PPO_BOOT_REFERENCE, PPO_BOOT_SPINUP = 0, 1
+
+
+def ppo_work_doubles(E):
+    """include/offsim.h: OFFSIM_PPO_WORK_DOUBLES(E)"""
+    return 3 * ((E + 255) // 256)
+
+
+class CollectValue(C.Structure):
+    """struct offsim_collect_value"""
+    _fields_ = [("form", _i32), ("n_layers", _i32), ("layers_host", C.POINTER(MLPLayer)), ("activation", _i32), ("slope", C.c_float),
+                ("x_dtype", _i32), ("dO", _i32), ("x_start", _vp), ("x_next", _vp), ("x_init", _vp), ("v_next", _vp), ("v_init", _vp)]
+
+
+class CollectPPOOut(C.Structure):
+    """struct offsim_collect_ppo_out"""
+    _fields_ = [("value", _vp), ("logp", _vp), ("final_value", _vp), ("v_trunc", _vp)]
+
+
 MAILBOX_MAX_ACTIONS = 24
 SERVER_CMD_STEP, SERVER_CMD_POP_ONE, SERVER_CMD_EXIT, SERVER_CMD_RESET = 1, 2, 3, 4
 SERVER_STARTING, SERVER_RUNNING, SERVER_EXITED = 1, 2, 3
@@ -154,6 +174,10 @@ SIGNATURES = {
     "offsim_policy_mlp": (C.c_int, [_vp, _i32, _i64, _i32, _vp, _i64, C.POINTER(MLPLayer), _i32, _i32, C.c_float, _vp, _vp]),
     "offsim_vector_collect": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), C.POINTER(CollectPolicy), _i32, _i32, _i64, _i32,
                                         C.POINTER(CollectState), C.POINTER(CollectOut), _vp]),
+    "offsim_value_mlp": (C.c_int, [_vp, _i32, _i64, _i32, _vp, _i64, C.POINTER(MLPLayer), _i32, _i32, C.c_float, _vp, _vp]),
+    "offsim_vector_collect_ppo": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), C.POINTER(CollectPolicy), C.POINTER(CollectValue), _i32, _i32,
+                                            _i64, _i32, C.POINTER(CollectState), C.POINTER(CollectOut), C.POINTER(CollectPPOOut), _vp]),
+    "offsim_ppo_advantages": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, C.c_double, C.c_double, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

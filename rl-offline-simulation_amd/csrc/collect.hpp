@@ -12,13 +12,21 @@
 //   3. the step's record ([T, R], step-major: a step's stores from all environments are adjacent);
 //   4. reset on done or at max_episode_steps (k_env_reset's logic, as k_vector_step's).
 // The environment's state lives in registers for the launch and is written back once at the end.
+//
+// VF (offsim_vector_collect_ppo) adds the critic of the PPO buffer, in either form whatever the actor's: at every live step v(obs) at the
+// observation the actor is asked at (VF = OFFSIM_VALUE_MLP: the same in-wave forward, its weights staged after the actor's; VF =
+// OFFSIM_VALUE_ROWS: v_next[row] / v_init[row]), logp of the served action, v(next_obs) of a step that truncates without terminating, and
+// after the last step v(obs) of the observation the environment holds.  VF = COLLECT_VF_NONE is offsim_vector_collect: none of it.
 #pragma once
+
+#include <type_traits>
 
 #define COLLECT_WAVES 8  // environments per workgroup: one copy of the weights in LDS serves eight wavefronts
 // candidates a step looks at per round (psrs_step's `width`; the served row and the draws consumed do not depend on it).  Every lane
 // that looks at a candidate gathers its columns from a random line of the log, and a step is usually served by the first or second
 // candidate, so 64 lanes per round made the kernel bound by that traffic.
 #define COLLECT_WIDTH 16
+#define COLLECT_VF_NONE -1  // VF of offsim_vector_collect: no critic
 
 struct CollectMlp {
     const float *W[PMLP_MAX_LAYERS];
@@ -30,6 +38,21 @@ struct CollectMlp {
     const void *x_start, *x_next, *x_init;
 };
 
+// the critic of offsim_vector_collect_ppo (offsim_collect_value): MLP layers as CollectMlp's (woff / boff from the LDS byte offset off_w),
+// or ROWS tables; and the PPO records (offsim_collect_ppo_out)
+struct CollectValue {
+    const float *W[PMLP_MAX_LAYERS];
+    const float *b[PMLP_MAX_LAYERS];
+    int in[PMLP_MAX_LAYERS], out[PMLP_MAX_LAYERS];
+    int woff[PMLP_MAX_LAYERS], boff[PMLP_MAX_LAYERS];
+    int n, act, dO;
+    float slope;
+    uint32_t off_w;
+    const void *x_start, *x_next, *x_init;
+    const float *v_next, *v_init;
+    offsim_collect_ppo_out rec;
+};
+
 struct CollectArgs {
     CollectMlp mlp;
     const void *p_next, *p_init, *pi;
@@ -39,6 +62,14 @@ struct CollectArgs {
     offsim_collect_out out;
     uint32_t off_pn, off_pf, off_act;  // byte offsets of the per-wave p_new (f64 slots), probs (f32) and activation buffers
 };
+
+// the kernel's arguments: offsim_vector_collect's instances (VF = COLLECT_VF_NONE) take CollectArgs alone, so their code and argument
+// layout are those of the kernel before the critic existed
+struct CollectPpoArgs : CollectArgs {
+    CollectValue V;
+};
+template <int VF>
+using CollectKArgs = std::conditional_t<VF == COLLECT_VF_NONE, CollectArgs, CollectPpoArgs>;
 
 __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's LDS writes are done
@@ -57,8 +88,39 @@ __device__ __forceinline__ void wave_copy_row(unsigned char *d, const unsigned c
 // obs_row encoding (offsim_eval_mc_rows_policy's out_obs_row): i >= 0 next_obs of caller row i, -2 - i obs of caller row i
 __device__ __forceinline__ bool collect_row_ok(int32_t v, int64_t N) { return (v >= 0 && v < N) || (v <= -2 && -2 - (int64_t)v < N); }
 
-template <typename PL, typename PROB, int FORM, typename XT>
-__global__ void __launch_bounds__(COLLECT_WAVES * WAVE) k_collect(offsim_table t, offsim_rollouts ro, CollectArgs A) {
+// The critic at an observation (moved false: the environment's x_start row; else obs_row encoding xrow), the same value in every lane.
+// MLP: the wave's forward through pmlp_unit over W^T in LDS, as the actor's (so offsim_value_mlp's bits); the last layer's one unit is
+// lane 0's chain.  It uses the wave's activation rows, which the actor's forward overwrites afterwards.  ROWS: the caller's tables.
+template <int VF, typename XT>
+__device__ __forceinline__ float collect_value(const CollectValue &V, const float *v_lds, float *act, int w_max, bool moved, int64_t r,
+                                               int32_t xrow, int lane) {
+    if constexpr (VF == OFFSIM_VALUE_ROWS) {
+        return xrow >= 0 ? V.v_next[xrow] : V.v_init[-2 - (int64_t)xrow];
+    } else {
+        const int dO = V.dO;
+        const XT *x = !moved ? (const XT *)V.x_start + r * dO
+                      : xrow >= 0 ? (const XT *)V.x_next + (int64_t)xrow * dO
+                                  : (const XT *)V.x_init + (-2 - (int64_t)xrow) * dO;
+        float *cur = act, *nxt = act + w_max;
+        for (int k = lane; k < dO; k += WAVE) cur[k] = pmlp_in<XT>(x, k);
+        wave_lds_sync();
+        for (int l = 0; l < V.n; l++) {
+            const int in = V.in[l], out = V.out[l];
+            const float *wt = v_lds + V.woff[l];
+            const float *bl = V.boff[l] >= 0 ? v_lds + V.boff[l] : nullptr;
+            const bool last = l == V.n - 1;
+            for (int j = lane; j < out; j += WAVE) nxt[j] = pmlp_unit(cur, wt + j, out, in, bl ? bl + j : nullptr, last, V.act, V.slope);
+            wave_lds_sync();
+            float *sw = cur;
+            cur = nxt;
+            nxt = sw;
+        }
+        return cur[0];
+    }
+}
+
+template <typename PL, typename PROB, int FORM, typename XT, int VF>
+__global__ void __launch_bounds__(COLLECT_WAVES * WAVE) k_collect(offsim_table t, offsim_rollouts ro, CollectKArgs<VF> A) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const int waves = blockDim.x / WAVE;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE), lane = threadIdx.x & (WAVE - 1);
@@ -83,6 +145,20 @@ __global__ void __launch_bounds__(COLLECT_WAVES * WAVE) k_collect(offsim_table t
     } else if constexpr (FORM == OFFSIM_COLLECT_TABULAR) {
         for (int i = threadIdx.x; i < t.n_slots * nA; i += blockDim.x) pi_lds[i] = ((const PROB *)A.pi)[i];
     }
+    float *v_lds = nullptr;  // the critic's W^T / b (VF = OFFSIM_VALUE_MLP)
+    if constexpr (VF == OFFSIM_VALUE_MLP) {
+        v_lds = (float *)(lds_raw + A.V.off_w);
+        for (int l = 0; l < A.V.n; l++) {
+            const int in = A.V.in[l], out = A.V.out[l];
+            const float *__restrict__ W = A.V.W[l];
+            for (int e = threadIdx.x; e < in * out; e += blockDim.x) {
+                const int j = e / in, k = e - j * in;
+                v_lds[A.V.woff[l] + k * out + j] = W[e];
+            }
+            if (A.V.boff[l] >= 0)
+                for (int j = threadIdx.x; j < out; j += blockDim.x) v_lds[A.V.boff[l] + j] = A.V.b[l][j];
+        }
+    }
     __syncthreads();
     const int r = blockIdx.x * waves + wave;
     if (r >= ro.R) return;
@@ -95,6 +171,8 @@ __global__ void __launch_bounds__(COLLECT_WAVES * WAVE) k_collect(offsim_table t
     bool alive = A.st.alive[r] != 0, moved = false, none = false;
     int status = slot < 0 ? OFFSIM_ST_INACTIVE : OFFSIM_ST_OK;
     if (FORM == OFFSIM_COLLECT_ROWS && status == OFFSIM_ST_OK && !collect_row_ok(xrow, t.N)) status = OFFSIM_ST_INACTIVE;  // (no tables row)
+    if (VF == OFFSIM_VALUE_ROWS && status == OFFSIM_ST_OK && !collect_row_ok(xrow, t.N)) status = OFFSIM_ST_INACTIVE;
+    const bool had_state = status == OFFSIM_ST_OK;
     bool live = status == OFFSIM_ST_OK;
 
     WaveRng rng;
@@ -124,14 +202,20 @@ __global__ void __launch_bounds__(COLLECT_WAVES * WAVE) k_collect(offsim_table t
             if (A.out.probs)
                 for (int a = lane; a < nA; a += WAVE) A.out.probs[o * nA + a] = 0.0f;
             if (A.out.obs) wave_copy_row((unsigned char *)A.out.obs + o * ob, nullptr, ob, lane);
+            if constexpr (VF != COLLECT_VF_NONE)
+                if (lane == 0) A.V.rec.value[o] = A.V.rec.logp[o] = 0.0f;
             continue;
         }
         if (A.out.obs) {
             const unsigned char *src = !moved ? obs_cur : xrow >= 0 ? obs_next + (int64_t)xrow * ob : obs_init + (-2 - (int64_t)xrow) * ob;
             wave_copy_row((unsigned char *)A.out.obs + o * ob, src, ob, lane);
         }
+        // 0. the critic at the current observation (the actor's forward reuses the activation rows after it)
+        float v = 0.0f;
+        if constexpr (VF != COLLECT_VF_NONE) v = collect_value<VF, XT>(A.V, v_lds, act_lds, A.mlp.w_max, moved, r, xrow, lane);
         // 1. the policy at the current observation
         const PROB *pn;
+        const float *logits = nullptr;  // MLP: the last layer's outputs, in the activation rows until the next forward
         if constexpr (FORM == OFFSIM_COLLECT_MLP) {
             const int dO = A.mlp.dO;
             const XT *x = !moved ? (const XT *)A.mlp.x_start + (int64_t)r * dO
@@ -152,6 +236,7 @@ __global__ void __launch_bounds__(COLLECT_WAVES * WAVE) k_collect(offsim_table t
                 nxt = sw;
             }
             if (lane == 0) pmlp_softmax(cur, nA, pf_lds);
+            logits = cur;
             wave_lds_sync();
             if (lane < nA) {
                 const float p = pf_lds[lane];
@@ -177,14 +262,29 @@ __global__ void __launch_bounds__(COLLECT_WAVES * WAVE) k_collect(offsim_table t
             if (lane == 0) {
                 A.out.row[o] = -1;
                 A.out.flags[o] = 0;
+                if constexpr (VF != COLLECT_VF_NONE) A.V.rec.value[o] = A.V.rec.logp[o] = 0.0f;
             }
             continue;
+        }
+        if constexpr (VF != COLLECT_VF_NONE) {  // the PPO records of a served step: v(obs), logp of the served action (lane 0)
+            if (lane == 0) {
+                const int a = t.a[s.g];
+                A.V.rec.value[o] = v;
+                if constexpr (FORM == OFFSIM_COLLECT_MLP) A.V.rec.logp[o] = pmlp_logp(logits, nA, a);
+                else A.V.rec.logp[o] = logf((float)pn[a]);
+            }
         }
         // 3. the record, 4. the reset at terminated / truncated
         const int32_t row = t.orig_idx[s.g];
         ep_t++;
         const bool term = s.done, trunc = A.max_ep > 0 && ep_t >= A.max_ep;
         uint32_t fl = OFFSIM_COLLECT_SERVED | (term ? OFFSIM_COLLECT_TERMINATED : 0u) | (trunc ? OFFSIM_COLLECT_TRUNCATED : 0u);
+        if constexpr (VF != COLLECT_VF_NONE) {  // v(next_obs) of the served row, before a reset replaces the observation (spinup's bootstrap)
+            if (trunc && !term && A.V.rec.v_trunc) {
+                const float vt = collect_value<VF, XT>(A.V, v_lds, act_lds, A.mlp.w_max, true, r, row, lane);
+                if (lane == 0) A.V.rec.v_trunc[o] = vt;
+            }
+        }
         slot = s.z_next;
         xrow = row;
         moved = true;
@@ -209,6 +309,10 @@ __global__ void __launch_bounds__(COLLECT_WAVES * WAVE) k_collect(offsim_table t
             A.out.row[o] = row;
             A.out.flags[o] = (uint8_t)fl;
         }
+    }
+    if constexpr (VF != COLLECT_VF_NONE) {  // the bootstrap of a path still open: v at the observation the environment holds (0: no state)
+        const float vf = had_state ? collect_value<VF, XT>(A.V, v_lds, act_lds, A.mlp.w_max, moved, r, xrow, lane) : 0.0f;
+        if (lane == 0) A.V.rec.final_value[r] = vf;
     }
     // the state, for the next call
     if (moved) wave_copy_row(obs_cur, xrow >= 0 ? obs_next + (int64_t)xrow * ob : obs_init + (-2 - (int64_t)xrow) * ob, ob, lane);
@@ -241,9 +345,10 @@ static size_t collect_lds_layout(int waves, size_t shared_bytes, int w_max, Coll
     return off;
 }
 
-extern "C" int offsim_vector_collect(const offsim_table *t, offsim_rollouts *ro, const offsim_collect_policy *pol, int32_t prob_mode,
-                                     int32_t reject_mode, int64_t T, int32_t max_episode_steps, const offsim_collect_state *st,
-                                     const offsim_collect_out *out, void *stream) {
+// Validation of offsim_vector_collect's arguments and the actor's part of A; `shared` gets the bytes of the actor's LDS region (weights or pi).
+static int collect_prepare(const offsim_table *t, offsim_rollouts *ro, const offsim_collect_policy *pol, int32_t prob_mode, int32_t reject_mode,
+                           int64_t T, int32_t max_episode_steps, const offsim_collect_state *st, const offsim_collect_out *out, CollectArgs &A,
+                           size_t &shared) {
     int rc = check_table(t);
     if (rc) return rc;
     if (!ro || ro->R < 0 || !pol || !st || !out || T < 0 || max_episode_steps < 0) return fail(OFFSIM_EINVAL, "vector_collect: bad argument%s");
@@ -254,10 +359,9 @@ extern "C" int offsim_vector_collect(const offsim_table *t, offsim_rollouts *ro,
         return fail(OFFSIM_EINVAL, "vector_collect: bad state (ep_t, obs_row, alive, obs, obs_next, obs_init, obs_bytes)%s");
     if (T > 0 && (!out->row || !out->flags)) return fail(OFFSIM_EINVAL, "vector_collect: out->row / out->flags is NULL%s");
     if (t->N0 > 0 && (!t->init_slot || !t->init_orig)) return fail(OFFSIM_EINVAL, "vector_collect: table has no init rows%s");
-    CollectArgs A;
     memset(&A, 0, sizeof(A));
     A.mlp.w_max = 0;
-    size_t shared = 0;
+    shared = 0;
     const size_t pb = prob_mode == OFFSIM_PROB_F32 ? 4 : 8;
     if (pol->form == OFFSIM_COLLECT_MLP) {
         const int n = pol->n_layers, dO = pol->dO;
@@ -310,34 +414,130 @@ extern "C" int offsim_vector_collect(const offsim_table *t, offsim_rollouts *ro,
     } else {
         return fail(OFFSIM_EINVAL, "vector_collect: unknown policy form%s");
     }
-    const size_t lds = collect_lds_layout(COLLECT_WAVES, shared, A.mlp.w_max, A);
-    if (lds > 160 * 1024) return fail(OFFSIM_EUNSUPPORTED, "vector_collect: the policy table and per-wave scratch exceed 160 KiB of LDS%s");
     A.reject_mode = reject_mode;
     A.max_ep = max_episode_steps;
     A.T = T;
     A.st = *st;
     A.out = *out;
-    if (ro->R == 0 || T == 0) return OFFSIM_OK;
+    return OFFSIM_OK;
+}
+
+// One launch of k_collect<..., VF> for the actor's form and the observations' type (XT: the in-kernel networks' input; float where none is).
+template <int VF>
+static int collect_launch(const offsim_table *t, offsim_rollouts *ro, int32_t form, int32_t x_dtype, int32_t prob_mode, size_t lds,
+                          const CollectKArgs<VF> &A, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     dim3 grid((unsigned)((ro->R + COLLECT_WAVES - 1) / COLLECT_WAVES)), block(COLLECT_WAVES * WAVE);
 #define LAUNCH_COLLECT(PL, PROB, FORM, XT)                                                               \
     do {                                                                                                  \
-        if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_collect<PL, PROB, FORM, XT>), (int)lds));          \
-        hipLaunchKernelGGL((k_collect<PL, PROB, FORM, XT>), grid, block, lds, s, *t, *ro, A);             \
+        if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_collect<PL, PROB, FORM, XT, VF>), (int)lds));      \
+        hipLaunchKernelGGL((k_collect<PL, PROB, FORM, XT, VF>), grid, block, lds, s, *t, *ro, A);         \
+    } while (0)
+#define LAUNCH_FORM_XT(PL, PROB, FORM)                                                                            \
+    do {                                                                                                          \
+        if (x_dtype == OFFSIM_F32) LAUNCH_COLLECT(PL, PROB, FORM, float);                                         \
+        else LAUNCH_COLLECT(PL, PROB, FORM, __half);                                                              \
     } while (0)
 #define LAUNCH_FORM(PL, PROB)                                                                                     \
     do {                                                                                                          \
-        if (pol->form == OFFSIM_COLLECT_MLP && pol->x_dtype == OFFSIM_F32) LAUNCH_COLLECT(PL, PROB, OFFSIM_COLLECT_MLP, float); \
-        else if (pol->form == OFFSIM_COLLECT_MLP) LAUNCH_COLLECT(PL, PROB, OFFSIM_COLLECT_MLP, __half);            \
-        else if (pol->form == OFFSIM_COLLECT_ROWS) LAUNCH_COLLECT(PL, PROB, OFFSIM_COLLECT_ROWS, float);           \
-        else LAUNCH_COLLECT(PL, PROB, OFFSIM_COLLECT_TABULAR, float);                                              \
+        if (form == OFFSIM_COLLECT_MLP) LAUNCH_FORM_XT(PL, PROB, OFFSIM_COLLECT_MLP);                             \
+        else if constexpr (VF == OFFSIM_VALUE_MLP) {                                                              \
+            if (form == OFFSIM_COLLECT_ROWS) LAUNCH_FORM_XT(PL, PROB, OFFSIM_COLLECT_ROWS);                       \
+            else LAUNCH_FORM_XT(PL, PROB, OFFSIM_COLLECT_TABULAR);                                                \
+        } else if (form == OFFSIM_COLLECT_ROWS) LAUNCH_COLLECT(PL, PROB, OFFSIM_COLLECT_ROWS, float);             \
+        else LAUNCH_COLLECT(PL, PROB, OFFSIM_COLLECT_TABULAR, float);                                             \
     } while (0)
     if (prob_mode == OFFSIM_PROB_F32) LAUNCH_FORM(float, float);
     else if (t->plog_dtype == OFFSIM_F32) LAUNCH_FORM(float, double);
     else if (t->plog_dtype == OFFSIM_F64) LAUNCH_FORM(double, double);
     else LAUNCH_FORM(__half, double);
 #undef LAUNCH_FORM
+#undef LAUNCH_FORM_XT
 #undef LAUNCH_COLLECT
     LAUNCH_CHECK();
     return OFFSIM_OK;
+}
+
+extern "C" int offsim_vector_collect(const offsim_table *t, offsim_rollouts *ro, const offsim_collect_policy *pol, int32_t prob_mode,
+                                     int32_t reject_mode, int64_t T, int32_t max_episode_steps, const offsim_collect_state *st,
+                                     const offsim_collect_out *out, void *stream) {
+    CollectArgs A;
+    size_t shared;
+    int rc = collect_prepare(t, ro, pol, prob_mode, reject_mode, T, max_episode_steps, st, out, A, shared);
+    if (rc) return rc;
+    const size_t lds = collect_lds_layout(COLLECT_WAVES, shared, A.mlp.w_max, A);
+    if (lds > 160 * 1024) return fail(OFFSIM_EUNSUPPORTED, "vector_collect: the policy table and per-wave scratch exceed 160 KiB of LDS%s");
+    if (ro->R == 0 || T == 0) return OFFSIM_OK;
+    return collect_launch<COLLECT_VF_NONE>(t, ro, pol->form, pol->form == OFFSIM_COLLECT_MLP ? pol->x_dtype : OFFSIM_F32, prob_mode, lds, A, stream);
+}
+
+extern "C" int offsim_vector_collect_ppo(const offsim_table *t, offsim_rollouts *ro, const offsim_collect_policy *pol, const offsim_collect_value *val,
+                                         int32_t prob_mode, int32_t reject_mode, int64_t T, int32_t max_episode_steps, const offsim_collect_state *st,
+                                         const offsim_collect_out *out, const offsim_collect_ppo_out *ppo, void *stream) {
+    CollectPpoArgs A;
+    size_t shared;
+    int rc = collect_prepare(t, ro, pol, prob_mode, reject_mode, T, max_episode_steps, st, out, A, shared);
+    if (rc) return rc;
+    memset(&A.V, 0, sizeof(A.V));
+    if (!val || !ppo) return fail(OFFSIM_EINVAL, "vector_collect_ppo: val / ppo is NULL%s");
+    if (T > 0 && (!ppo->value || !ppo->logp || !ppo->final_value))
+        return fail(OFFSIM_EINVAL, "vector_collect_ppo: ppo->value / logp / final_value is NULL%s");
+    CollectValue &V = A.V;
+    int x_dtype = pol->form == OFFSIM_COLLECT_MLP ? pol->x_dtype : OFFSIM_F32;
+    if (val->form == OFFSIM_VALUE_MLP) {
+        const int n = val->n_layers, dO = val->dO;
+        if (!val->layers_host || n < 1 || n > PMLP_MAX_LAYERS) return fail(OFFSIM_EINVAL, "vector_collect_ppo: the critic has 1 to 4 Linear layers%s");
+        if (val->x_dtype != OFFSIM_F32 && val->x_dtype != OFFSIM_F16) return fail(OFFSIM_EINVAL, "vector_collect_ppo: critic x_dtype must be OFFSIM_F32 or OFFSIM_F16%s");
+        if (pol->form == OFFSIM_COLLECT_MLP && val->x_dtype != pol->x_dtype)
+            return fail(OFFSIM_EINVAL, "vector_collect_ppo: the actor and the critic read observations of different types%s");
+        if (val->activation != OFFSIM_ACT_IDENTITY && val->activation != OFFSIM_ACT_TANH && val->activation != OFFSIM_ACT_RELU &&
+            val->activation != OFFSIM_ACT_LEAKY_RELU)
+            return fail(OFFSIM_EINVAL, "vector_collect_ppo: unknown critic activation%s");
+        if (dO < 1 || dO > PMLP_MAX_IN) return fail(OFFSIM_EINVAL, "vector_collect_ppo: critic observation width must be 1..128%s");
+        if (!val->x_start || (t->N > 0 && (!val->x_next || !val->x_init))) return fail(OFFSIM_EINVAL, "vector_collect_ppo: critic x_start / x_next / x_init is NULL%s");
+        x_dtype = val->x_dtype;
+        int floats = 0, w_max = dO;
+        for (int l = 0; l < n; l++) {
+            const offsim_mlp_layer &y = val->layers_host[l];
+            const bool last = l == n - 1;
+            if (!y.W) return fail(OFFSIM_EINVAL, "vector_collect_ppo: a critic layer's W is NULL%s");
+            if (y.in != (l == 0 ? dO : val->layers_host[l - 1].out)) return fail(OFFSIM_EINVAL, "vector_collect_ppo: critic layer widths do not chain%s");
+            if (last ? y.out != 1 : (y.out < 1 || y.out > PMLP_MAX_HIDDEN))
+                return fail(OFFSIM_EINVAL, last ? "vector_collect_ppo: the critic's last layer must have one output unit%s" : "vector_collect_ppo: critic hidden width above 256%s");
+            V.W[l] = y.W;
+            V.b[l] = y.b;
+            V.in[l] = y.in;
+            V.out[l] = y.out;
+            V.woff[l] = floats;
+            floats += y.in * y.out;
+            V.boff[l] = y.b ? floats : -1;
+            floats += y.b ? y.out : 0;
+            if (y.out > w_max) w_max = y.out;
+        }
+        if (A.mlp.floats + floats > OFFSIM_COLLECT_MLP_MAX_FLOATS)
+            return fail(OFFSIM_EUNSUPPORTED, "vector_collect_ppo: the actor's and the critic's weights exceed OFFSIM_COLLECT_MLP_MAX_FLOATS (64 KiB of LDS)%s");
+        V.n = n;
+        V.act = val->activation;
+        V.slope = val->slope;
+        V.dO = dO;
+        V.x_start = val->x_start;
+        V.x_next = val->x_next;
+        V.x_init = val->x_init;
+        if (w_max > A.mlp.w_max) A.mlp.w_max = w_max;
+        const size_t actor = (shared + 15) & ~(size_t)15;
+        V.off_w = (uint32_t)((size_t)COLLECT_WAVES * (WAVE + 1) * sizeof(Jump) + actor);
+        shared = actor + (size_t)floats * sizeof(float);
+    } else if (val->form == OFFSIM_VALUE_ROWS) {
+        if (t->N > 0 && (!val->v_next || !val->v_init)) return fail(OFFSIM_EINVAL, "vector_collect_ppo: v_next / v_init is NULL%s");
+        V.v_next = val->v_next;
+        V.v_init = val->v_init;
+    } else {
+        return fail(OFFSIM_EINVAL, "vector_collect_ppo: unknown critic form%s");
+    }
+    V.rec = *ppo;
+    const size_t lds = collect_lds_layout(COLLECT_WAVES, shared, A.mlp.w_max, A);
+    if (lds > 160 * 1024) return fail(OFFSIM_EUNSUPPORTED, "vector_collect_ppo: the policy table, the critic and per-wave scratch exceed 160 KiB of LDS%s");
+    if (ro->R == 0 || T == 0) return OFFSIM_OK;
+    if (val->form == OFFSIM_VALUE_MLP) return collect_launch<OFFSIM_VALUE_MLP>(t, ro, pol->form, x_dtype, prob_mode, lds, A, stream);
+    return collect_launch<OFFSIM_VALUE_ROWS>(t, ro, pol->form, x_dtype, prob_mode, lds, A, stream);
 }

@@ -2226,26 +2226,28 @@ extern "C" int offsim_encode_mlp(const void *x, int32_t x_dtype, int64_t N, int3
 // ---- the policy network of a row-policy evalMC: probs = softmax(MLP(x[rows])) (csrc/policy_mlp.hpp) ----
 #include "policy_mlp.hpp"
 
-extern "C" int offsim_policy_mlp(const void *x, int32_t x_dtype, int64_t n_x, int32_t dO, const int32_t *rows, int64_t M,
-                                 const offsim_mlp_layer *layers_host, int32_t n_layers, int32_t activation, float slope, float *out_probs,
-                                 void *stream) {
-    if (M < 0 || n_x < 0 || dO <= 0 || !layers_host) return fail(OFFSIM_EINVAL, "policy_mlp: bad argument%s");
-    if (x_dtype != OFFSIM_F32 && x_dtype != OFFSIM_F16) return fail(OFFSIM_EINVAL, "policy_mlp: x_dtype must be OFFSIM_F32 or OFFSIM_F16%s");
-    if (n_layers < 1 || n_layers > PMLP_MAX_LAYERS) return fail(OFFSIM_EINVAL, "policy_mlp: 1 to 4 Linear layers%s");
+// the forward of offsim_policy_mlp (value false: softmax over the last layer's units) and offsim_value_mlp (value true: the last layer has
+// one unit, written as it is); `who` names the entry point in the error messages
+static int mlp_forward(const void *x, int32_t x_dtype, int64_t n_x, int32_t dO, const int32_t *rows, int64_t M, const offsim_mlp_layer *layers_host,
+                       int32_t n_layers, int32_t activation, float slope, float *out, void *stream, bool value, const char *who) {
+    if (M < 0 || n_x < 0 || dO <= 0 || !layers_host) return fail(OFFSIM_EINVAL, "%s: bad argument", who);
+    if (x_dtype != OFFSIM_F32 && x_dtype != OFFSIM_F16) return fail(OFFSIM_EINVAL, "%s: x_dtype must be OFFSIM_F32 or OFFSIM_F16", who);
+    if (n_layers < 1 || n_layers > PMLP_MAX_LAYERS) return fail(OFFSIM_EINVAL, "%s: 1 to 4 Linear layers", who);
     if (activation != OFFSIM_ACT_IDENTITY && activation != OFFSIM_ACT_TANH && activation != OFFSIM_ACT_RELU && activation != OFFSIM_ACT_LEAKY_RELU)
-        return fail(OFFSIM_EINVAL, "policy_mlp: unknown activation%s");
-    if (dO > PMLP_MAX_IN) return fail(OFFSIM_EINVAL, "policy_mlp: observation width above 128%s");
+        return fail(OFFSIM_EINVAL, "%s: unknown activation", who);
+    if (dO > PMLP_MAX_IN) return fail(OFFSIM_EINVAL, "%s: observation width above 128", who);
     PmlpLayers L{};
     L.n = n_layers;
     L.w_max = dO;
     L.w_floats = 0;
     for (int l = 0; l < n_layers; l++) {
         const offsim_mlp_layer &y = layers_host[l];
-        if (!y.W) return fail(OFFSIM_EINVAL, "policy_mlp: a layer's W is NULL%s");
-        if (y.in != (l == 0 ? dO : layers_host[l - 1].out)) return fail(OFFSIM_EINVAL, "policy_mlp: layer widths do not chain%s");
+        if (!y.W) return fail(OFFSIM_EINVAL, "%s: a layer's W is NULL", who);
+        if (y.in != (l == 0 ? dO : layers_host[l - 1].out)) return fail(OFFSIM_EINVAL, "%s: layer widths do not chain", who);
         const bool last = l == n_layers - 1;
+        if (value && last && y.out != 1) return fail(OFFSIM_EINVAL, "%s: the last layer must have one output unit", who);
         if (y.out < 1 || y.out > (last ? PMLP_MAX_ACTIONS : PMLP_MAX_HIDDEN))
-            return fail(OFFSIM_EINVAL, last ? "policy_mlp: more than 16 actions%s" : "policy_mlp: hidden width above 256%s");
+            return fail(OFFSIM_EINVAL, last ? "%s: more than 16 actions" : "%s: hidden width above 256", who);
         L.W[l] = y.W;
         L.b[l] = y.b;
         L.in[l] = y.in;
@@ -2256,22 +2258,39 @@ extern "C" int offsim_policy_mlp(const void *x, int32_t x_dtype, int64_t n_x, in
         if (need > L.w_floats) L.w_floats = need;
     }
     if (M == 0) return OFFSIM_OK;
-    if (!x || !out_probs) return fail(OFFSIM_EINVAL, "policy_mlp: x / out_probs is NULL%s");
+    if (!x || !out) return fail(OFFSIM_EINVAL, value ? "%s: x / out_v is NULL" : "%s: x / out_probs is NULL", who);
     const size_t lds = policy_mlp_lds_bytes(L);
     const uint64_t nb = (uint64_t)((M + PMLP_TM - 1) / PMLP_TM);
-    if (nb > 0x7fffffffull) return fail(OFFSIM_EINVAL, "policy_mlp: too many rows%s");
+    if (nb > 0x7fffffffull) return fail(OFFSIM_EINVAL, "%s: too many rows", who);
     hipStream_t st = (hipStream_t)stream;
     const float sl = slope;
-    if (x_dtype == OFFSIM_F32) {
-        if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_policy_mlp<float>), (int)lds));
-        hipLaunchKernelGGL(k_policy_mlp<float>, dim3((unsigned)nb), dim3(256), lds, st, (const float *)x, n_x, dO, rows, M, L, activation, sl, out_probs);
-    } else {
-        if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_policy_mlp<__half>), (int)lds));
-        hipLaunchKernelGGL(k_policy_mlp<__half>, dim3((unsigned)nb), dim3(256), lds, st, (const __half *)x, n_x, dO, rows, M, L, activation, sl, out_probs);
-    }
+#define LAUNCH_PMLP(XT, V)                                                                                                              \
+    do {                                                                                                                                \
+        if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_policy_mlp<XT, V>), (int)lds));                                                  \
+        hipLaunchKernelGGL((k_policy_mlp<XT, V>), dim3((unsigned)nb), dim3(256), lds, st, (const XT *)x, n_x, dO, rows, M, L, activation, sl, out); \
+    } while (0)
+    if (x_dtype == OFFSIM_F32 && !value) LAUNCH_PMLP(float, false);
+    else if (!value) LAUNCH_PMLP(__half, false);
+    else if (x_dtype == OFFSIM_F32) LAUNCH_PMLP(float, true);
+    else LAUNCH_PMLP(__half, true);
+#undef LAUNCH_PMLP
     LAUNCH_CHECK();
     return OFFSIM_OK;
 }
 
+extern "C" int offsim_policy_mlp(const void *x, int32_t x_dtype, int64_t n_x, int32_t dO, const int32_t *rows, int64_t M,
+                                 const offsim_mlp_layer *layers_host, int32_t n_layers, int32_t activation, float slope, float *out_probs,
+                                 void *stream) {
+    return mlp_forward(x, x_dtype, n_x, dO, rows, M, layers_host, n_layers, activation, slope, out_probs, stream, false, "policy_mlp");
+}
+
+extern "C" int offsim_value_mlp(const void *x, int32_t x_dtype, int64_t n_x, int32_t dO, const int32_t *rows, int64_t M,
+                                const offsim_mlp_layer *layers_host, int32_t n_layers, int32_t activation, float slope, float *out_v, void *stream) {
+    return mlp_forward(x, x_dtype, n_x, dO, rows, M, layers_host, n_layers, activation, slope, out_v, stream, true, "value_mlp");
+}
+
 // ---- a learner's data collection: T steps of policy -> PSRS.step -> reset per launch (csrc/collect.hpp) ----
 #include "collect.hpp"
+
+// ---- the PPO buffer: GAE-lambda, rewards-to-go and spinup's normalisation over [T, E] records (csrc/ppo_buffer.hpp) ----
+#include "ppo_buffer.hpp"

@@ -61,6 +61,17 @@ __device__ __forceinline__ void pmlp_softmax(const float *z, int nA, float *o) {
         if (a < nA) o[a] = e[a] / s;
 }
 
+// log of the probability of action a under the logits z[0..nA) (torch.distributions.Categorical(logits=...).log_prob(a), which
+// normalises by logsumexp = max + log(sum(exp(z - max)))): z[a] - (max + logf(sum)), the max and the sum in pmlp_softmax's order.  One
+// thread per row (the PPO buffer's logp, offsim_vector_collect_ppo).
+__device__ __forceinline__ float pmlp_logp(const float *z, int nA, int a) {
+    float mx = z[0];
+    for (int b = 1; b < nA; b++) mx = z[b] > mx ? z[b] : mx;
+    float s = 0.0f;
+    for (int b = 0; b < nA; b++) s = s + expf(z[b] - mx);
+    return z[a] - (mx + logf(s));
+}
+
 template <typename XT>
 __device__ __forceinline__ float pmlp_in(const XT *x, int64_t i);
 template <>
@@ -68,7 +79,9 @@ __device__ __forceinline__ float pmlp_in<float>(const float *x, int64_t i) { ret
 template <>
 __device__ __forceinline__ float pmlp_in<__half>(const __half *x, int64_t i) { return __half2float(x[i]); }
 
-template <typename XT>
+// VALUE: the critic of the same shape (offsim_value_mlp, spinup's MLPCritic: v = squeeze(v_net(obs), -1)): the last layer has one unit and
+// no softmax follows, probs is then out[M].
+template <typename XT, bool VALUE>
 __global__ void __launch_bounds__(256) k_policy_mlp(const XT *__restrict__ x, int64_t n_x, int dO, const int32_t *__restrict__ rows, int64_t M,
                                                     PmlpLayers L, int act, float slope, float *__restrict__ probs) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -106,6 +119,10 @@ __global__ void __launch_bounds__(256) k_policy_mlp(const XT *__restrict__ x, in
         float *t = cur;
         cur = nxt;
         nxt = t;
+    }
+    if constexpr (VALUE) {
+        for (int m = threadIdx.x; m < tm; m += blockDim.x) probs[m0 + m] = cur[m * ld];
+        return;
     }
     // softmax of the logits (torch.distributions.Categorical(logits=...).probs)
     const int nA = L.out[L.n - 1];

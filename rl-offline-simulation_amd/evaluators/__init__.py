@@ -4,4 +4,5 @@ from .trivial_baselines import FollowObservationOnly, FollowActionOnly, ServeRan
 from .queue_evaluator import QueueEvaluator, BatchedQueueEvaluator  # noqa: F401
 from .psrs_exo import PSRS_Exo  # noqa: F401
 from .vector_env import VectorPSRS  # noqa: F401
-from .obs_policy import MLPPolicy, RowPolicy, CallablePolicy  # noqa: F401
+from .obs_policy import MLPPolicy, RowPolicy, CallablePolicy, MLPValue, RowValue  # noqa: F401
+from .ppo_buffer import PPOBatch, ppo_advantages  # noqa: F401

@@ -39,6 +39,38 @@ def obs_tensor(obs, device):
     return t.reshape(t.shape[0], -1).contiguous()
 
 
+def _sequential_layers(net, who):
+    """(layers [(W, b)], activation, slope) of an nn.Sequential of Linear layers with one activation kind between them, optionally
+    followed by one nn.Identity (spinup's mlp(..., output_activation=nn.Identity)); anything else raises TypeError."""
+    kinds = {torch.nn.Tanh: "tanh", torch.nn.ReLU: "relu", torch.nn.LeakyReLU: "leaky_relu", torch.nn.Identity: "identity"}
+    mods = list(net)
+    if len(mods) >= 2 and type(mods[-1]) is torch.nn.Identity and isinstance(mods[-2], torch.nn.Linear):
+        mods = mods[:-1]
+    layers, acts, slope, expect_linear = [], [], 0.01, True
+    for mod in mods:
+        if isinstance(mod, torch.nn.Linear):
+            if not expect_linear and layers:
+                raise TypeError(f"{who}.from_torch: two Linear layers without an activation between them")
+            layers.append((mod.weight, mod.bias))
+            expect_linear = False
+        elif type(mod) in kinds:
+            if expect_linear:
+                raise TypeError(f"{who}.from_torch: an activation must follow a Linear layer")
+            acts.append(kinds[type(mod)])
+            if isinstance(mod, torch.nn.LeakyReLU):
+                slope = float(mod.negative_slope)
+            expect_linear = True
+        else:
+            raise TypeError(f"{who}.from_torch: unsupported module {type(mod).__name__} (Linear, Tanh, ReLU, LeakyReLU, Identity only)")
+    if not layers or expect_linear:
+        raise TypeError(f"{who}.from_torch: the network must end with a Linear layer (its outputs are the logits)")
+    if len(set(acts)) > 1:
+        raise TypeError(f"{who}.from_torch: one activation kind between all layers, got {acts}")
+    if acts and acts[0] == "leaky_relu" and len({float(x.negative_slope) for x in mods if isinstance(x, torch.nn.LeakyReLU)}) > 1:
+        raise TypeError(f"{who}.from_torch: LeakyReLU layers with different slopes")
+    return layers, acts[0] if acts else "identity", slope
+
+
 class ObsPolicy:
     """Base: a policy over observations, turned into (P_next grouped [N, nA], P_init [N0, nA]) device tensors for a table."""
 
@@ -46,63 +78,28 @@ class ObsPolicy:
         raise NotImplementedError
 
 
-class MLPPolicy(ObsPolicy):
-    """probs = softmax(L_n(act(... act(L_1(obs))))) -- spinup's MLPCategoricalActor (ppo.py:18-27) -- on the HIP forward.
-
-    weights: list of (W [out, in], b [out] or None), state_dict layout; activation: 'tanh' | 'relu' | 'leaky_relu' | 'identity' between
-    layers (slope: leaky_relu's negative slope).  1-4 layers, observation width <= 128, hidden widths <= 256, <= 16 actions."""
+class _MLPNet:
+    """Linear layers with one activation kind between them, in state_dict layout as the HIP forwards read them (MLPPolicy, MLPValue)."""
 
     def __init__(self, weights, activation="tanh", slope=0.01):
         if activation not in _ACT:
-            raise ValueError(f"MLPPolicy: activation must be one of {sorted(_ACT)}, got {activation!r}")
+            raise ValueError(f"{type(self).__name__}: activation must be one of {sorted(_ACT)}, got {activation!r}")
         if not 1 <= len(weights) <= L.POLICY_MLP_MAX_LAYERS:
-            raise ValueError(f"MLPPolicy: 1 to {L.POLICY_MLP_MAX_LAYERS} Linear layers, got {len(weights)}")
+            raise ValueError(f"{type(self).__name__}: 1 to {L.POLICY_MLP_MAX_LAYERS} Linear layers, got {len(weights)}")
         self.weights = []
         for W, b in weights:
             W = torch.as_tensor(W.detach() if isinstance(W, torch.Tensor) else np.asarray(W)).to(torch.float32).contiguous()
             b = None if b is None else torch.as_tensor(b.detach() if isinstance(b, torch.Tensor) else np.asarray(b)).to(torch.float32).contiguous()
             if W.dim() != 2 or (b is not None and b.shape != (W.shape[0],)):
-                raise ValueError("MLPPolicy: every layer is (W [out, in], b [out] or None)")
+                raise ValueError(f"{type(self).__name__}: every layer is (W [out, in], b [out] or None)")
             self.weights.append((W, b))
         for (W0, _), (W1, _) in zip(self.weights, self.weights[1:]):
             if W1.shape[1] != W0.shape[0]:
-                raise ValueError("MLPPolicy: layer widths do not chain")
+                raise ValueError(f"{type(self).__name__}: layer widths do not chain")
         self.activation, self.slope = activation, float(slope)
         self.nA = int(self.weights[-1][0].shape[0])
         self.dO = int(self.weights[0][0].shape[1])
         self._dev = {}
-
-    @classmethod
-    def from_torch(cls, m):
-        """An nn.Sequential of Linear and Tanh | ReLU | LeakyReLU | Identity (one activation kind, between the Linear layers), or any object
-        with such a `.logits_net` (spinup's MLPCategoricalActor).  Anything else is refused."""
-        net = m.logits_net if hasattr(m, "logits_net") else m
-        if not isinstance(net, torch.nn.Sequential):
-            raise TypeError(f"MLPPolicy.from_torch: needs an nn.Sequential (or an object with .logits_net), got {type(m).__name__}")
-        kinds = {torch.nn.Tanh: "tanh", torch.nn.ReLU: "relu", torch.nn.LeakyReLU: "leaky_relu", torch.nn.Identity: "identity"}
-        layers, acts, slope, expect_linear = [], [], 0.01, True
-        for mod in net:
-            if isinstance(mod, torch.nn.Linear):
-                if not expect_linear and layers:
-                    raise TypeError("MLPPolicy.from_torch: two Linear layers without an activation between them")
-                layers.append((mod.weight, mod.bias))
-                expect_linear = False
-            elif type(mod) in kinds:
-                if expect_linear:
-                    raise TypeError("MLPPolicy.from_torch: an activation must follow a Linear layer")
-                acts.append(kinds[type(mod)])
-                if isinstance(mod, torch.nn.LeakyReLU):
-                    slope = float(mod.negative_slope)
-                expect_linear = True
-            else:
-                raise TypeError(f"MLPPolicy.from_torch: unsupported module {type(mod).__name__} (Linear, Tanh, ReLU, LeakyReLU, Identity only)")
-        if not layers or expect_linear:
-            raise TypeError("MLPPolicy.from_torch: the network must end with a Linear layer (its outputs are the logits)")
-        if len(set(acts)) > 1:
-            raise TypeError(f"MLPPolicy.from_torch: one activation kind between all layers, got {acts}")
-        if acts and acts[0] == "leaky_relu" and len({float(x.negative_slope) for x in net if isinstance(x, torch.nn.LeakyReLU)}) > 1:
-            raise TypeError("MLPPolicy.from_torch: LeakyReLU layers with different slopes")
-        return cls(layers, acts[0] if acts else "identity", slope)
 
     def _device_weights(self, device):
         key = str(device)
@@ -115,6 +112,23 @@ class MLPPolicy(ObsPolicy):
                 arr[i].out = int(W.shape[0])
             self._dev[key] = (ws, arr)
         return self._dev[key]
+
+
+class MLPPolicy(_MLPNet, ObsPolicy):
+    """probs = softmax(L_n(act(... act(L_1(obs))))) -- spinup's MLPCategoricalActor (ppo.py:18-27) -- on the HIP forward.
+
+    weights: list of (W [out, in], b [out] or None), state_dict layout; activation: 'tanh' | 'relu' | 'leaky_relu' | 'identity' between
+    layers (slope: leaky_relu's negative slope).  1-4 layers, observation width <= 128, hidden widths <= 256, <= 16 actions."""
+
+    @classmethod
+    def from_torch(cls, m):
+        """An nn.Sequential of Linear and Tanh | ReLU | LeakyReLU | Identity (one activation kind, between the Linear layers), or any object
+        with such a `.logits_net` (spinup's MLPCategoricalActor).  A trailing nn.Identity after the last Linear (spinup's mlp() output
+        activation) is dropped.  Anything else is refused."""
+        net = m.logits_net if hasattr(m, "logits_net") else m
+        if not isinstance(net, torch.nn.Sequential):
+            raise TypeError(f"MLPPolicy.from_torch: needs an nn.Sequential (or an object with .logits_net), got {type(m).__name__}")
+        return cls(*_sequential_layers(net, "MLPPolicy"))
 
     def forward(self, x, rows=None, out=None):
         """probs [M, nA] f32 on x's device: x [n, dO] f32 / f16 device tensor, rows (optional) [M] int32 gather index into x."""
@@ -161,6 +175,62 @@ class RowPolicy(ObsPolicy):
             if p.dim() != 2 or p.shape[0] != table.N or p.shape[1] != table.nA:
                 raise ValueError(f"RowPolicy: {name} must be [{table.N}, {table.nA}] (one row per logged transition), got {tuple(p.shape)}")
         return gather_rows(pn, table.order), gather_rows(p0, table.init_orig)
+
+
+class MLPValue(_MLPNet):
+    """v = L_n(act(... act(L_1(obs)))) with one output unit -- spinup's MLPCritic (ppo.py:18-27: v = squeeze(v_net(obs), -1)) -- on the
+    HIP forward (offsim_value_mlp), and the critic VectorPSRS.collect_ppo runs inside its kernel.  Layers, activations and limits are
+    MLPPolicy's; the last layer has one output."""
+
+    def __init__(self, weights, activation="tanh", slope=0.01):
+        super().__init__(weights, activation, slope)
+        if self.nA != 1:
+            raise ValueError(f"MLPValue: the last layer must have one output, got {self.nA}")
+
+    @classmethod
+    def from_torch(cls, m):
+        """An nn.Sequential as MLPPolicy.from_torch takes, ending in Linear(H, 1) (a trailing nn.Identity is dropped), or any object with
+        such a `.v_net` (spinup's MLPCritic)."""
+        net = m.v_net if hasattr(m, "v_net") else m
+        if not isinstance(net, torch.nn.Sequential):
+            raise TypeError(f"MLPValue.from_torch: needs an nn.Sequential (or an object with .v_net), got {type(m).__name__}")
+        return cls(*_sequential_layers(net, "MLPValue"))
+
+    def forward(self, x, rows=None, out=None):
+        """v [M] f32 on x's device: x [n, dO] f32 / f16 device tensor, rows (optional) [M] int32 gather index into x."""
+        if x.dim() != 2 or x.shape[1] != self.dO:
+            raise ValueError(f"MLPValue: observations of width {self.dO} expected, got shape {tuple(x.shape)}")
+        if x.dtype not in (torch.float32, torch.float16):
+            x = x.to(torch.float32)
+        x = x.contiguous()
+        if rows is not None:
+            rows = rows.to(device=x.device, dtype=torch.int32).contiguous()
+        M = int(x.shape[0]) if rows is None else int(rows.numel())
+        if out is None:
+            out = torch.empty((M,), dtype=torch.float32, device=x.device)
+        ws, arr = self._device_weights(x.device)
+        L.check(L.load().offsim_value_mlp(L.ptr(x) if x.numel() else None, L.F32 if x.dtype == torch.float32 else L.F16, int(x.shape[0]),
+                                          self.dO, L.ptr(rows) if rows is not None and M else None, M, arr, len(ws), _ACT[self.activation],
+                                          self.slope, L.ptr(out) if M else None, L.stream_ptr()))
+        return out
+
+
+class RowValue:
+    """A critic as per-row values in caller order: v_next[i] = v(next_obs[i]), v_init[i] = v(obs[i]) (only the rows with t == 0 are
+    read) -- any torch critic through its tables, for VectorPSRS.collect_ppo (offsim_collect_value's ROWS form).  Read as f32."""
+
+    def __init__(self, v_next, v_init):
+        self.v_next, self.v_init = v_next, v_init
+
+    def tables(self, N, device):
+        out = []
+        for name, v in (("v_next", self.v_next), ("v_init", self.v_init)):
+            t = v.to(device) if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v)).to(device)
+            t = t.to(torch.float32).reshape(-1).contiguous()
+            if t.numel() != N:
+                raise ValueError(f"RowValue: {name} must have {N} entries (one per logged transition), got {t.numel()}")
+            out.append(t)
+        return out
 
 
 class CallablePolicy(ObsPolicy):

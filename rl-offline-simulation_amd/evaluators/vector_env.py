@@ -208,12 +208,121 @@ class VectorPSRS:
         cap = 0 if max_episode_steps is None else int(max_episode_steps)
         if cap < 0 or cap >= 1 << 31:
             raise ValueError(f"collect: max_episode_steps must be None or in [0, 2**31), got {max_episode_steps} (0 = no limit)")
-        from .obs_policy import MLPPolicy, ObsPolicy
-        if form == "auto":
-            form = "mlp" if isinstance(policy, MLPPolicy) else "rows" if isinstance(policy, ObsPolicy) else "tabular"
         env, t = self.env, self.table
         env._quiesce()
         env._orders_for_generic()
+        pol, keep, f32 = self._collect_policy(policy, form)
+        return self._collect_launch(pol, keep, f32, T, cap, record_obs, record_probs)
+
+    def _collect_launch(self, pol, keep, f32, T, cap, record_obs, record_probs, ppo=None):
+        """offsim_vector_collect (ppo None) or offsim_vector_collect_ppo (ppo = (offsim_collect_value, offsim_collect_ppo_out)) over T steps;
+        returns the Collected records."""
+        env, t = self.env, self.table
+        E, dev = self.num_envs, t.device
+        row = torch.empty((T, E), dtype=torch.int32, device=dev)
+        flags = torch.empty((T, E), dtype=torch.uint8, device=dev)
+        obs = torch.empty((T,) + tuple(self.obs.shape), dtype=self.obs.dtype, device=dev) if record_obs else None
+        probs = torch.empty((T, E, t.nA), dtype=torch.float32, device=dev) if record_probs else None
+        status = torch.full((E,), L.ST_OK, dtype=torch.int32, device=dev)
+        st = L.CollectState()
+        st.ep_t, st.obs_row, st.alive, st.obs = L.ptr(self._ep_t), L.ptr(self._obs_row), L.ptr(self.alive), L.ptr(self.obs)
+        st.obs_next, st.obs_init = L.ptr(self._next_obs), L.ptr(self._obs)
+        st.obs_bytes = self.obs.element_size() * int(np.prod(self.obs.shape[1:], dtype=np.int64))
+        out = L.CollectOut()
+        out.row, out.flags, out.obs, out.probs, out.status = L.ptr(row), L.ptr(flags), L.ptr(obs), L.ptr(probs), L.ptr(status)
+        if ppo is None:
+            L.check(L.load().offsim_vector_collect(C.byref(t.c), C.byref(env.state.c), C.byref(pol), L.PROB_F32 if f32 else L.PROB_F64,
+                                                   env.reject_mode, T, cap, C.byref(st), C.byref(out), L.stream_ptr()))
+        else:
+            L.check(L.load().offsim_vector_collect_ppo(C.byref(t.c), C.byref(env.state.c), C.byref(pol), C.byref(ppo[0]),
+                                                       L.PROB_F32 if f32 else L.PROB_F64, env.reject_mode, T, cap, C.byref(st), C.byref(out),
+                                                       C.byref(ppo[1]), L.stream_ptr()))
+        self._keep = keep
+        if self.strict and bool((status == L.ST_KEYERROR).any()):
+            k = int(torch.nonzero(status == L.ST_KEYERROR)[0])
+            raise KeyError(self.table.z_of(int(env.state.cur_slot[k])))
+        served = (flags & L.COLLECT_SERVED) != 0
+        rl = row.clamp(min=0).to(torch.int64)
+
+        def take(col):
+            if t.N == 0:
+                return torch.zeros((T, E) + tuple(col.shape[1:]), dtype=col.dtype, device=dev)
+            v = col[rl]
+            return torch.where(served.reshape(served.shape + (1,) * (v.dim() - 2)), v, torch.zeros((), dtype=v.dtype, device=dev))
+
+        return Collected(obs=obs, probs=probs, row=row, action=take(self._a), reward=take(self._r), next_obs=take(self._next_obs),
+                         terminated=(flags & L.COLLECT_TERMINATED) != 0, truncated=(flags & L.COLLECT_TRUNCATED) != 0,
+                         reset=(flags & L.COLLECT_RESET) != 0, alive=(flags & L.COLLECT_ALIVE) != 0, final_obs=self.obs.clone(), status=status)
+
+    def collect_ppo(self, actor, critic, num_steps, max_episode_steps=500, gamma=0.99, lam=0.97, normalize=True, bootstrap="reference",
+                    form="auto"):
+        """One PPO epoch buffer per environment from one call: collect(actor, num_steps, max_episode_steps) with the critic and logp of the
+        served action recorded in the same launch (offsim_vector_collect_ppo), then GAE-lambda advantages, rewards-to-go and spinup's
+        normalisation on the device (offsim_ppo_advantages).  E environments are E spinup MPI processes of local_steps_per_epoch =
+        num_steps: PPOAgentRevealed (offsim4rl/agents/ppo.py:30-158) driven by the CartPole example's loop
+        (examples/cartpole/psrs_from_expert_heuristic.py:59-80), with the networks fixed for the epoch.  The defaults are the agent's and
+        the example's.
+
+        actor: as collect's policy (form likewise).  critic: MLPValue (evaluated inside the kernel at the observation the actor is asked
+        at) or RowValue (per-row tables of any critic).  bootstrap: "reference" -- the agent's rules: a path that ends truncated, or ends
+        at the call's last step even if terminated, bootstraps with v(obs) of its last step, one that terminates earlier with 0 -- or
+        "spinup" -- terminated 0, truncated v(next_obs) of the truncating row.  Either way a path the call leaves open (the epoch cut,
+        or an environment that stopped) bootstraps with v at the observation it holds (final_value), and stays open for the next call.
+
+        Returns a PPOBatch of step-major [T, E] device tensors (flat() gives the loss inputs of ppo.py:_compute_loss_pi / _v).  The sampler
+        state, observations and episode counters carry over exactly as for collect: the trajectory is collect's."""
+        from .obs_policy import MLPValue, RowValue
+        from .ppo_buffer import PPOBatch, _advantages
+        T = int(num_steps)
+        if T < 0:
+            raise ValueError(f"collect_ppo: num_steps must be >= 0, got {num_steps}")
+        cap = 0 if max_episode_steps is None else int(max_episode_steps)
+        if cap < 0 or cap >= 1 << 31:
+            raise ValueError(f"collect_ppo: max_episode_steps must be None or in [0, 2**31), got {max_episode_steps} (0 = no limit)")
+        if bootstrap not in ("reference", "spinup"):
+            raise ValueError(f"collect_ppo: bootstrap must be 'reference' or 'spinup', got {bootstrap!r}")
+        env, t = self.env, self.table
+        E, dev = self.num_envs, t.device
+        env._quiesce()
+        env._orders_for_generic()
+        pol, keep, f32 = self._collect_policy(actor, form)
+        val = L.CollectValue()
+        if isinstance(critic, MLPValue):
+            x_next, x_init = self._x_tables()
+            if critic.dO != x_next.shape[1]:
+                raise ValueError(f"collect_ppo: the critic takes observations of width {critic.dO}, the log's have {x_next.shape[1]}")
+            x_start = self.obs.reshape(E, -1).to(x_next.dtype).contiguous()
+            ws, arr = critic._device_weights(dev)
+            val.form, val.n_layers, val.layers_host = L.VALUE_MLP, len(ws), C.cast(arr, C.POINTER(L.MLPLayer))
+            val.activation, val.slope = _mlp_act(critic), critic.slope
+            val.x_dtype, val.dO = (L.F32 if x_next.dtype == torch.float32 else L.F16), critic.dO
+            val.x_start, val.x_next, val.x_init = L.ptr(x_start), L.ptr(x_next), L.ptr(x_init)
+            keep += [x_start, x_next, x_init, ws]
+        elif isinstance(critic, RowValue):
+            vn, v0 = critic.tables(t.N, dev)
+            val.form, val.v_next, val.v_init = L.VALUE_ROWS, L.ptr(vn), L.ptr(v0)
+            keep += [vn, v0]
+        else:
+            raise TypeError(f"collect_ppo: the critic must be an MLPValue or a RowValue, got {type(critic).__name__}")
+        value = torch.zeros((T, E), dtype=torch.float32, device=dev)
+        logp = torch.zeros((T, E), dtype=torch.float32, device=dev)
+        final_value = torch.zeros((E,), dtype=torch.float32, device=dev)
+        v_trunc = torch.zeros((T, E), dtype=torch.float32, device=dev) if bootstrap == "spinup" else None
+        out = L.CollectPPOOut(value=L.ptr(value), logp=L.ptr(logp), final_value=L.ptr(final_value), v_trunc=L.ptr(v_trunc))
+        c = self._collect_launch(pol, keep, f32, T, cap, True, True, ppo=(val, out))
+        rew = c.reward.to(torch.float32)
+        flags = ((c.row >= 0).to(torch.uint8) * L.COLLECT_SERVED + c.terminated.to(torch.uint8) * L.COLLECT_TERMINATED
+                 + c.truncated.to(torch.uint8) * L.COLLECT_TRUNCATED).to(torch.uint8)
+        adv_raw, ret, adv, mean, std = _advantages(rew, value, flags, final_value, v_trunc, gamma, lam, normalize, bootstrap)
+        return PPOBatch(obs=c.obs, act=c.action, rew=rew, val=value, logp=logp, adv=adv, adv_raw=adv_raw, ret=ret, valid=c.row >= 0,
+                        final_value=final_value, v_trunc=v_trunc, adv_mean=mean, adv_std=std, collected=c)
+
+    def _collect_policy(self, policy, form):
+        """offsim_collect_policy for collect / collect_ppo: (struct, tensors to keep alive, whether p_new is compared in f32)."""
+        from .obs_policy import MLPPolicy, ObsPolicy
+        if form == "auto":
+            form = "mlp" if isinstance(policy, MLPPolicy) else "rows" if isinstance(policy, ObsPolicy) else "tabular"
+        t = self.table
         pol, keep = L.CollectPolicy(), []
         if form == "mlp":
             if not isinstance(policy, MLPPolicy):
@@ -254,36 +363,7 @@ class VectorPSRS:
             keep.append(ps)
         else:
             raise ValueError(f"collect: form must be 'auto', 'mlp', 'rows' or 'tabular', got {form!r}")
-        E, dev = self.num_envs, t.device
-        row = torch.empty((T, E), dtype=torch.int32, device=dev)
-        flags = torch.empty((T, E), dtype=torch.uint8, device=dev)
-        obs = torch.empty((T,) + tuple(self.obs.shape), dtype=self.obs.dtype, device=dev) if record_obs else None
-        probs = torch.empty((T, E, t.nA), dtype=torch.float32, device=dev) if record_probs else None
-        status = torch.full((E,), L.ST_OK, dtype=torch.int32, device=dev)
-        st = L.CollectState()
-        st.ep_t, st.obs_row, st.alive, st.obs = L.ptr(self._ep_t), L.ptr(self._obs_row), L.ptr(self.alive), L.ptr(self.obs)
-        st.obs_next, st.obs_init = L.ptr(self._next_obs), L.ptr(self._obs)
-        st.obs_bytes = self.obs.element_size() * int(np.prod(self.obs.shape[1:], dtype=np.int64))
-        out = L.CollectOut()
-        out.row, out.flags, out.obs, out.probs, out.status = L.ptr(row), L.ptr(flags), L.ptr(obs), L.ptr(probs), L.ptr(status)
-        L.check(L.load().offsim_vector_collect(C.byref(t.c), C.byref(env.state.c), C.byref(pol), L.PROB_F32 if f32 else L.PROB_F64,
-                                               env.reject_mode, T, cap, C.byref(st), C.byref(out), L.stream_ptr()))
-        self._keep = keep
-        if self.strict and bool((status == L.ST_KEYERROR).any()):
-            k = int(torch.nonzero(status == L.ST_KEYERROR)[0])
-            raise KeyError(self.table.z_of(int(env.state.cur_slot[k])))
-        served = (flags & L.COLLECT_SERVED) != 0
-        rl = row.clamp(min=0).to(torch.int64)
-
-        def take(col):
-            if t.N == 0:
-                return torch.zeros((T, E) + tuple(col.shape[1:]), dtype=col.dtype, device=dev)
-            v = col[rl]
-            return torch.where(served.reshape(served.shape + (1,) * (v.dim() - 2)), v, torch.zeros((), dtype=v.dtype, device=dev))
-
-        return Collected(obs=obs, probs=probs, row=row, action=take(self._a), reward=take(self._r), next_obs=take(self._next_obs),
-                         terminated=(flags & L.COLLECT_TERMINATED) != 0, truncated=(flags & L.COLLECT_TRUNCATED) != 0,
-                         reset=(flags & L.COLLECT_RESET) != 0, alive=(flags & L.COLLECT_ALIVE) != 0, final_obs=self.obs.clone(), status=status)
+        return pol, keep, f32
 
     def _x_tables(self):
         """The log's observations as the in-kernel network reads them: next_obs / obs [N, dO], f16 kept, anything else f32 (MLPPolicy.forward's

@@ -1,0 +1,122 @@
+"""The CartPole PPO example of the reference (examples/cartpole/psrs_from_expert_heuristic.py: PPOAgentRevealed trained inside PSRS on a
+logged dataset), vectorised: E environments play E spinup MPI processes of T local steps per epoch.  Per epoch:
+
+  1. VectorPSRS.collect_ppo(actor, critic, T): the actor and the critic inside the collect kernel, the PPO buffer on the device;
+  2. the update of PPOAgentRevealed.adapt (offsim4rl/agents/ppo.py:162-201) in torch: Adam on the clipped surrogate for up to train_pi_iters
+     iterations, stopping early once the approximate KL passes 1.5 * target_kl, then train_v_iters iterations on the value loss;
+  3. the new weights are read back into the MLPPolicy / MLPValue the kernel runs.
+
+Prints per epoch the mean return of the episodes that ended in it, the simulated steps per second of the collect, and the split of the
+epoch's time between collect and update.  Uses the synthetic CartPole log of synth.cartpole_log (a uniform-random logging policy).
+
+usage: python tools/ppo_in_psrs.py [--rows 1000000] [--envs 1024] [--steps 256] [--epochs 20] [--hid 64] [--l 2]"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+from torch.optim import Adam
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from rl_offline_simulation_amd import OfflineDataset, ProbDistribution, spaces, synth  # noqa: E402
+from rl_offline_simulation_amd.encoders import CartpoleBoxEncoder  # noqa: E402
+from rl_offline_simulation_amd.evaluators import MLPPolicy, MLPValue, VectorPSRS  # noqa: E402
+
+
+def net(sizes):
+    mods = []
+    for j in range(len(sizes) - 1):
+        mods += [torch.nn.Linear(sizes[j], sizes[j + 1]), torch.nn.Tanh() if j < len(sizes) - 2 else torch.nn.Identity()]
+    return torch.nn.Sequential(*mods)
+
+
+def episode_returns(b, open_ret):
+    """Returns of the episodes that ended in this epoch (per environment, the running return carries across epochs in open_ret)."""
+    rew, valid = b.rew, b.valid
+    end = valid & (b.collected.terminated | b.collected.truncated)
+    out = []
+    for t in range(rew.shape[0]):
+        open_ret += torch.where(valid[t], rew[t], torch.zeros_like(rew[t]))
+        if bool(end[t].any()):
+            out.append(open_ret[end[t]].clone())
+            open_ret[end[t]] = 0.0
+    return torch.cat(out) if out else torch.zeros(0, device=rew.device)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=1_000_000)
+    ap.add_argument("--envs", type=int, default=1024)
+    ap.add_argument("--steps", type=int, default=256, help="local steps per epoch (T)")
+    ap.add_argument("--epochs", type=int, default=20)
+    ap.add_argument("--hid", type=int, default=64)
+    ap.add_argument("--l", type=int, default=2)
+    ap.add_argument("--gamma", type=float, default=0.99)
+    ap.add_argument("--lam", type=float, default=0.97)
+    ap.add_argument("--clip-ratio", type=float, default=0.2)
+    ap.add_argument("--pi-lr", type=float, default=3e-4)
+    ap.add_argument("--vf-lr", type=float, default=1e-3)
+    ap.add_argument("--train-pi-iters", type=int, default=80)
+    ap.add_argument("--train-v-iters", type=int, default=80)
+    ap.add_argument("--target-kl", type=float, default=0.01)
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args()
+
+    e = synth.cartpole_log(a.rows, seed=a.seed)
+    ds = OfflineDataset(spaces.Box(-np.inf, np.inf, (4,), np.float32), spaces.Discrete(2), ProbDistribution.Discrete,
+                        **{k: e[k] for k in ("observations", "actions", "action_distributions", "rewards", "next_observations", "terminals", "steps", "episode_ids")})
+    env = VectorPSRS(ds, num_envs=a.envs, num_states=162, encoder=CartpoleBoxEncoder())
+    env.reset_sampler(np.arange(a.envs) + a.seed)
+    env.reset()
+    torch.manual_seed(a.seed)
+    pi_net = net([4] + [a.hid] * a.l + [2]).cuda()
+    v_net = net([4] + [a.hid] * a.l + [1]).cuda()
+    pi_opt, v_opt = Adam(pi_net.parameters(), lr=a.pi_lr), Adam(v_net.parameters(), lr=a.vf_lr)
+    open_ret = torch.zeros(a.envs, device="cuda")
+    for epoch in range(a.epochs):
+        actor, critic = MLPPolicy.from_torch(pi_net), MLPValue.from_torch(v_net)  # the current weights, as the kernel reads them
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        b = env.collect_ppo(actor, critic, a.steps, max_episode_steps=500, gamma=a.gamma, lam=a.lam)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        d = b.flat()
+        if d["adv"].numel() == 0:
+            print(f"epoch {epoch}: no transition served (the log ran dry)")
+            break
+        obs, act, adv, logp_old, ret = d["obs"].float(), d["act"].long(), d["adv"], d["logp"], d["ret"]
+
+        def loss_pi():
+            logits = pi_net(obs)
+            dist = torch.distributions.Categorical(logits=logits)
+            logp = dist.log_prob(act)
+            ratio = torch.exp(logp - logp_old)
+            clip_adv = torch.clamp(ratio, 1 - a.clip_ratio, 1 + a.clip_ratio) * adv
+            return -(torch.min(ratio * adv, clip_adv)).mean(), (logp_old - logp).mean().item()
+
+        stop = a.train_pi_iters
+        for i in range(a.train_pi_iters):
+            pi_opt.zero_grad()
+            loss, kl = loss_pi()
+            if kl > 1.5 * a.target_kl:
+                stop = i
+                break
+            loss.backward()
+            pi_opt.step()
+        for _ in range(a.train_v_iters):
+            v_opt.zero_grad()
+            ((v_net(obs)[:, 0] - ret) ** 2).mean().backward()
+            v_opt.step()
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        rets = episode_returns(b, open_ret)
+        served = int(b.valid.sum())
+        ep = f"{float(rets.mean()):8.2f} over {rets.numel():6d} episodes" if rets.numel() else "      -- (no episode ended)"
+        print(f"epoch {epoch:3d}: return {ep}  {served / (t1 - t0):.3e} simulated steps/s  collect {1e3 * (t1 - t0):7.2f} ms  "
+              f"update {1e3 * (t2 - t1):7.2f} ms (pi iters {stop})", flush=True)
+
+
+if __name__ == "__main__":
+    main()
