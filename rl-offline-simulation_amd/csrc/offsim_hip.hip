@@ -174,14 +174,14 @@ extern "C" int offsim_group_by_state(const int32_t *slot, int64_t N, int32_t n_s
     return OFFSIM_OK;
 }
 
-// dst[g] = src[order[g]] for rows of row_bytes bytes (1,2,4,8 or a multiple of 4)
+// dst[g] = src[order[g]] for rows of row_bytes bytes (any width: 1, 2, 4, 8 one element per row, else rows of 4-, 2- or 1-byte words)
 template <typename T>
 __global__ void k_gather_elem(const T *__restrict__ src, const int32_t *__restrict__ order, int64_t N, T *__restrict__ dst) {
     int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g < N) dst[g] = src[order[g]];
 }
-__global__ void k_gather_words(const uint32_t *__restrict__ src, const int32_t *__restrict__ order, int64_t N, int32_t words,
-                               uint32_t *__restrict__ dst) {
+template <typename W>
+__global__ void k_gather_words(const W *__restrict__ src, const int32_t *__restrict__ order, int64_t N, int32_t words, W *__restrict__ dst) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N * words) return;
     int64_t g = i / words;
@@ -197,13 +197,13 @@ extern "C" int offsim_gather_rows(const void *src, const int32_t *order, int64_t
     else if (row_bytes == 2) hipLaunchKernelGGL(k_gather_elem<uint16_t>, dim3(nb), dim3(256), 0, st, (const uint16_t *)src, order, N, (uint16_t *)dst);
     else if (row_bytes == 4) hipLaunchKernelGGL(k_gather_elem<uint32_t>, dim3(nb), dim3(256), 0, st, (const uint32_t *)src, order, N, (uint32_t *)dst);
     else if (row_bytes == 8) hipLaunchKernelGGL(k_gather_elem<uint64_t>, dim3(nb), dim3(256), 0, st, (const uint64_t *)src, order, N, (uint64_t *)dst);
-    else if (row_bytes % 4 == 0) {
-        int32_t words = row_bytes / 4;
+    else {  // (f16 p_log of an odd nA: rows of 2-byte words)
+        const int32_t wb = row_bytes % 4 == 0 ? 4 : row_bytes % 2 == 0 ? 2 : 1, words = row_bytes / wb;
         unsigned nbw = (unsigned)((N * words + 255) / 256);
-        hipLaunchKernelGGL(k_gather_words, dim3(nbw), dim3(256), 0, st, (const uint32_t *)src, order, N, words, (uint32_t *)dst);
-    } else if (row_bytes % 2 == 0) {
-        return fail(OFFSIM_EUNSUPPORTED, "gather_rows: row_bytes must be 1, 2 or a multiple of 4%s");
-    } else return fail(OFFSIM_EUNSUPPORTED, "gather_rows: row_bytes must be 1, 2 or a multiple of 4%s");
+        if (wb == 4) hipLaunchKernelGGL(k_gather_words<uint32_t>, dim3(nbw), dim3(256), 0, st, (const uint32_t *)src, order, N, words, (uint32_t *)dst);
+        else if (wb == 2) hipLaunchKernelGGL(k_gather_words<uint16_t>, dim3(nbw), dim3(256), 0, st, (const uint16_t *)src, order, N, words, (uint16_t *)dst);
+        else hipLaunchKernelGGL(k_gather_words<uint8_t>, dim3(nbw), dim3(256), 0, st, (const uint8_t *)src, order, N, words, (uint8_t *)dst);
+    }
     LAUNCH_CHECK();
     return OFFSIM_OK;
 }
