@@ -632,6 +632,82 @@ int offsim_ppo_advantages(const float *rew, const float *value, const uint8_t *f
                           int64_t T, int64_t E, double gamma, double lam, int32_t bootstrap, float *adv, float *ret, float *adv_norm,
                           double *stats, double *work, void *stream);
 
+/* ---- the PPO update (PPOLearner.update, ppo_grad) --------------------------------------------------------------------------------
+ * PPOAgentRevealed.adapt (offsim4rl/agents/ppo.py:162-223) over M records -- a PPO buffer as offsim_vector_collect_ppo and
+ * offsim_ppo_advantages leave it, [T*E] step-major, or any flat batch -- for one network at a time (kind):
+ *   OFFSIM_PPO_ACTOR   logp = log_softmax(logits(obs))[act], ratio = exp(logp - logp_old),
+ *                      loss = -mean(min(ratio * adv, clamp(ratio, 1 - c, 1 + c) * adv)),  kl = mean(logp_old - logp),
+ *                      entropy = mean(-sum_a p_a log p_a),  clipfrac = mean(ratio > 1 + c or ratio < 1 - c)     (_compute_loss_pi);
+ *   OFFSIM_PPO_CRITIC  loss = mean((v(obs) - ret)^2)  (_compute_loss_v); kl, entropy and clipfrac are 0.
+ * The means run over the records with valid != 0 (valid NULL: all M) of all environments together, and the gradient is that of this
+ * loss.  spinup averages per-process means and gradients over its E MPI processes instead: the same numbers whenever every environment
+ * holds T valid records.  A record whose act lies outside [0, nA) counts as invalid (for the actor).  Records with valid = 0 are never compacted
+ * away: they contribute nothing, and their obs / adv / logp / ret may hold anything finite or not.
+ * The network is offsim_policy_mlp's / offsim_value_mlp's (1-4 layers, dO <= 128, hidden <= 256, nA <= 16 or one output for the critic,
+ * the same activations; a leaky_relu slope below 0 is refused), its W and b together at most OFFSIM_COLLECT_MLP_MAX_FLOATS floats
+ * (they are staged into LDS as offsim_vector_collect stages them), otherwise OFFSIM_EUNSUPPORTED.  f32 arithmetic per record (fmaf
+ * chains in k order; not the bits of offsim_policy_mlp, as the reference's batched forward is not those of its per-step forward);
+ * per-workgroup partial gradients in f32, summed over a fixed assignment of records to at most OFFSIM_PPO_MAX_BLOCKS workgroups and
+ * then in block order in f64: no float atomics, two calls on the same input give the same bits.
+ *
+ * offsim_ppo_grad: one pass.  grad [P] f32: the gradient of the loss, flat in layer order, W [out,in] then b [out] of each layer (a
+ * layer without b has none), P the number of parameters; stats [5] f64: n (valid records), loss, kl, entropy, clipfrac.  Two launches.
+ *
+ * offsim_ppo_update: the loop for one network, 2 * iters + 1 launches enqueued at once, no host round trip:
+ *   for i in 0 .. iters-1:  pass i (loss, kl, ... and the gradient at the current weights);
+ *                           actor only: if kl > 1.5 * target_kl: stop -- StopIter = i, nothing is changed by this or any later launch;
+ *                           torch.optim.Adam's default step, in place on the layers' W / b:  t += 1,
+ *                             m = b1 m + (1 - b1) g,  v = b2 v + (1 - b2) g^2,  p -= (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+ *                             with b1 = 0.9, b2 = 0.999, eps = 1e-8 and no weight decay; each line is evaluated in f64 from the f32 state and g, and m and v
+ *                             are rounded to f32 before the last line reads them, as torch's f32 step reads its stored state.
+ *   opt: m, v [P] f32 (flat as grad) and t [1] i64 on the device, all zero before the first call and carried from call to call.
+ *   stats [6] f64: loss of pass 0, loss of the last pass computed, kl of the last pass, entropy of pass 0, clipfrac of the last pass,
+ *   StopIter (the pass that stopped, else iters - 1) -- what adapt() logs as LossPi / LossV, DeltaLoss* (last - first), KL, Entropy,
+ *   ClipFrac, StopIter.  trace [iters,2] f64: (loss, kl) of every pass computed, NaN for the passes after a stop.
+ *   A batch without a valid record changes nothing (StopIter = 0, zeros).
+ * The early stop is a flag in `work` that every launch reads first; no kernel waits for another.
+ * work: OFFSIM_PPO_UPDATE_WORK_DOUBLES(P) doubles of device scratch (offsim_ppo_update_work_doubles computes P from the layers; a
+ * negative return is an error code).  Argument validation happens before any HIP call; M = 0 or iters = 0 launches nothing. */
+#define OFFSIM_PPO_ACTOR 0
+#define OFFSIM_PPO_CRITIC 1
+#define OFFSIM_PPO_MAX_BLOCKS 256
+#define OFFSIM_PPO_UPDATE_WORK_DOUBLES(P) (OFFSIM_PPO_MAX_BLOCKS * 8 + 8 + OFFSIM_PPO_MAX_BLOCKS * (((P) + 1) / 2))
+typedef struct offsim_ppo_layer {      /* offsim_mlp_layer's layout with writable weights: offsim_ppo_update steps W and b in place */
+    float *W;                          /* [out, in] */
+    float *b;                          /* [out] or NULL */
+    int32_t in;
+    int32_t out;
+} offsim_ppo_layer;
+typedef struct offsim_ppo_net {
+    int32_t n_layers;                  /* layers_host[n_layers]: a HOST array, device pointers, as offsim_policy_mlp's */
+    int32_t activation;
+    const offsim_ppo_layer *layers_host;
+    float slope;
+    int32_t reserved;
+} offsim_ppo_net;
+typedef struct offsim_ppo_batch {
+    const void *obs;                   /* [M,dO] f32 or f16 (x_dtype)                               */
+    int32_t x_dtype;
+    int32_t dO;
+    const int32_t *act;                /* [M]   actor                                               */
+    const float *adv;                  /* [M]   actor                                               */
+    const float *logp;                 /* [M]   actor: logp_old                                     */
+    const float *ret;                  /* [M]   critic                                              */
+    const uint8_t *valid;              /* [M], or NULL: every record is valid                       */
+    int64_t M;
+} offsim_ppo_batch;
+typedef struct offsim_ppo_adam {
+    float *m;                          /* [P] in/out                                                */
+    float *v;                          /* [P] in/out                                                */
+    int64_t *t;                        /* [1] in/out: Adam's step count                             */
+    double lr;
+} offsim_ppo_adam;
+int64_t offsim_ppo_update_work_doubles(const offsim_ppo_net *net);
+int offsim_ppo_grad(const offsim_ppo_net *net, int32_t kind, const offsim_ppo_batch *batch, double clip_ratio, float *grad, double *stats,
+                    double *work, void *stream);
+int offsim_ppo_update(const offsim_ppo_net *net, int32_t kind, const offsim_ppo_batch *batch, double clip_ratio, double target_kl,
+                      int32_t iters, const offsim_ppo_adam *opt, double *stats, double *trace, double *work, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -110,6 +110,31 @@ class CollectPPOOut(C.Structure):
     _fields_ = [("value", _vp), ("logp", _vp), ("final_value", _vp), ("v_trunc", _vp)]
 
 
+PPO_ACTOR, PPO_CRITIC = 0, 1
+PPO_MAX_BLOCKS = 256
+
+
+def ppo_update_work_doubles(P):
+    """include/offsim.h: OFFSIM_PPO_UPDATE_WORK_DOUBLES(P)"""
+    return PPO_MAX_BLOCKS * 8 + 8 + PPO_MAX_BLOCKS * ((P + 1) // 2)
+
+
+class PPONet(C.Structure):
+    """struct offsim_ppo_net"""
+    _fields_ = [("n_layers", _i32), ("activation", _i32), ("layers_host", C.POINTER(MLPLayer)), ("slope", C.c_float), ("reserved", _i32)]
+
+
+class PPOBatchC(C.Structure):
+    """struct offsim_ppo_batch"""
+    _fields_ = [("obs", _vp), ("x_dtype", _i32), ("dO", _i32), ("act", _vp), ("adv", _vp), ("logp", _vp), ("ret", _vp), ("valid", _vp),
+                ("M", _i64)]
+
+
+class PPOAdam(C.Structure):
+    """struct offsim_ppo_adam"""
+    _fields_ = [("m", _vp), ("v", _vp), ("t", _vp), ("lr", C.c_double)]
+
+
 MAILBOX_MAX_ACTIONS = 24
 SERVER_CMD_STEP, SERVER_CMD_POP_ONE, SERVER_CMD_EXIT, SERVER_CMD_RESET = 1, 2, 3, 4
 SERVER_STARTING, SERVER_RUNNING, SERVER_EXITED = 1, 2, 3
@@ -178,6 +203,10 @@ SIGNATURES = {
     "offsim_vector_collect_ppo": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), C.POINTER(CollectPolicy), C.POINTER(CollectValue), _i32, _i32,
                                             _i64, _i32, C.POINTER(CollectState), C.POINTER(CollectOut), C.POINTER(CollectPPOOut), _vp]),
     "offsim_ppo_advantages": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, C.c_double, C.c_double, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "offsim_ppo_update_work_doubles": (_i64, [C.POINTER(PPONet)]),
+    "offsim_ppo_grad": (C.c_int, [C.POINTER(PPONet), _i32, C.POINTER(PPOBatchC), C.c_double, _vp, _vp, _vp, _vp]),
+    "offsim_ppo_update": (C.c_int, [C.POINTER(PPONet), _i32, C.POINTER(PPOBatchC), C.c_double, C.c_double, _i32, C.POINTER(PPOAdam), _vp, _vp,
+                                    _vp, _vp]),
 }
 
 _lib = None

@@ -6,3 +6,4 @@ from .psrs_exo import PSRS_Exo  # noqa: F401
 from .vector_env import VectorPSRS  # noqa: F401
 from .obs_policy import MLPPolicy, RowPolicy, CallablePolicy, MLPValue, RowValue  # noqa: F401
 from .ppo_buffer import PPOBatch, ppo_advantages  # noqa: F401
+from .ppo_learner import PPOLearner, PPOUpdateInfo, ppo_grad  # noqa: F401

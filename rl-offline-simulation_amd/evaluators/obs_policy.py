@@ -113,6 +113,42 @@ class _MLPNet:
             self._dev[key] = (ws, arr)
         return self._dev[key]
 
+    def refresh_host(self, device=None):
+        """Copy the device weights back into self.weights (a learner that owns the device copy -- PPOLearner -- updates it in place, and
+        the host copy is only brought up to date here, on demand).  device: which copy (default: the only one there is).  Synchronises."""
+        if not self._dev:
+            return self
+        if device is None and len(self._dev) > 1:
+            raise ValueError(f"{type(self).__name__}.refresh_host: copies on {sorted(self._dev)} exist, say which device to read")
+        key = str(device) if device is not None else next(iter(self._dev))
+        ws, _ = self._dev[key]
+        self.weights = [(W.detach().cpu().clone(), None if b is None else b.detach().cpu().clone()) for W, b in ws]
+        return self
+
+    def state_dict(self, device=None):
+        """The current weights as an nn.Sequential's state_dict of to_torch()'s layout: {'0.weight', '0.bias', '2.weight', ...} (CPU
+        tensors, refreshed from the device copy first)."""
+        self.refresh_host(device)
+        out = {}
+        for i, (W, b) in enumerate(self.weights):
+            out[f"{2 * i}.weight"] = W.clone()
+            if b is not None:
+                out[f"{2 * i}.bias"] = b.clone()
+        return out
+
+    def to_torch(self, device=None):
+        """An nn.Sequential of the current weights (Linear, activation, ..., Linear, Identity -- spinup's mlp() layout), on the CPU."""
+        acts = {"tanh": torch.nn.Tanh, "relu": torch.nn.ReLU, "identity": torch.nn.Identity,
+                "leaky_relu": lambda: torch.nn.LeakyReLU(self.slope)}
+        sd = self.state_dict(device)
+        mods = []
+        for i, (W, b) in enumerate(self.weights):
+            mods += [torch.nn.Linear(int(W.shape[1]), int(W.shape[0]), bias=b is not None),
+                     acts[self.activation]() if i < len(self.weights) - 1 else torch.nn.Identity()]
+        net = torch.nn.Sequential(*mods)
+        net.load_state_dict(sd)
+        return net
+
 
 class MLPPolicy(_MLPNet, ObsPolicy):
     """probs = softmax(L_n(act(... act(L_1(obs))))) -- spinup's MLPCategoricalActor (ppo.py:18-27) -- on the HIP forward.

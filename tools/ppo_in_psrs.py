@@ -2,14 +2,16 @@
 logged dataset), vectorised: E environments play E spinup MPI processes of T local steps per epoch.  Per epoch:
 
   1. VectorPSRS.collect_ppo(actor, critic, T): the actor and the critic inside the collect kernel, the PPO buffer on the device;
-  2. the update of PPOAgentRevealed.adapt (offsim4rl/agents/ppo.py:162-201) in torch: Adam on the clipped surrogate for up to train_pi_iters
-     iterations, stopping early once the approximate KL passes 1.5 * target_kl, then train_v_iters iterations on the value loss;
-  3. the new weights are read back into the MLPPolicy / MLPValue the kernel runs.
+  2. the update of PPOAgentRevealed.adapt (offsim4rl/agents/ppo.py:162-201): Adam on the clipped surrogate for up to train_pi_iters
+     iterations, stopping early once the approximate KL passes 1.5 * target_kl, then train_v_iters iterations on the value loss --
+     --update device (default): PPOLearner.update, the HIP kernels of offsim_ppo_update on the [T, E] records, in place on the weights
+     the collect kernel reads; --update torch: torch autograd over PPOBatch.flat(), the new weights read back into the MLPPolicy /
+     MLPValue with from_torch every epoch (the comparison route).
 
 Prints per epoch the mean return of the episodes that ended in it, the simulated steps per second of the collect, and the split of the
 epoch's time between collect and update.  Uses the synthetic CartPole log of synth.cartpole_log (a uniform-random logging policy).
 
-usage: python tools/ppo_in_psrs.py [--rows 1000000] [--envs 1024] [--steps 256] [--epochs 20] [--hid 64] [--l 2]"""
+usage: python tools/ppo_in_psrs.py [--rows 1000000] [--envs 1024] [--steps 256] [--epochs 20] [--hid 64] [--l 2] [--update device|torch]"""
 import argparse
 import os
 import sys
@@ -22,7 +24,7 @@ from torch.optim import Adam
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from rl_offline_simulation_amd import OfflineDataset, ProbDistribution, spaces, synth  # noqa: E402
 from rl_offline_simulation_amd.encoders import CartpoleBoxEncoder  # noqa: E402
-from rl_offline_simulation_amd.evaluators import MLPPolicy, MLPValue, VectorPSRS  # noqa: E402
+from rl_offline_simulation_amd.evaluators import MLPPolicy, MLPValue, PPOLearner, VectorPSRS  # noqa: E402
 
 
 def net(sizes):
@@ -62,6 +64,7 @@ def main():
     ap.add_argument("--train-v-iters", type=int, default=80)
     ap.add_argument("--target-kl", type=float, default=0.01)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--update", choices=("device", "torch"), default="device")
     a = ap.parse_args()
 
     e = synth.cartpole_log(a.rows, seed=a.seed)
@@ -73,49 +76,58 @@ def main():
     torch.manual_seed(a.seed)
     pi_net = net([4] + [a.hid] * a.l + [2]).cuda()
     v_net = net([4] + [a.hid] * a.l + [1]).cuda()
-    pi_opt, v_opt = Adam(pi_net.parameters(), lr=a.pi_lr), Adam(v_net.parameters(), lr=a.vf_lr)
     open_ret = torch.zeros(a.envs, device="cuda")
+    actor, critic = MLPPolicy.from_torch(pi_net), MLPValue.from_torch(v_net)
+    if a.update == "device":  # (pi_net / v_net only supply the initial weights; the learner steps the device copy the kernel reads)
+        learner = PPOLearner(actor, critic, pi_lr=a.pi_lr, vf_lr=a.vf_lr, clip_ratio=a.clip_ratio, train_pi_iters=a.train_pi_iters,
+                             train_v_iters=a.train_v_iters, target_kl=a.target_kl)
+    else:
+        pi_opt, v_opt = Adam(pi_net.parameters(), lr=a.pi_lr), Adam(v_net.parameters(), lr=a.vf_lr)
     for epoch in range(a.epochs):
-        actor, critic = MLPPolicy.from_torch(pi_net), MLPValue.from_torch(v_net)  # the current weights, as the kernel reads them
+        if a.update == "torch":
+            actor, critic = MLPPolicy.from_torch(pi_net), MLPValue.from_torch(v_net)  # the current weights, as the kernel reads them
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         b = env.collect_ppo(actor, critic, a.steps, max_episode_steps=500, gamma=a.gamma, lam=a.lam)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
-        d = b.flat()
-        if d["adv"].numel() == 0:
+        if not bool(b.valid.any()):
             print(f"epoch {epoch}: no transition served (the log ran dry)")
             break
-        obs, act, adv, logp_old, ret = d["obs"].float(), d["act"].long(), d["adv"], d["logp"], d["ret"]
+        if a.update == "device":
+            stop = int(learner.update(b).StopIter)  # (the int() is this script's only read-back; update itself enqueues and returns)
+        else:
+            d = b.flat()
+            obs, act, adv, logp_old, ret = d["obs"].float(), d["act"].long(), d["adv"], d["logp"], d["ret"]
 
-        def loss_pi():
-            logits = pi_net(obs)
-            dist = torch.distributions.Categorical(logits=logits)
-            logp = dist.log_prob(act)
-            ratio = torch.exp(logp - logp_old)
-            clip_adv = torch.clamp(ratio, 1 - a.clip_ratio, 1 + a.clip_ratio) * adv
-            return -(torch.min(ratio * adv, clip_adv)).mean(), (logp_old - logp).mean().item()
+            def loss_pi():
+                logits = pi_net(obs)
+                dist = torch.distributions.Categorical(logits=logits)
+                logp = dist.log_prob(act)
+                ratio = torch.exp(logp - logp_old)
+                clip_adv = torch.clamp(ratio, 1 - a.clip_ratio, 1 + a.clip_ratio) * adv
+                return -(torch.min(ratio * adv, clip_adv)).mean(), (logp_old - logp).mean().item()
 
-        stop = a.train_pi_iters
-        for i in range(a.train_pi_iters):
-            pi_opt.zero_grad()
-            loss, kl = loss_pi()
-            if kl > 1.5 * a.target_kl:
-                stop = i
-                break
-            loss.backward()
-            pi_opt.step()
-        for _ in range(a.train_v_iters):
-            v_opt.zero_grad()
-            ((v_net(obs)[:, 0] - ret) ** 2).mean().backward()
-            v_opt.step()
+            stop = a.train_pi_iters - 1  # (StopIter as adapt() logs it: the pass that stopped, else the last one)
+            for i in range(a.train_pi_iters):
+                pi_opt.zero_grad()
+                loss, kl = loss_pi()
+                if kl > 1.5 * a.target_kl:
+                    stop = i
+                    break
+                loss.backward()
+                pi_opt.step()
+            for _ in range(a.train_v_iters):
+                v_opt.zero_grad()
+                ((v_net(obs)[:, 0] - ret) ** 2).mean().backward()
+                v_opt.step()
         torch.cuda.synchronize()
         t2 = time.perf_counter()
         rets = episode_returns(b, open_ret)
         served = int(b.valid.sum())
         ep = f"{float(rets.mean()):8.2f} over {rets.numel():6d} episodes" if rets.numel() else "      -- (no episode ended)"
         print(f"epoch {epoch:3d}: return {ep}  {served / (t1 - t0):.3e} simulated steps/s  collect {1e3 * (t1 - t0):7.2f} ms  "
-              f"update {1e3 * (t2 - t1):7.2f} ms (pi iters {stop})", flush=True)
+              f"update {1e3 * (t2 - t1):7.2f} ms (StopIter {stop})", flush=True)
 
 
 if __name__ == "__main__":
