@@ -39,15 +39,16 @@ def forward(net, obs, activation="tanh", slope=0.01):
     return a, ins, pre
 
 
-def backward(net, ins, pre, d_out, activation="tanh", slope=0.01):
-    """flat gradient from d loss / d outputs [M, out_last]"""
+def backward(net, ins, pre, d_out, activation="tanh", slope=0.01, dact=None):
+    """flat gradient from d loss / d outputs [M, out_last]; dact: another derivative in _dact's place (tests of a comparator's sensitivity)"""
+    dact = dact or _dact
     grads = [None] * len(net)
     d = d_out
     for i in range(len(net) - 1, -1, -1):
         W, b = net[i]
         grads[i] = (d.T @ ins[i], None if b is None else d.sum(0))
         if i > 0:
-            d = (d @ np.asarray(W, np.float64)) * _dact(pre[i - 1], ins[i], activation, slope)
+            d = (d @ np.asarray(W, np.float64)) * dact(pre[i - 1], ins[i], activation, slope)
     return flatten(grads)
 
 
@@ -69,7 +70,7 @@ def unflatten(flat, like):
     return out
 
 
-def loss_pi(net, obs, act, adv, logp_old, clip, activation="tanh", slope=0.01, valid=None):
+def loss_pi(net, obs, act, adv, logp_old, clip, activation="tanh", slope=0.01, valid=None, dact=None):
     """(loss, kl, entropy, clipfrac, flat gradient, n) of _compute_loss_pi over the valid entries"""
     obs, act, adv, logp_old = np.asarray(obs, np.float64), np.asarray(act).astype(np.int64), np.asarray(adv, np.float64), np.asarray(logp_old, np.float64)
     if valid is not None:
@@ -94,11 +95,11 @@ def loss_pi(net, obs, act, adv, logp_old, clip, activation="tanh", slope=0.01, v
     dlogp = -dsurr * ratio / n
     onehot = np.zeros_like(z)
     onehot[np.arange(n), act] = 1.0
-    g = backward(net, ins, pre, dlogp[:, None] * (onehot - p), activation, slope)
+    g = backward(net, ins, pre, dlogp[:, None] * (onehot - p), activation, slope, dact)
     return loss, kl, ent, cf, g, n
 
 
-def loss_v(net, obs, ret, activation="tanh", slope=0.01, valid=None):
+def loss_v(net, obs, ret, activation="tanh", slope=0.01, valid=None, dact=None):
     """(loss, flat gradient, n) of _compute_loss_v over the valid entries"""
     obs, ret = np.asarray(obs, np.float64), np.asarray(ret, np.float64)
     if valid is not None:
@@ -107,7 +108,7 @@ def loss_v(net, obs, ret, activation="tanh", slope=0.01, valid=None):
     n = len(ret)
     z, ins, pre = forward(net, obs, activation, slope)
     e = z[:, 0] - ret
-    return (e * e).mean(), backward(net, ins, pre, (2.0 * e / n)[:, None], activation, slope), n
+    return (e * e).mean(), backward(net, ins, pre, (2.0 * e / n)[:, None], activation, slope, dact), n
 
 
 class Adam:

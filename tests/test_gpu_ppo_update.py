@@ -205,7 +205,7 @@ def _torch_grad(net, kind, f, clip, dtype, device):
         loss = ((m(t["obs"])[:, 0] - t["ret"]) ** 2).mean()
         kl = torch.zeros((), dtype=dtype)
     loss.backward()
-    g = torch.cat([p.grad.reshape(-1) for x in m if isinstance(x, torch.nn.Linear) for p in (x.weight, x.bias)])
+    g = torch.cat([p.grad.reshape(-1) for x in m if isinstance(x, torch.nn.Linear) for p in (x.weight, x.bias) if p is not None])
     return g.double().cpu().numpy(), float(loss), float(kl)
 
 
