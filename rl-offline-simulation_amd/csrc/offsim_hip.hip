@@ -265,6 +265,28 @@ static hipError_t allow_big_lds_fn(const void *fn, int bytes) {
 }
 #define allow_big_lds(kernel, bytes) allow_big_lds_fn((const void *)(kernel), (bytes))
 
+// The launches of the keyed chains of the longest size class, cut at shuf_cuts[] (shuffle_wave.hpp): launch K runs the steps
+// shuf_cuts[K-1]-1 .. shuf_cuts[K] -- the first from n-1 with the whole segment in LDS (lds_top bytes, the deep j ring), the others with
+// their TOP low positions only (2 * TOP bytes behind the fixed part: two chains per CU at 32768, three at 16384, seven at 4096), the last
+// down to step 1.  Only these instances of the kernel exist.
+template <int K>
+static int shuf_launch_cuts(int n_launches, size_t lds_top, unsigned n_blocks, hipStream_t st, const offsim_table *t, const uint64_t *seeds, int32_t n_perm,
+                            uint32_t *perm_out, uint32_t *init_perm_out, uint32_t lo, uint32_t hi, const uint32_t *dig32, uint32_t *dig_out,
+                            uint16_t *loc_out, uint32_t a_xchg) {
+    constexpr uint32_t TOP = K == 0 ? 0u : shuf_cuts[K > 0 ? K - 1 : 0], STOP = K == shuf_n_cuts ? 1u : shuf_cuts[K < shuf_n_cuts ? K : 0];
+    constexpr uint32_t SQ = K == 0 ? SHUF_SQ_BIG : SHUF_SQ_SMALL;
+    if (K >= n_launches) return OFFSIM_OK;
+    const size_t ldsb = K == 0 ? lds_top : shuf_fixed_lds_bytes(SQ) + (size_t)TOP * 2 + 16;
+    HIP_TRY(allow_big_lds((k_shuffle_wave<true, SQ, TOP, STOP>), 160 * 1024));
+    hipLaunchKernelGGL((k_shuffle_wave<true, SQ, TOP, STOP>), dim3(n_blocks), dim3(256), ldsb, st, t->seg_off, t->n_slots, t->N, t->N0, seeds, n_perm,
+                       perm_out, init_perm_out, lo, hi, dig32, dig_out, loc_out, a_xchg);
+    LAUNCH_CHECK();
+    if constexpr (K < shuf_n_cuts)
+        return shuf_launch_cuts<K + 1>(n_launches, lds_top, n_blocks, st, t, seeds, n_perm, perm_out, init_perm_out, lo, hi, dig32, dig_out, loc_out, a_xchg);
+    else
+        return OFFSIM_OK;
+}
+
 // wave-parallel exact Fisher-Yates (shuffle_wave.hpp), one workgroup per chain.  dig_out == NULL: orders as permutations of grouped
 // rows; otherwise the keyed form (digest stream + 16-bit local rows per queue position) for the state queues
 static int lds_order_ok_on(void *stream);  // the LDS lane-order guard as the launch paths ask it (defined beside offsim_lds_order_ok)
@@ -301,27 +323,16 @@ static int launch_shuffle(const offsim_table *t, const uint64_t *seeds, int32_t 
         const uint32_t sq = k == 0 ? SHUF_SQ_BIG : SHUF_SQ_SMALL;
         const size_t lds16 = shuf_fixed_lds_bytes(sq) + (((size_t)need * 2 + 15) & ~(size_t)15) + 16;
         if (k == 0 && dig_out) {
-            // keyed chains of the longest class in three launches (shuffle_wave.hpp, <TOP, STOP>): the steps above 16384 with the
-            // whole segment in LDS, then 16383 .. 4096 with 32 KB per chain (three chains per CU), then the conflict-ridden low end
-            // with 8 KB (seven per CU); the init queue (never keyed) keeps the one-launch form
-#define SHUF_LAUNCH(SQ, TOP, STOP, LDSB)                                                                                              \
-    do {                                                                                                                              \
-        HIP_TRY(allow_big_lds((k_shuffle_wave<true, SQ, TOP, STOP>), 160 * 1024));                                                     \
-        hipLaunchKernelGGL((k_shuffle_wave<true, SQ, TOP, STOP>), dim3((unsigned)n_blocks), dim3(256), (LDSB), st, t->seg_off, t->n_slots, \
-                           t->N, t->N0, seeds, n_perm, perm_out, init_perm_out, lo, hi, dig32, dig_out, loc_out, a_xchg);             \
-        LAUNCH_CHECK();                                                                                                               \
-    } while (0)
-#define SHUF_TAILB(TOP) (shuf_fixed_lds_bytes(SHUF_SQ_SMALL) + (size_t)(TOP) * 2 + 16)
-#ifdef SHUF_PROF  // (tools/prof_shuffle.py: the stamps of the LAST launch survive in the streams -- OFFSIM_SHUFFLE_PROF_LAUNCHES = 1 / 2 stops after the first / second)
-            const int prof_launches = getenv("OFFSIM_SHUFFLE_PROF_LAUNCHES") ? atoi(getenv("OFFSIM_SHUFFLE_PROF_LAUNCHES")) : 3;
+            // keyed chains of the longest class in one launch per cut and one more (shuffle_wave.hpp, <TOP, STOP>; shuf_launch_cuts
+            // above); the init queue (never keyed) keeps the one-launch form
+#ifdef SHUF_PROF  // (tools/prof_shuffle.py: the stamps of the LAST launch survive in the streams -- OFFSIM_SHUFFLE_PROF_LAUNCHES = k stops after the k-th)
+            const int prof_launches = getenv("OFFSIM_SHUFFLE_PROF_LAUNCHES") ? atoi(getenv("OFFSIM_SHUFFLE_PROF_LAUNCHES")) : shuf_n_cuts + 1;
 #else
-            const int prof_launches = 3;
+            const int prof_launches = shuf_n_cuts + 1;
 #endif
-            SHUF_LAUNCH(SHUF_SQ_BIG, 0, SHUF_CUT_HI, lds16);
-            if (prof_launches >= 2) SHUF_LAUNCH(SHUF_SQ_SMALL, SHUF_CUT_HI, SHUF_CUT_LO, SHUF_TAILB(SHUF_CUT_HI));
-            if (prof_launches >= 3) SHUF_LAUNCH(SHUF_SQ_SMALL, SHUF_CUT_LO, 1, SHUF_TAILB(SHUF_CUT_LO));
-#undef SHUF_LAUNCH
-#undef SHUF_TAILB
+            const int rc = shuf_launch_cuts<0>(prof_launches, lds16, (unsigned)n_blocks, st, t, seeds, n_perm, perm_out, init_perm_out, lo, hi, dig32, dig_out,
+                                               loc_out, a_xchg);
+            if (rc != OFFSIM_OK) return rc;
             if (init_in)  // (an init queue of this size class: its chains are not keyed)
                 hipLaunchKernelGGL((k_shuffle_wave<true, SHUF_SQ_BIG>), dim3((unsigned)n_perm), dim3(256), lds16, st, t->seg_off, t->n_slots, t->N,
                                    t->N0, seeds, n_perm, perm_out, init_perm_out, lo, hi, dig32, nullptr, nullptr, a_xchg);

@@ -35,16 +35,26 @@ namespace offsim {
 // partners in the j ring (power of two, >= 3 * 128), a template parameter (as a kernel argument it cost 3.5 %): 4096 for the class of the longest LDS-resident
 // chains (deep enough that C rarely waits behind a slow group of A; there one chain fills a CU anyway), 1024 elsewhere (the
 // short chains of a skewed table share a CU, and their occupancy is what the fixed part of the LDS costs)
-// cuts of the keyed chains of the longest size class (see k_shuffle_wave).  Measured per pass of the headline job
-// (tools/time_reset.py ... keyed): uncut 0.645 s; one cut at 4096 / 8192 / 16384 / 32768: 0.575 / 0.548 / 0.540 / 0.568 s;
-// two cuts at 16384 + 4096: 0.528 s, 16384 + 2048: 0.529 s; three cuts at 16384 + 4096 + 1024: 0.535 s, 32768 + 8192 + 2048:
-// 0.536 s, 16384 + 8192 + 2048: 0.538 s, 32768 + 16384 + 4096: 0.552 s
-#ifndef SHUF_CUT_HI
-#define SHUF_CUT_HI 16384u
+// cuts of the keyed chains of the longest size class (see k_shuffle_wave): a short descending list of powers of two, the first at most
+// 32768 (every chain of the class is longer), launch k runs the steps cut[k-1]-1 .. cut[k] (the first from n-1, the last down to 1).
+// Only the instances of this list are compiled (offsim_hip.hip, shuf_launch_cuts).  Measured per pass of the headline job
+// (tools/time_reset.py ... keyed, one box, two rounds; profiles/shuffle_handover/sweep_cut_lists.txt), with the hand-over as
+// shuf_fill_from_stream makes it: 16384 + 4096: 0.380 s (with the 2-byte fill it had until then: 0.405 s -- the earlier sweeps priced
+// that fill, 64 us per chain at 32768, not the cuts); 16384 + 4096 + 1024: 0.387 s; 32768 + 16384 + 4096: 0.3635 s;
+// 32768 + 16384 + 8192 + 2048: 0.3655 s; 32768 + 16384 + 4096 + 1024: 0.3695 s; 32768 + 8192 + 2048: 0.362 s (kept).  The steps
+// 32767 .. 16384 take 128 k clocks per chain at two chains per CU against 92 k at one (top launch 322 -> 220 ms, the launch from 32768
+// 77 ms); a launch from 1024 costs more than it saves (its chains wait 27 k clocks for the first draws, a quarter of their time).
+#ifndef SHUF_CUT_LIST
+#define SHUF_CUT_LIST 32768u, 8192u, 2048u
 #endif
-#ifndef SHUF_CUT_LO
-#define SHUF_CUT_LO 4096u
-#endif
+constexpr uint32_t shuf_cuts[] = {SHUF_CUT_LIST};
+constexpr int shuf_n_cuts = (int)(sizeof(shuf_cuts) / sizeof(shuf_cuts[0]));
+constexpr bool shuf_cuts_ok() {
+    for (int k = 0; k < shuf_n_cuts; k++)
+        if ((shuf_cuts[k] & (shuf_cuts[k] - 1u)) != 0u || shuf_cuts[k] < 1024u || (k == 0 ? shuf_cuts[k] > 32768u : shuf_cuts[k] >= shuf_cuts[k - 1])) return false;
+    return true;
+}
+static_assert(shuf_cuts_ok(), "SHUF_CUT_LIST: descending powers of two, 32768 at most, 1024 at least");
 #define SHUF_SQ_BIG 4096u
 #define SHUF_SQ_SMALL 1024u
 #define SHUF_CAP16 65536u
@@ -85,6 +95,62 @@ __device__ __forceinline__ int sh_rank(uint64_t m) {  // set bits of m in front 
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
+// The hand-over of a cut chain: the TOP low positions of the loc stream (16-bit rows, as the launch before left them) into the segment's
+// place in LDS.  The stream of a chain starts wherever its rollout and its state put it -- 2-byte aligned, any phase -- while the segment
+// in LDS is 16-byte aligned (the applier exchanges whole dwords of it).  So the source is read as dwords from the address rounded DOWN to 4
+// bytes, 16 bytes per lane and load, ALL loads of a thread issued before the first is waited for (one 2-byte load per entry, each waited
+// for before the next, was 64 dependent HBM round trips per chain at TOP = 16384), and where the stream starts in the upper half of a dword
+// every 16 bytes take a fifth dword (the first of the next 16) and go through v_alignbyte.  Reads stay inside the stream: the dword in
+// front of an odd start belongs to the entry before this chain's (the buffer itself is dword-aligned), the fifth dword of the last 16 bytes
+// ends with entry TOP, and every cut chain has more than TOP rows.
+template <uint32_t TOP>
+__device__ __forceinline__ void shuf_fill_from_stream(lds_vu16 *x16, const uint16_t *lc) {
+    typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    constexpr uint32_t VEC = TOP / 8u, J = VEC ? (VEC + 255u) / 256u : 1u;  // 16-byte pieces of the segment, per thread (TOP = 0: never called)
+    static_assert(TOP % 8u == 0u, "the fill moves 16 bytes at a time");
+    const bool odd = (((uintptr_t)lc >> 1) & 1u) != 0u;
+    const uint32_t *src = (const uint32_t *)(lc - (odd ? 1 : 0));
+    __attribute__((address_space(3))) u32x4 *dst = (__attribute__((address_space(3))) u32x4 *)x16;
+    u32x4 w[J];
+    if (odd) {
+        uint32_t e[J];
+#pragma unroll
+        for (uint32_t j = 0; j < J; j++) {
+            const uint32_t q = threadIdx.x + 256u * j;
+            if (VEC % 256u == 0u || q < VEC) {
+                w[j] = *(const u32x4_a4 *)(src + 4u * q);
+                e[j] = src[4u * q + 4u];
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);  // (every load in front of the first use: no wait between the loads, whatever the register count)
+#pragma unroll
+        for (uint32_t j = 0; j < J; j++) {
+            const uint32_t q = threadIdx.x + 256u * j;
+            if (VEC % 256u == 0u || q < VEC) {
+                u32x4 o;
+                o.x = __builtin_amdgcn_alignbyte(w[j].y, w[j].x, 2u);
+                o.y = __builtin_amdgcn_alignbyte(w[j].z, w[j].y, 2u);
+                o.z = __builtin_amdgcn_alignbyte(w[j].w, w[j].z, 2u);
+                o.w = __builtin_amdgcn_alignbyte(e[j], w[j].w, 2u);
+                dst[q] = o;
+            }
+        }
+    } else {
+#pragma unroll
+        for (uint32_t j = 0; j < J; j++) {
+            const uint32_t q = threadIdx.x + 256u * j;
+            if (VEC % 256u == 0u || q < VEC) w[j] = *(const u32x4_a4 *)(src + 4u * q);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (uint32_t j = 0; j < J; j++) {
+            const uint32_t q = threadIdx.x + 256u * j;
+            if (VEC % 256u == 0u || q < VEC) dst[q] = w[j];
+        }
+    }
+}
+
 // LDS layout: [ctrl 16 w][draw ring RG w][j ring SQ w + 64 w trash][64 w tag winners][segment]
 constexpr uint32_t shuf_fixed_lds_bytes(uint32_t sq) { return 4u * (16u + SHUF_RG + sq + 64u + 64u); }
 
@@ -99,8 +165,9 @@ constexpr uint32_t shuf_fixed_lds_bytes(uint32_t sq) { return 4u * (16u + SHUF_R
 // identity): it loads the TOP low positions as the previous launch left them (16-bit local rows, from the loc stream) and
 // the number of 32-bit draws used so far (left in the chain's first digest word), continues the random stream from that
 // count, and writes out the positions below TOP -- final above STOP, as they stand below.  Cuts are powers of two: mask
-// boundaries, where C's batches end exactly anyway.  With cuts at 16384 and 4096 the launches hold one, three and seven
-// chains per CU; the chains of a CU hide each other's latencies.
+// boundaries, where C's batches end exactly anyway.  A launch from 32768 / 16384 / 8192 / 4096 / 2048 holds two / three / five / seven / eight
+// chains per CU (the first launch one); the chains of a CU hide each other's latencies.  A chain of cut + 1 rows runs one step in
+// its first launch: C's first batch ends at the mask boundary, A's only group is the partial one.
 template <bool LDS16, uint32_t SHUF_SQ, uint32_t TOP = 0, uint32_t STOP = 1>
 __global__ void __launch_bounds__(256)
     k_shuffle_wave(const uint32_t *__restrict__ seg_off, int32_t n_slots, int64_t N, int64_t N0, const uint64_t *__restrict__ seeds,
@@ -112,6 +179,9 @@ __global__ void __launch_bounds__(256)
     lds_vu32 *jq = ring + SHUF_RG;  // partners in step order; [SQ .. SQ+63] takes the stores of rejected lanes
     lds_vu32 *win = jq + SHUF_SQ + 64u;  // A: "lane l won a tag" (all zero between uses)
     lds_vu16 *x16 = (lds_vu16 *)(win + 64u);
+#ifdef SHUF_PROF
+    const uint64_t pf_entry = __builtin_amdgcn_s_memtime();
+#endif
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
 
     // chain of this workgroup: the init queue first (usually the longest chain), then state by state
@@ -193,7 +263,7 @@ __global__ void __launch_bounds__(256)
     uint32_t c_start = 0;  // 32-bit draws the launches before this one used
     if (FROM_STREAM) {  // the low positions as the previous launch left them, and its draw count
         c_start = dg[0];
-        for (uint32_t k = threadIdx.x; k < TOP; k += 256u) x16[k] = lc[k];
+        shuf_fill_from_stream<TOP>(x16, lc);
     } else if (LDS16) {  // identity, two entries per lane and store
         __attribute__((address_space(3))) uint32_t *xw = (__attribute__((address_space(3))) uint32_t *)x16;
         for (uint32_t k = threadIdx.x; 2u * k < n; k += 256u) xw[k] = ((2u * k + 1u) << 16) | (2u * k);
@@ -207,9 +277,12 @@ __global__ void __launch_bounds__(256)
     // read issued after a counter was seen comes after the data.  So the counters are plain volatile words (the
     // volatile qualifier keeps the compiler from reordering them) and no s_waitcnt is spent on publishing.
     // -DSHUF_PROF (tools/prof_shuffle.py): per role, clocks in its loop / waiting for its neighbour / in the named extra
-    // activity; written over the first 13 digests of the chain's stream, so the results of such a build are not usable
+    // activity; and the hand-over of a cut chain, which the roles' clocks leave out: kernel entry to the end of the fill (word 13), the
+    // classifier's SH_DONE to the workgroup's last store (word 14: the applier's last groups, the barrier, the chunks the G wavefronts
+    // did not get to), and G0's way to its first published block (word 15: seeding and the jump to the stream's position, which the
+    // classifier waits for).  Written over the first 16 digests of the chain's stream, so the results of such a build are not usable
 #ifdef SHUF_PROF
-    uint64_t pf_wait = 0, pf_w0 = 0, pf_extra = 0;
+    uint64_t pf_wait = 0, pf_w0 = 0, pf_extra = 0, pf_g_first = 0;
     const uint64_t pf_begin = __builtin_amdgcn_s_memtime();
 #define SPW0() pf_w0 = __builtin_amdgcn_s_memtime()
 #define SPW1() pf_wait += __builtin_amdgcn_s_memtime() - pf_w0
@@ -270,6 +343,9 @@ __global__ void __launch_bounds__(256)
                 blk += 2u;
                 done_blocks++;
                 sh_st(ctrl + (g ? SH_GEN1 : SH_GEN0), done_blocks);
+#ifdef SHUF_PROF
+                if (done_blocks == 1u) pf_g_first = __builtin_amdgcn_s_memtime() - pf_begin;
+#endif
             }
         } else if (wave == 1) {
             // ---------------- C: the j sequence, 2 x 64 draws per iteration.  The second batch starts from i2 = i - accepts
@@ -766,7 +842,12 @@ __global__ void __launch_bounds__(256)
         dg[3 * wave + 0] = (uint32_t)((pf_end - pf_begin) >> 6);
         dg[3 * wave + 1] = (uint32_t)(pf_wait >> 6);
         dg[3 * wave + 2] = (uint32_t)(pf_extra >> 6);
-        if (wave == 0) dg[12] = (uint32_t)((__builtin_amdgcn_s_memtime() - pf_begin) >> 6);
+        if (wave == 0) {
+            dg[12] = (uint32_t)((__builtin_amdgcn_s_memtime() - pf_begin) >> 6);
+            dg[13] = (uint32_t)((pf_begin - pf_entry) >> 6);
+            dg[15] = (uint32_t)(pf_g_first >> 6);
+        }
+        if (wave == 1) dg[14] = (uint32_t)((__builtin_amdgcn_s_memtime() - pf_end) >> 6);  // (C's loop ends with the store of SH_DONE)
     }
 #endif
 }
