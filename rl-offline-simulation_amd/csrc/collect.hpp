@@ -14,9 +14,12 @@
 // The environment's state lives in registers for the launch and is written back once at the end.
 //
 // VF (offsim_vector_collect_ppo) adds the critic of the PPO buffer, in either form whatever the actor's: at every live step v(obs) at the
-// observation the actor is asked at (VF = OFFSIM_VALUE_MLP: the same in-wave forward, its weights staged after the actor's; VF =
-// OFFSIM_VALUE_ROWS: v_next[row] / v_init[row]), logp of the served action, v(next_obs) of a step that truncates without terminating, and
-// after the last step v(obs) of the observation the environment holds.  VF = COLLECT_VF_NONE is offsim_vector_collect: none of it.
+// observation the actor is asked at (VF = OFFSIM_VALUE_MLP: a second network in LDS behind the actor's; VF = OFFSIM_VALUE_ROWS:
+// v_next[row] / v_init[row]), logp of the served action, v(next_obs) of a step that truncates without terminating, and after the last
+// step v(obs) of the observation the environment holds.  VF = COLLECT_VF_NONE is offsim_vector_collect: none of it.
+//
+// An in-LDS network, the actor's or the critic's, is ONE descriptor (CollectMlp, filled by collect_mlp from policy_mlp.hpp's PmlpNet),
+// staged by pmlp_stage and evaluated by collect_forward; where an environment's observation row is, is collect_obs_row.
 #pragma once
 
 #include <type_traits>
@@ -28,6 +31,8 @@
 #define COLLECT_WIDTH 16
 #define COLLECT_VF_NONE -1  // VF of offsim_vector_collect: no critic
 
+// a network in LDS and the observations it reads.  The actor's w_max is the stride of the wave's activation rows: the widest activation
+// of the actor and, where there is one, the critic.
 struct CollectMlp {
     const float *W[PMLP_MAX_LAYERS];
     const float *b[PMLP_MAX_LAYERS];
@@ -38,17 +43,11 @@ struct CollectMlp {
     const void *x_start, *x_next, *x_init;
 };
 
-// the critic of offsim_vector_collect_ppo (offsim_collect_value): MLP layers as CollectMlp's (woff / boff from the LDS byte offset off_w),
-// or ROWS tables; and the PPO records (offsim_collect_ppo_out)
+// the critic of offsim_vector_collect_ppo (offsim_collect_value): a network in LDS from the byte offset off_w, or ROWS tables; and the PPO
+// records (offsim_collect_ppo_out)
 struct CollectValue {
-    const float *W[PMLP_MAX_LAYERS];
-    const float *b[PMLP_MAX_LAYERS];
-    int in[PMLP_MAX_LAYERS], out[PMLP_MAX_LAYERS];
-    int woff[PMLP_MAX_LAYERS], boff[PMLP_MAX_LAYERS];
-    int n, act, dO;
-    float slope;
+    CollectMlp mlp;
     uint32_t off_w;
-    const void *x_start, *x_next, *x_init;
     const float *v_next, *v_init;
     offsim_collect_ppo_out rec;
 };
@@ -88,34 +87,45 @@ __device__ __forceinline__ void wave_copy_row(unsigned char *d, const unsigned c
 // obs_row encoding (offsim_eval_mc_rows_policy's out_obs_row): i >= 0 next_obs of caller row i, -2 - i obs of caller row i
 __device__ __forceinline__ bool collect_row_ok(int32_t v, int64_t N) { return (v >= 0 && v < N) || (v <= -2 && -2 - (int64_t)v < N); }
 
+// Where an environment's observation row is, in rows of w elements T: its own row `own` of the start rows until the observation has
+// moved, then obs_row encoding xrow into next / init.
+template <typename T>
+__device__ __forceinline__ const T *collect_obs_row(const T *own, const void *next, const void *init, int64_t w, bool moved, int32_t xrow) {
+    return !moved ? own : xrow >= 0 ? (const T *)next + (int64_t)xrow * w : (const T *)init + (-2 - (int64_t)xrow) * w;
+}
+
+// One wave's forward of the network M, its W^T / b at w (pmlp_stage, stride out), from the observation row x: lanes run over output
+// units, every unit pmlp_unit's chain (so offsim_policy_mlp's / offsim_value_mlp's bits).  cur / nxt: the wave's two activation rows.
+// Returns the last layer's outputs, which stay in one of the rows until the wave's next forward.
+template <typename XT>
+__device__ __forceinline__ const float *collect_forward(const CollectMlp &M, const float *w, const XT *x, float *cur, float *nxt, int lane) {
+    for (int k = lane; k < M.dO; k += WAVE) cur[k] = pmlp_in<XT>(x, k);
+    wave_lds_sync();
+    for (int l = 0; l < M.n; l++) {
+        const int in = M.in[l], out = M.out[l];
+        const float *wt = w + M.woff[l];
+        const float *bl = M.boff[l] >= 0 ? w + M.boff[l] : nullptr;
+        const bool last = l == M.n - 1;
+        for (int j = lane; j < out; j += WAVE) nxt[j] = pmlp_unit(cur, wt + j, out, in, bl ? bl + j : nullptr, last, M.act, M.slope);
+        wave_lds_sync();
+        float *sw = cur;
+        cur = nxt;
+        nxt = sw;
+    }
+    return cur;
+}
+
 // The critic at an observation (moved false: the environment's x_start row; else obs_row encoding xrow), the same value in every lane.
-// MLP: the wave's forward through pmlp_unit over W^T in LDS, as the actor's (so offsim_value_mlp's bits); the last layer's one unit is
-// lane 0's chain.  It uses the wave's activation rows, which the actor's forward overwrites afterwards.  ROWS: the caller's tables.
+// MLP: the last layer's one unit.  It uses the wave's activation rows, which the actor's forward overwrites afterwards.  ROWS: the
+// caller's tables.
 template <int VF, typename XT>
 __device__ __forceinline__ float collect_value(const CollectValue &V, const float *v_lds, float *act, int w_max, bool moved, int64_t r,
                                                int32_t xrow, int lane) {
     if constexpr (VF == OFFSIM_VALUE_ROWS) {
         return xrow >= 0 ? V.v_next[xrow] : V.v_init[-2 - (int64_t)xrow];
     } else {
-        const int dO = V.dO;
-        const XT *x = !moved ? (const XT *)V.x_start + r * dO
-                      : xrow >= 0 ? (const XT *)V.x_next + (int64_t)xrow * dO
-                                  : (const XT *)V.x_init + (-2 - (int64_t)xrow) * dO;
-        float *cur = act, *nxt = act + w_max;
-        for (int k = lane; k < dO; k += WAVE) cur[k] = pmlp_in<XT>(x, k);
-        wave_lds_sync();
-        for (int l = 0; l < V.n; l++) {
-            const int in = V.in[l], out = V.out[l];
-            const float *wt = v_lds + V.woff[l];
-            const float *bl = V.boff[l] >= 0 ? v_lds + V.boff[l] : nullptr;
-            const bool last = l == V.n - 1;
-            for (int j = lane; j < out; j += WAVE) nxt[j] = pmlp_unit(cur, wt + j, out, in, bl ? bl + j : nullptr, last, V.act, V.slope);
-            wave_lds_sync();
-            float *sw = cur;
-            cur = nxt;
-            nxt = sw;
-        }
-        return cur[0];
+        const XT *x = collect_obs_row((const XT *)V.mlp.x_start + r * V.mlp.dO, V.mlp.x_next, V.mlp.x_init, V.mlp.dO, moved, xrow);
+        return collect_forward<XT>(V.mlp, v_lds, x, act, act + w_max, lane)[0];
     }
 }
 
@@ -132,32 +142,14 @@ __global__ void __launch_bounds__(COLLECT_WAVES * WAVE) k_collect(offsim_table t
     float *pf_lds = (float *)(lds_raw + A.off_pf) + wave * PMLP_MAX_ACTIONS;
     float *act_lds = (float *)(lds_raw + A.off_act) + (size_t)wave * 2 * A.mlp.w_max;
     if constexpr (FORM == OFFSIM_COLLECT_MLP) {
-        for (int l = 0; l < A.mlp.n; l++) {
-            const int in = A.mlp.in[l], out = A.mlp.out[l];
-            const float *__restrict__ W = A.mlp.W[l];
-            for (int e = threadIdx.x; e < in * out; e += blockDim.x) {  // W [out][in] (coalesced) -> W^T [in][out]
-                const int j = e / in, k = e - j * in;
-                w_lds[A.mlp.woff[l] + k * out + j] = W[e];
-            }
-            if (A.mlp.boff[l] >= 0)
-                for (int j = threadIdx.x; j < out; j += blockDim.x) w_lds[A.mlp.boff[l] + j] = A.mlp.b[l][j];
-        }
+        pmlp_stage(w_lds, A.mlp, A.mlp.out, threadIdx.x, blockDim.x);
     } else if constexpr (FORM == OFFSIM_COLLECT_TABULAR) {
         for (int i = threadIdx.x; i < t.n_slots * nA; i += blockDim.x) pi_lds[i] = ((const PROB *)A.pi)[i];
     }
     float *v_lds = nullptr;  // the critic's W^T / b (VF = OFFSIM_VALUE_MLP)
     if constexpr (VF == OFFSIM_VALUE_MLP) {
         v_lds = (float *)(lds_raw + A.V.off_w);
-        for (int l = 0; l < A.V.n; l++) {
-            const int in = A.V.in[l], out = A.V.out[l];
-            const float *__restrict__ W = A.V.W[l];
-            for (int e = threadIdx.x; e < in * out; e += blockDim.x) {
-                const int j = e / in, k = e - j * in;
-                v_lds[A.V.woff[l] + k * out + j] = W[e];
-            }
-            if (A.V.boff[l] >= 0)
-                for (int j = threadIdx.x; j < out; j += blockDim.x) v_lds[A.V.boff[l] + j] = A.V.b[l][j];
-        }
+        pmlp_stage(v_lds, A.V.mlp, A.V.mlp.out, threadIdx.x, blockDim.x);
     }
     __syncthreads();
     const int r = blockIdx.x * waves + wave;
@@ -184,7 +176,6 @@ __global__ void __launch_bounds__(COLLECT_WAVES * WAVE) k_collect(offsim_table t
     const uint32_t *perm_row = ro.perm ? ro.perm + (int64_t)r * ro.perm_stride : nullptr;
     const uint32_t *init_row = ro.init_perm ? ro.init_perm + (int64_t)r * ro.init_stride : nullptr;
     uint32_t *cursor = ro.cursor + (int64_t)r * t.n_slots;
-    const unsigned char *obs_next = (const unsigned char *)A.st.obs_next, *obs_init = (const unsigned char *)A.st.obs_init;
     unsigned char *obs_cur = (unsigned char *)A.st.obs + r * ob;
 
     for (int64_t i = 0; i < A.T; i++) {
@@ -206,10 +197,7 @@ __global__ void __launch_bounds__(COLLECT_WAVES * WAVE) k_collect(offsim_table t
                 if (lane == 0) A.V.rec.value[o] = A.V.rec.logp[o] = 0.0f;
             continue;
         }
-        if (A.out.obs) {
-            const unsigned char *src = !moved ? obs_cur : xrow >= 0 ? obs_next + (int64_t)xrow * ob : obs_init + (-2 - (int64_t)xrow) * ob;
-            wave_copy_row((unsigned char *)A.out.obs + o * ob, src, ob, lane);
-        }
+        if (A.out.obs) wave_copy_row((unsigned char *)A.out.obs + o * ob, collect_obs_row(obs_cur, A.st.obs_next, A.st.obs_init, ob, moved, xrow), ob, lane);
         // 0. the critic at the current observation (the actor's forward reuses the activation rows after it)
         float v = 0.0f;
         if constexpr (VF != COLLECT_VF_NONE) v = collect_value<VF, XT>(A.V, v_lds, act_lds, A.mlp.w_max, moved, r, xrow, lane);
@@ -217,26 +205,9 @@ __global__ void __launch_bounds__(COLLECT_WAVES * WAVE) k_collect(offsim_table t
         const PROB *pn;
         const float *logits = nullptr;  // MLP: the last layer's outputs, in the activation rows until the next forward
         if constexpr (FORM == OFFSIM_COLLECT_MLP) {
-            const int dO = A.mlp.dO;
-            const XT *x = !moved ? (const XT *)A.mlp.x_start + (int64_t)r * dO
-                          : xrow >= 0 ? (const XT *)A.mlp.x_next + (int64_t)xrow * dO
-                                      : (const XT *)A.mlp.x_init + (-2 - (int64_t)xrow) * dO;
-            float *cur = act_lds, *nxt = act_lds + A.mlp.w_max;
-            for (int k = lane; k < dO; k += WAVE) cur[k] = pmlp_in<XT>(x, k);
-            wave_lds_sync();
-            for (int l = 0; l < A.mlp.n; l++) {
-                const int in = A.mlp.in[l], out = A.mlp.out[l];
-                const float *wt = w_lds + A.mlp.woff[l];
-                const float *bl = A.mlp.boff[l] >= 0 ? w_lds + A.mlp.boff[l] : nullptr;
-                const bool last = l == A.mlp.n - 1;
-                for (int j = lane; j < out; j += WAVE) nxt[j] = pmlp_unit(cur, wt + j, out, in, bl ? bl + j : nullptr, last, A.mlp.act, A.mlp.slope);
-                wave_lds_sync();
-                float *sw = cur;
-                cur = nxt;
-                nxt = sw;
-            }
-            if (lane == 0) pmlp_softmax(cur, nA, pf_lds);
-            logits = cur;
+            const XT *x = collect_obs_row((const XT *)A.mlp.x_start + (int64_t)r * A.mlp.dO, A.mlp.x_next, A.mlp.x_init, A.mlp.dO, moved, xrow);
+            logits = collect_forward<XT>(A.mlp, w_lds, x, act_lds, act_lds + A.mlp.w_max, lane);
+            if (lane == 0) pmlp_softmax(logits, nA, pf_lds);
             wave_lds_sync();
             if (lane < nA) {
                 const float p = pf_lds[lane];
@@ -315,7 +286,7 @@ __global__ void __launch_bounds__(COLLECT_WAVES * WAVE) k_collect(offsim_table t
         if (lane == 0) A.V.rec.final_value[r] = vf;
     }
     // the state, for the next call
-    if (moved) wave_copy_row(obs_cur, xrow >= 0 ? obs_next + (int64_t)xrow * ob : obs_init + (-2 - (int64_t)xrow) * ob, ob, lane);
+    if (moved) wave_copy_row(obs_cur, collect_obs_row(obs_cur, A.st.obs_next, A.st.obs_init, ob, moved, xrow), ob, lane);
     if (lane == 0) {
         if (consumed && ro.rng_kind == OFFSIM_STREAM_PHILOX) {
             ro.rng[4 * r + 1] = base.lo + consumed;
@@ -345,8 +316,39 @@ static size_t collect_lds_layout(int waves, size_t shared_bytes, int w_max, Coll
     return off;
 }
 
-// Validation of offsim_vector_collect's arguments and the actor's part of A; `shared` gets the bytes of the actor's LDS region (weights or pi).
-static int collect_prepare(const offsim_table *t, offsim_rollouts *ro, const offsim_collect_policy *pol, int32_t prob_mode, int32_t reject_mode,
+// The MLP form of an offsim_collect_policy (n_out = the table's nA) or an offsim_collect_value (n_out = 1): pmlp_describe's checks, the
+// observations, and the kernel's descriptor with W^T [in][out] and b packed from LDS float 0.  The float cap is the caller's.
+template <typename SPEC>
+static int collect_mlp(const char *who, const offsim_table *t, const SPEC &p, int n_out, CollectMlp &M) {
+    PmlpNet N;
+    int rc = pmlp_describe(who, p.layers_host, p.n_layers, p.dO, p.activation, p.slope, p.x_dtype, n_out, N);
+    if (rc) return rc;
+    M.floats = 0;
+    if (!p.x_start || (t->N > 0 && (!p.x_next || !p.x_init))) return fail(OFFSIM_EINVAL, "%s: x_start / x_next / x_init is NULL", who);
+    for (int l = 0; l < N.n; l++) {
+        M.W[l] = N.W[l];
+        M.b[l] = N.b[l];
+        M.in[l] = N.in[l];
+        M.out[l] = N.out[l];
+        M.woff[l] = M.floats;
+        M.floats += N.in[l] * N.out[l];
+        M.boff[l] = N.b[l] ? M.floats : -1;
+        M.floats += N.b[l] ? N.out[l] : 0;
+    }
+    M.n = N.n;
+    M.w_max = N.w_max;
+    M.act = N.act;
+    M.slope = N.slope;
+    M.dO = N.dO;
+    M.x_start = p.x_start;
+    M.x_next = p.x_next;
+    M.x_init = p.x_init;
+    return OFFSIM_OK;
+}
+
+// Validation of offsim_vector_collect's arguments and the actor's part of A (`who`: the entry point, in the network's error text); `shared`
+// gets the bytes of the actor's LDS region (weights or pi).
+static int collect_prepare(const char *who, const offsim_table *t, offsim_rollouts *ro, const offsim_collect_policy *pol, int32_t prob_mode, int32_t reject_mode,
                            int64_t T, int32_t max_episode_steps, const offsim_collect_state *st, const offsim_collect_out *out, CollectArgs &A,
                            size_t &shared) {
     int rc = check_table(t);
@@ -360,49 +362,14 @@ static int collect_prepare(const offsim_table *t, offsim_rollouts *ro, const off
     if (T > 0 && (!out->row || !out->flags)) return fail(OFFSIM_EINVAL, "vector_collect: out->row / out->flags is NULL%s");
     if (t->N0 > 0 && (!t->init_slot || !t->init_orig)) return fail(OFFSIM_EINVAL, "vector_collect: table has no init rows%s");
     memset(&A, 0, sizeof(A));
-    A.mlp.w_max = 0;
     shared = 0;
     const size_t pb = prob_mode == OFFSIM_PROB_F32 ? 4 : 8;
     if (pol->form == OFFSIM_COLLECT_MLP) {
-        const int n = pol->n_layers, dO = pol->dO;
-        if (!pol->layers_host || n < 1 || n > PMLP_MAX_LAYERS) return fail(OFFSIM_EINVAL, "vector_collect: 1 to 4 Linear layers%s");
-        if (pol->x_dtype != OFFSIM_F32 && pol->x_dtype != OFFSIM_F16) return fail(OFFSIM_EINVAL, "vector_collect: x_dtype must be OFFSIM_F32 or OFFSIM_F16%s");
-        if (pol->activation != OFFSIM_ACT_IDENTITY && pol->activation != OFFSIM_ACT_TANH && pol->activation != OFFSIM_ACT_RELU &&
-            pol->activation != OFFSIM_ACT_LEAKY_RELU)
-            return fail(OFFSIM_EINVAL, "vector_collect: unknown activation%s");
-        if (dO < 1 || dO > PMLP_MAX_IN) return fail(OFFSIM_EINVAL, "vector_collect: observation width must be 1..128%s");
-        if (!pol->x_start || (t->N > 0 && (!pol->x_next || !pol->x_init))) return fail(OFFSIM_EINVAL, "vector_collect: x_start / x_next / x_init is NULL%s");
-        int floats = 0;
-        A.mlp.w_max = dO;
-        for (int l = 0; l < n; l++) {
-            const offsim_mlp_layer &y = pol->layers_host[l];
-            const bool last = l == n - 1;
-            if (!y.W) return fail(OFFSIM_EINVAL, "vector_collect: a layer's W is NULL%s");
-            if (y.in != (l == 0 ? dO : pol->layers_host[l - 1].out)) return fail(OFFSIM_EINVAL, "vector_collect: layer widths do not chain%s");
-            if (y.out < 1 || y.out > (last ? PMLP_MAX_ACTIONS : PMLP_MAX_HIDDEN))
-                return fail(OFFSIM_EINVAL, last ? "vector_collect: more than 16 actions%s" : "vector_collect: hidden width above 256%s");
-            if (last && y.out != t->nA) return fail(OFFSIM_EINVAL, "vector_collect: the network's outputs differ from the table's nA%s");
-            A.mlp.W[l] = y.W;
-            A.mlp.b[l] = y.b;
-            A.mlp.in[l] = y.in;
-            A.mlp.out[l] = y.out;
-            A.mlp.woff[l] = floats;
-            floats += y.in * y.out;
-            A.mlp.boff[l] = y.b ? floats : -1;
-            floats += y.b ? y.out : 0;
-            if (y.out > A.mlp.w_max) A.mlp.w_max = y.out;
-        }
-        if (floats > OFFSIM_COLLECT_MLP_MAX_FLOATS)
-            return fail(OFFSIM_EUNSUPPORTED, "vector_collect: the network's weights exceed OFFSIM_COLLECT_MLP_MAX_FLOATS (64 KiB of LDS)%s");
-        A.mlp.n = n;
-        A.mlp.floats = floats;
-        A.mlp.act = pol->activation;
-        A.mlp.slope = pol->slope;
-        A.mlp.dO = dO;
-        A.mlp.x_start = pol->x_start;
-        A.mlp.x_next = pol->x_next;
-        A.mlp.x_init = pol->x_init;
-        shared = (size_t)floats * sizeof(float);
+        rc = collect_mlp(who, t, *pol, t->nA, A.mlp);
+        if (rc) return rc;
+        if (A.mlp.floats > OFFSIM_COLLECT_MLP_MAX_FLOATS)
+            return fail(OFFSIM_EUNSUPPORTED, "%s: the network's weights exceed OFFSIM_COLLECT_MLP_MAX_FLOATS (64 KiB of LDS)", who);
+        shared = (size_t)A.mlp.floats * sizeof(float);
     } else if (pol->form == OFFSIM_COLLECT_ROWS) {
         if (t->N > 0 && (!pol->p_next || !pol->p_init)) return fail(OFFSIM_EINVAL, "vector_collect: p_next / p_init is NULL%s");
         A.p_next = pol->p_next;
@@ -463,7 +430,7 @@ extern "C" int offsim_vector_collect(const offsim_table *t, offsim_rollouts *ro,
                                      const offsim_collect_out *out, void *stream) {
     CollectArgs A;
     size_t shared;
-    int rc = collect_prepare(t, ro, pol, prob_mode, reject_mode, T, max_episode_steps, st, out, A, shared);
+    int rc = collect_prepare("vector_collect", t, ro, pol, prob_mode, reject_mode, T, max_episode_steps, st, out, A, shared);
     if (rc) return rc;
     const size_t lds = collect_lds_layout(COLLECT_WAVES, shared, A.mlp.w_max, A);
     if (lds > 160 * 1024) return fail(OFFSIM_EUNSUPPORTED, "vector_collect: the policy table and per-wave scratch exceed 160 KiB of LDS%s");
@@ -476,7 +443,7 @@ extern "C" int offsim_vector_collect_ppo(const offsim_table *t, offsim_rollouts 
                                          const offsim_collect_out *out, const offsim_collect_ppo_out *ppo, void *stream) {
     CollectPpoArgs A;
     size_t shared;
-    int rc = collect_prepare(t, ro, pol, prob_mode, reject_mode, T, max_episode_steps, st, out, A, shared);
+    int rc = collect_prepare("vector_collect_ppo", t, ro, pol, prob_mode, reject_mode, T, max_episode_steps, st, out, A, shared);
     if (rc) return rc;
     memset(&A.V, 0, sizeof(A.V));
     if (!val || !ppo) return fail(OFFSIM_EINVAL, "vector_collect_ppo: val / ppo is NULL%s");
@@ -485,48 +452,17 @@ extern "C" int offsim_vector_collect_ppo(const offsim_table *t, offsim_rollouts 
     CollectValue &V = A.V;
     int x_dtype = pol->form == OFFSIM_COLLECT_MLP ? pol->x_dtype : OFFSIM_F32;
     if (val->form == OFFSIM_VALUE_MLP) {
-        const int n = val->n_layers, dO = val->dO;
-        if (!val->layers_host || n < 1 || n > PMLP_MAX_LAYERS) return fail(OFFSIM_EINVAL, "vector_collect_ppo: the critic has 1 to 4 Linear layers%s");
-        if (val->x_dtype != OFFSIM_F32 && val->x_dtype != OFFSIM_F16) return fail(OFFSIM_EINVAL, "vector_collect_ppo: critic x_dtype must be OFFSIM_F32 or OFFSIM_F16%s");
+        rc = collect_mlp("vector_collect_ppo critic", t, *val, 1, V.mlp);
+        if (rc) return rc;
         if (pol->form == OFFSIM_COLLECT_MLP && val->x_dtype != pol->x_dtype)
             return fail(OFFSIM_EINVAL, "vector_collect_ppo: the actor and the critic read observations of different types%s");
-        if (val->activation != OFFSIM_ACT_IDENTITY && val->activation != OFFSIM_ACT_TANH && val->activation != OFFSIM_ACT_RELU &&
-            val->activation != OFFSIM_ACT_LEAKY_RELU)
-            return fail(OFFSIM_EINVAL, "vector_collect_ppo: unknown critic activation%s");
-        if (dO < 1 || dO > PMLP_MAX_IN) return fail(OFFSIM_EINVAL, "vector_collect_ppo: critic observation width must be 1..128%s");
-        if (!val->x_start || (t->N > 0 && (!val->x_next || !val->x_init))) return fail(OFFSIM_EINVAL, "vector_collect_ppo: critic x_start / x_next / x_init is NULL%s");
-        x_dtype = val->x_dtype;
-        int floats = 0, w_max = dO;
-        for (int l = 0; l < n; l++) {
-            const offsim_mlp_layer &y = val->layers_host[l];
-            const bool last = l == n - 1;
-            if (!y.W) return fail(OFFSIM_EINVAL, "vector_collect_ppo: a critic layer's W is NULL%s");
-            if (y.in != (l == 0 ? dO : val->layers_host[l - 1].out)) return fail(OFFSIM_EINVAL, "vector_collect_ppo: critic layer widths do not chain%s");
-            if (last ? y.out != 1 : (y.out < 1 || y.out > PMLP_MAX_HIDDEN))
-                return fail(OFFSIM_EINVAL, last ? "vector_collect_ppo: the critic's last layer must have one output unit%s" : "vector_collect_ppo: critic hidden width above 256%s");
-            V.W[l] = y.W;
-            V.b[l] = y.b;
-            V.in[l] = y.in;
-            V.out[l] = y.out;
-            V.woff[l] = floats;
-            floats += y.in * y.out;
-            V.boff[l] = y.b ? floats : -1;
-            floats += y.b ? y.out : 0;
-            if (y.out > w_max) w_max = y.out;
-        }
-        if (A.mlp.floats + floats > OFFSIM_COLLECT_MLP_MAX_FLOATS)
+        if (A.mlp.floats + V.mlp.floats > OFFSIM_COLLECT_MLP_MAX_FLOATS)
             return fail(OFFSIM_EUNSUPPORTED, "vector_collect_ppo: the actor's and the critic's weights exceed OFFSIM_COLLECT_MLP_MAX_FLOATS (64 KiB of LDS)%s");
-        V.n = n;
-        V.act = val->activation;
-        V.slope = val->slope;
-        V.dO = dO;
-        V.x_start = val->x_start;
-        V.x_next = val->x_next;
-        V.x_init = val->x_init;
-        if (w_max > A.mlp.w_max) A.mlp.w_max = w_max;
+        x_dtype = val->x_dtype;
+        if (V.mlp.w_max > A.mlp.w_max) A.mlp.w_max = V.mlp.w_max;
         const size_t actor = (shared + 15) & ~(size_t)15;
         V.off_w = (uint32_t)((size_t)COLLECT_WAVES * (WAVE + 1) * sizeof(Jump) + actor);
-        shared = actor + (size_t)floats * sizeof(float);
+        shared = actor + (size_t)V.mlp.floats * sizeof(float);
     } else if (val->form == OFFSIM_VALUE_ROWS) {
         if (t->N > 0 && (!val->v_next || !val->v_init)) return fail(OFFSIM_EINVAL, "vector_collect_ppo: v_next / v_init is NULL%s");
         V.v_next = val->v_next;

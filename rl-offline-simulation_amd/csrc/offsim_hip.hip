@@ -2241,30 +2241,19 @@ extern "C" int offsim_encode_mlp(const void *x, int32_t x_dtype, int64_t N, int3
 // one unit, written as it is); `who` names the entry point in the error messages
 static int mlp_forward(const void *x, int32_t x_dtype, int64_t n_x, int32_t dO, const int32_t *rows, int64_t M, const offsim_mlp_layer *layers_host,
                        int32_t n_layers, int32_t activation, float slope, float *out, void *stream, bool value, const char *who) {
-    if (M < 0 || n_x < 0 || dO <= 0 || !layers_host) return fail(OFFSIM_EINVAL, "%s: bad argument", who);
-    if (x_dtype != OFFSIM_F32 && x_dtype != OFFSIM_F16) return fail(OFFSIM_EINVAL, "%s: x_dtype must be OFFSIM_F32 or OFFSIM_F16", who);
-    if (n_layers < 1 || n_layers > PMLP_MAX_LAYERS) return fail(OFFSIM_EINVAL, "%s: 1 to 4 Linear layers", who);
-    if (activation != OFFSIM_ACT_IDENTITY && activation != OFFSIM_ACT_TANH && activation != OFFSIM_ACT_RELU && activation != OFFSIM_ACT_LEAKY_RELU)
-        return fail(OFFSIM_EINVAL, "%s: unknown activation", who);
-    if (dO > PMLP_MAX_IN) return fail(OFFSIM_EINVAL, "%s: observation width above 128", who);
+    if (M < 0 || n_x < 0) return fail(OFFSIM_EINVAL, "%s: bad argument", who);
+    PmlpNet N;
+    int rc = pmlp_describe(who, layers_host, n_layers, dO, activation, slope, x_dtype, value ? 1 : PMLP_OUT_ACTIONS, N);
+    if (rc) return rc;
     PmlpLayers L{};
-    L.n = n_layers;
-    L.w_max = dO;
-    L.w_floats = 0;
-    for (int l = 0; l < n_layers; l++) {
-        const offsim_mlp_layer &y = layers_host[l];
-        if (!y.W) return fail(OFFSIM_EINVAL, "%s: a layer's W is NULL", who);
-        if (y.in != (l == 0 ? dO : layers_host[l - 1].out)) return fail(OFFSIM_EINVAL, "%s: layer widths do not chain", who);
-        const bool last = l == n_layers - 1;
-        if (value && last && y.out != 1) return fail(OFFSIM_EINVAL, "%s: the last layer must have one output unit", who);
-        if (y.out < 1 || y.out > (last ? PMLP_MAX_ACTIONS : PMLP_MAX_HIDDEN))
-            return fail(OFFSIM_EINVAL, last ? "%s: more than 16 actions" : "%s: hidden width above 256", who);
-        L.W[l] = y.W;
-        L.b[l] = y.b;
-        L.in[l] = y.in;
-        L.out[l] = y.out;
-        if (y.out > L.w_max) L.w_max = y.out;
-        const int chunk = y.out * (y.in + 1);
+    L.n = N.n;
+    L.w_max = N.w_max;
+    for (int l = 0; l < N.n; l++) {
+        L.W[l] = N.W[l];
+        L.b[l] = N.b[l];
+        L.in[l] = N.in[l];
+        L.out[l] = N.out[l];
+        const int chunk = N.out[l] * (N.in[l] + 1);
         const int need = chunk < PMLP_W_FLOATS ? chunk : PMLP_W_FLOATS;
         if (need > L.w_floats) L.w_floats = need;
     }

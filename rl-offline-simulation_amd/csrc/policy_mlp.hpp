@@ -18,6 +18,53 @@
 #define PMLP_MAX_HIDDEN 256
 #define PMLP_MAX_ACTIONS 16
 
+// THE description of a network on the host: what offsim_policy_mlp / offsim_value_mlp, offsim_vector_collect[_ppo] (actor and critic) and
+// offsim_ppo_grad / offsim_ppo_update all take.  pmlp_describe is the only place that knows the limits; each entry point derives its own
+// kernel's descriptor (LDS layout, chunk size, parameter offsets) from this.
+struct PmlpNet {
+    const float *W[PMLP_MAX_LAYERS];
+    const float *b[PMLP_MAX_LAYERS];  // NULL: no bias
+    int in[PMLP_MAX_LAYERS], out[PMLP_MAX_LAYERS];
+    int n, act, dO, w_max;  // number of layers, OFFSIM_ACT_*, observation width, widest activation (input included)
+    float slope;
+};
+
+#define PMLP_OUT_ACTIONS 0  // pmlp_describe's n_out: the last layer has 1..16 units (an actor's logits)
+
+// Validates a network (1-4 Linear layers, f32 / f16 observations of width 1..128, a known activation, W present, widths that chain, hidden
+// widths <= 256, and the last layer: n_out units -- 1 for a critic, a table's nA -- or PMLP_OUT_ACTIONS) and fills N.  LAYER:
+// offsim_mlp_layer or offsim_ppo_layer (the same layout with writable pointers).  `who` names the entry point in the error text.
+template <typename LAYER>
+static int pmlp_describe(const char *who, const LAYER *layers_host, int n, int dO, int activation, float slope, int x_dtype, int n_out, PmlpNet &N) {
+    if (!layers_host || n < 1 || n > PMLP_MAX_LAYERS) return fail(OFFSIM_EINVAL, "%s: 1 to 4 Linear layers", who);
+    if (x_dtype != OFFSIM_F32 && x_dtype != OFFSIM_F16) return fail(OFFSIM_EINVAL, "%s: x_dtype must be OFFSIM_F32 or OFFSIM_F16", who);
+    if (activation != OFFSIM_ACT_IDENTITY && activation != OFFSIM_ACT_TANH && activation != OFFSIM_ACT_RELU && activation != OFFSIM_ACT_LEAKY_RELU)
+        return fail(OFFSIM_EINVAL, "%s: unknown activation", who);
+    if (dO < 1 || dO > PMLP_MAX_IN) return fail(OFFSIM_EINVAL, "%s: observation width must be 1..128", who);
+    N = PmlpNet{};
+    N.n = n;
+    N.act = activation;
+    N.slope = slope;
+    N.dO = N.w_max = dO;
+    for (int l = 0; l < n; l++) {
+        const LAYER &y = layers_host[l];
+        const bool last = l == n - 1;
+        if (!y.W) return fail(OFFSIM_EINVAL, "%s: a layer's W is NULL", who);
+        if (y.in != (l == 0 ? dO : layers_host[l - 1].out)) return fail(OFFSIM_EINVAL, "%s: layer widths do not chain", who);
+        if (last && n_out == 1 && y.out != 1) return fail(OFFSIM_EINVAL, "%s: the last layer must have one output unit", who);
+        if (y.out < 1 || y.out > (last ? PMLP_MAX_ACTIONS : PMLP_MAX_HIDDEN))
+            return fail(OFFSIM_EINVAL, last ? "%s: more than 16 actions" : "%s: hidden width above 256", who);
+        if (last && n_out != PMLP_OUT_ACTIONS && y.out != n_out) return fail(OFFSIM_EINVAL, "%s: the network's outputs differ from the table's nA", who);
+        N.W[l] = y.W;
+        N.b[l] = y.b;
+        N.in[l] = y.in;
+        N.out[l] = y.out;
+        if (y.out > N.w_max) N.w_max = y.out;
+    }
+    return OFFSIM_OK;
+}
+
+// k_policy_mlp's descriptor
 struct PmlpLayers {
     const float *W[PMLP_MAX_LAYERS];
     const float *b[PMLP_MAX_LAYERS];
@@ -36,8 +83,8 @@ __device__ __forceinline__ float pmlp_act(float v, int act, float slope) {
 }
 
 // One output unit of a layer: sum_k x[k] * w[k * ws] as ONE fmaf chain in k order, then + bias (b NULL: none), then the activation unless
-// the layer is the last.  Shared by k_policy_mlp (w = a row of W, ws = 1) and the in-wave forward of offsim_vector_collect (w = a column
-// of W^T, ws = out), so both produce the same bits.
+// the layer is the last.  Shared by k_policy_mlp (w = a row of W, ws = 1) and k_collect's in-wave forward (collect.hpp: collect_forward,
+// w = a column of W^T, ws = out), so both produce the same bits.
 __device__ __forceinline__ float pmlp_unit(const float *x, const float *w, int ws, int in, const float *b, bool last, int act, float slope) {
     float acc = 0.0f;
     for (int k = 0; k < in; k++) acc = fmaf(x[k], w[k * ws], acc);
@@ -78,6 +125,23 @@ template <>
 __device__ __forceinline__ float pmlp_in<float>(const float *x, int64_t i) { return x[i]; }
 template <>
 __device__ __forceinline__ float pmlp_in<__half>(const __half *x, int64_t i) { return __half2float(x[i]); }
+
+// Stages a network for a kernel that keeps all of it in LDS (k_collect, k_ppo_grad), all nt threads of the workgroup striding: per layer
+// W [out][in] (read coalesced) -> W^T [in][ld[l]] at dst + woff[l], then b at dst + boff[l] (boff < 0: no bias).  N: that kernel's
+// descriptor, with W, b, in, out, woff, boff and n; nt: the workgroup's size as that kernel has it (blockDim.x, or its constant).
+template <typename NET, typename NT>
+__device__ __forceinline__ void pmlp_stage(float *dst, const NET &N, const int *ld, int tid, NT nt) {
+    for (int l = 0; l < N.n; l++) {
+        const int in = N.in[l], out = N.out[l], ldw = ld[l];
+        const float *__restrict__ W = N.W[l];
+        for (int e = tid; e < in * out; e += nt) {
+            const int j = e / in, k = e - j * in;
+            dst[N.woff[l] + k * ldw + j] = W[e];
+        }
+        if (N.boff[l] >= 0)
+            for (int j = tid; j < out; j += nt) dst[N.boff[l] + j] = N.b[l][j];
+    }
+}
 
 // VALUE: the critic of the same shape (offsim_value_mlp, spinup's MLPCritic: v = squeeze(v_net(obs), -1)): the last layer has one unit and
 // no softmax follows, probs is then out[M].

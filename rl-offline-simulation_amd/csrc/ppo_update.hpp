@@ -3,8 +3,8 @@
 // loss -- as pairs of launches, with no host round trip between them.
 //
 //   k_ppo_grad<KIND, XT>  one fused forward, loss and backward pass over M records.  A workgroup of 512 threads stages every layer's W^T
-//                         and b into LDS once and then takes tiles of TM records (tile i of workgroup b is b + i * gridDim.x: a fixed
-//                         assignment).  A tile's activations A [TM][all layers' widths] and back-propagated deltas D [TM][all layers'
+//                         and b into LDS once (pmlp_stage, policy_mlp.hpp) and then takes tiles of TM records (tile i of workgroup
+//                         b is b + i * gridDim.x: a fixed assignment).  A tile's activations A [TM][all layers' widths] and back-propagated deltas D [TM][all layers'
 //                         outputs] live in LDS and are never written to HBM.  Per tile:
 //                           F  per layer, thread = (4 records, one output unit): one fmaf chain over k per record, W^T[k][j] read once
 //                              for the four;
@@ -74,16 +74,7 @@ __global__ void __launch_bounds__(PPOU_THREADS) k_ppo_grad(PpoNet N, PpoBatchArg
     const int tid = threadIdx.x, TM = B.TM, lda = N.lda, ldd = N.ldd, nl = N.n;
     const int nout = N.out[nl - 1];
 
-    for (int l = 0; l < nl; l++) {  // W [out][in] (coalesced) -> W^T [in][ldw]
-        const int in = N.in[l], out = N.out[l], ldw = N.ldw[l];
-        const float *__restrict__ W = N.W[l];
-        for (int e = tid; e < in * out; e += PPOU_THREADS) {
-            const int j = e / in, k = e - j * in;
-            w_lds[N.woff[l] + k * ldw + j] = W[e];
-        }
-        if (N.boff[l] >= 0)
-            for (int j = tid; j < out; j += PPOU_THREADS) w_lds[N.boff[l] + j] = N.b[l][j];
-    }
+    pmlp_stage(w_lds, N, N.ldw, tid, PPOU_THREADS);
     for (int e = tid; e < TM * lda; e += PPOU_THREADS) A[e] = 0.0f;
     for (int e = tid; e < TM * ldd; e += PPOU_THREADS) D[e] = 0.0f;
     __syncthreads();
@@ -354,38 +345,22 @@ __global__ void k_ppo_finish(int64_t *t, const double *stats, const double *work
     *t += stopped ? (int64_t)stats[5] : (int64_t)iters;
 }
 
-// Validation and the layouts of a network for k_ppo_grad / k_ppo_adam.
+// The network (pmlp_describe's checks) and the batch of an update, and k_ppo_grad's / k_ppo_adam's layouts of them.
 static int ppou_prepare(const char *who, const offsim_ppo_net *net, int32_t kind, const offsim_ppo_batch *bt, PpoNet &N, PpoBatchArgs &B, size_t &lds) {
-    static thread_local char msg[160];
-#define PPOU_FAIL(code, text)                                  \
-    do {                                                       \
-        snprintf(msg, sizeof(msg), "%s: " text "%%s", who);    \
-        return fail(code, msg);                                \
-    } while (0)
-    if (!net || !bt) PPOU_FAIL(OFFSIM_EINVAL, "net / batch is NULL");
-    if (kind != OFFSIM_PPO_ACTOR && kind != OFFSIM_PPO_CRITIC) PPOU_FAIL(OFFSIM_EINVAL, "kind must be OFFSIM_PPO_ACTOR or OFFSIM_PPO_CRITIC");
-    const int n = net->n_layers, dO = bt->dO;
-    if (!net->layers_host || n < 1 || n > PMLP_MAX_LAYERS) PPOU_FAIL(OFFSIM_EINVAL, "1 to 4 Linear layers");
-    if (bt->x_dtype != OFFSIM_F32 && bt->x_dtype != OFFSIM_F16) PPOU_FAIL(OFFSIM_EINVAL, "x_dtype must be OFFSIM_F32 or OFFSIM_F16");
-    if (net->activation != OFFSIM_ACT_IDENTITY && net->activation != OFFSIM_ACT_TANH && net->activation != OFFSIM_ACT_RELU &&
-        net->activation != OFFSIM_ACT_LEAKY_RELU)
-        PPOU_FAIL(OFFSIM_EINVAL, "unknown activation");
-    if (net->activation == OFFSIM_ACT_LEAKY_RELU && !(net->slope >= 0.0f)) PPOU_FAIL(OFFSIM_EINVAL, "a leaky_relu slope below 0 is not supported");
-    if (dO < 1 || dO > PMLP_MAX_IN) PPOU_FAIL(OFFSIM_EINVAL, "observation width must be 1..128");
-    if (bt->M < 0) PPOU_FAIL(OFFSIM_EINVAL, "M must be >= 0");
+    if (!net || !bt) return fail(OFFSIM_EINVAL, "%s: net / batch is NULL", who);
+    if (kind != OFFSIM_PPO_ACTOR && kind != OFFSIM_PPO_CRITIC) return fail(OFFSIM_EINVAL, "%s: kind must be OFFSIM_PPO_ACTOR or OFFSIM_PPO_CRITIC", who);
+    PmlpNet D;
+    int rc = pmlp_describe(who, net->layers_host, net->n_layers, bt->dO, net->activation, net->slope, bt->x_dtype,
+                           kind == OFFSIM_PPO_CRITIC ? 1 : PMLP_OUT_ACTIONS, D);
+    if (rc) return rc;
+    if (D.act == OFFSIM_ACT_LEAKY_RELU && !(D.slope >= 0.0f)) return fail(OFFSIM_EINVAL, "%s: a leaky_relu slope below 0 is not supported", who);
+    if (bt->M < 0) return fail(OFFSIM_EINVAL, "%s: M must be >= 0", who);
     memset(&N, 0, sizeof(N));
     memset(&B, 0, sizeof(B));
-    int P = 0, wf = 0, ac = dO, dc = 0;
+    const int n = D.n;
+    int P = 0, wf = 0, ac = D.dO, dc = 0;
     for (int l = 0; l < n; l++) {
-        const offsim_ppo_layer &y = net->layers_host[l];
-        const bool last = l == n - 1;
-        if (!y.W) PPOU_FAIL(OFFSIM_EINVAL, "a layer's W is NULL");
-        if (y.in != (l == 0 ? dO : net->layers_host[l - 1].out)) PPOU_FAIL(OFFSIM_EINVAL, "layer widths do not chain");
-        if (y.out < 1 || y.out > (last ? PMLP_MAX_ACTIONS : PMLP_MAX_HIDDEN)) {
-            if (last) PPOU_FAIL(OFFSIM_EINVAL, "more than 16 actions");
-            PPOU_FAIL(OFFSIM_EINVAL, "hidden width above 256");
-        }
-        if (last && kind == OFFSIM_PPO_CRITIC && y.out != 1) PPOU_FAIL(OFFSIM_EINVAL, "the critic's last layer must have one output unit");
+        const offsim_ppo_layer &y = net->layers_host[l];  // (the writable pointers)
         N.W[l] = y.W;
         N.b[l] = y.b;
         N.in[l] = y.in;
@@ -402,7 +377,7 @@ static int ppou_prepare(const char *who, const offsim_ppo_net *net, int32_t kind
         N.dcol[l] = dc;
         dc += y.out;
     }
-    if (P > OFFSIM_COLLECT_MLP_MAX_FLOATS) PPOU_FAIL(OFFSIM_EUNSUPPORTED, "the network's weights exceed OFFSIM_COLLECT_MLP_MAX_FLOATS");
+    if (P > OFFSIM_COLLECT_MLP_MAX_FLOATS) return fail(OFFSIM_EUNSUPPORTED, "%s: the network's weights exceed OFFSIM_COLLECT_MLP_MAX_FLOATS", who);
     N.acol[n] = ac;
     ac += N.out[n - 1];
     N.ones = ac;
@@ -410,19 +385,19 @@ static int ppou_prepare(const char *who, const offsim_ppo_net *net, int32_t kind
     N.ldd = dc | 1;
     N.n = n;
     N.P = P;
-    N.act = net->activation;
-    N.slope = net->slope;
+    N.act = D.act;
+    N.slope = D.slope;
     N.w_floats = (wf + 3) & ~3;
     int TM = 32;
     for (;; TM /= 2) {
         lds = sizeof(float) * ((size_t)N.w_floats + (size_t)TM * N.lda + (((size_t)TM * N.ldd + 1) & ~(size_t)1)) + sizeof(double) * 5 * TM;
         if (lds <= 160 * 1024 || TM == PPOU_RB) break;
     }
-    if (lds > 160 * 1024) PPOU_FAIL(OFFSIM_EUNSUPPORTED, "the weights and one tile's activations exceed 160 KiB of LDS");
+    if (lds > 160 * 1024) return fail(OFFSIM_EUNSUPPORTED, "%s: the weights and one tile's activations exceed 160 KiB of LDS", who);
     if (bt->M > 0) {
-        if (!bt->obs) PPOU_FAIL(OFFSIM_EINVAL, "obs is NULL");
-        if (kind == OFFSIM_PPO_ACTOR && (!bt->act || !bt->adv || !bt->logp)) PPOU_FAIL(OFFSIM_EINVAL, "the actor needs act, adv and logp");
-        if (kind == OFFSIM_PPO_CRITIC && !bt->ret) PPOU_FAIL(OFFSIM_EINVAL, "the critic needs ret");
+        if (!bt->obs) return fail(OFFSIM_EINVAL, "%s: obs is NULL", who);
+        if (kind == OFFSIM_PPO_ACTOR && (!bt->act || !bt->adv || !bt->logp)) return fail(OFFSIM_EINVAL, "%s: the actor needs act, adv and logp", who);
+        if (kind == OFFSIM_PPO_CRITIC && !bt->ret) return fail(OFFSIM_EINVAL, "%s: the critic needs ret", who);
     }
     B.obs = bt->obs;
     B.act = bt->act;
@@ -431,9 +406,8 @@ static int ppou_prepare(const char *who, const offsim_ppo_net *net, int32_t kind
     B.ret = bt->ret;
     B.valid = bt->valid;
     B.M = bt->M;
-    B.dO = dO;
+    B.dO = D.dO;
     B.TM = TM;
-#undef PPOU_FAIL
     return OFFSIM_OK;
 }
 

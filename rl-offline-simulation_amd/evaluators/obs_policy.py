@@ -113,6 +113,28 @@ class _MLPNet:
             self._dev[key] = (ws, arr)
         return self._dev[key]
 
+    _value = False  # MLPValue: the entry point is offsim_value_mlp and the output [M], not offsim_policy_mlp and [M, nA]
+
+    def forward(self, x, rows=None, out=None):
+        """The HIP forward, f32 on x's device (MLPPolicy: probs [M, nA]; MLPValue: v [M]): x [n, dO] f32 / f16 device tensor, rows
+        (optional) [M] int32 gather index into x."""
+        if x.dim() != 2 or x.shape[1] != self.dO:
+            raise ValueError(f"{type(self).__name__}: observations of width {self.dO} expected, got shape {tuple(x.shape)}")
+        if x.dtype not in (torch.float32, torch.float16):
+            x = x.to(torch.float32)
+        x = x.contiguous()
+        if rows is not None:
+            rows = rows.to(device=x.device, dtype=torch.int32).contiguous()
+        M = int(x.shape[0]) if rows is None else int(rows.numel())
+        if out is None:
+            out = torch.empty((M,) if self._value else (M, self.nA), dtype=torch.float32, device=x.device)
+        ws, arr = self._device_weights(x.device)
+        entry = L.load().offsim_value_mlp if self._value else L.load().offsim_policy_mlp
+        L.check(entry(L.ptr(x) if x.numel() else None, L.F32 if x.dtype == torch.float32 else L.F16, int(x.shape[0]), self.dO,
+                      L.ptr(rows) if rows is not None and M else None, M, arr, len(ws), _ACT[self.activation], self.slope,
+                      L.ptr(out) if M else None, L.stream_ptr()))
+        return out
+
     def refresh_host(self, device=None):
         """Copy the device weights back into self.weights (a learner that owns the device copy -- PPOLearner -- updates it in place, and
         the host copy is only brought up to date here, on demand).  device: which copy (default: the only one there is).  Synchronises."""
@@ -166,24 +188,6 @@ class MLPPolicy(_MLPNet, ObsPolicy):
             raise TypeError(f"MLPPolicy.from_torch: needs an nn.Sequential (or an object with .logits_net), got {type(m).__name__}")
         return cls(*_sequential_layers(net, "MLPPolicy"))
 
-    def forward(self, x, rows=None, out=None):
-        """probs [M, nA] f32 on x's device: x [n, dO] f32 / f16 device tensor, rows (optional) [M] int32 gather index into x."""
-        if x.dim() != 2 or x.shape[1] != self.dO:
-            raise ValueError(f"MLPPolicy: observations of width {self.dO} expected, got shape {tuple(x.shape)}")
-        if x.dtype not in (torch.float32, torch.float16):
-            x = x.to(torch.float32)
-        x = x.contiguous()
-        if rows is not None:
-            rows = rows.to(device=x.device, dtype=torch.int32).contiguous()
-        M = int(x.shape[0]) if rows is None else int(rows.numel())
-        if out is None:
-            out = torch.empty((M, self.nA), dtype=torch.float32, device=x.device)
-        ws, arr = self._device_weights(x.device)
-        L.check(L.load().offsim_policy_mlp(L.ptr(x) if x.numel() else None, L.F32 if x.dtype == torch.float32 else L.F16, int(x.shape[0]),
-                                           self.dO, L.ptr(rows) if rows is not None and M else None, M, arr, len(ws), _ACT[self.activation],
-                                           self.slope, L.ptr(out) if M else None, L.stream_ptr()))
-        return out
-
     def row_tables(self, table, obs, next_obs):
         xn, x0 = obs_tensor(next_obs, table.device), obs_tensor(obs, table.device)
         return self.forward(xn, table.order), self.forward(x0, table.init_orig)
@@ -203,13 +207,18 @@ class RowPolicy(ObsPolicy):
             t = t.to(torch.float64)
         return t.contiguous()
 
-    def row_tables(self, table, obs=None, next_obs=None):
+    def caller_tables(self, table):
+        """(p_next, p_init) [N, nA] on the table's device, in caller row order, shapes checked, of one dtype (f32 or f64)."""
         pn, p0 = self._dev(self.p_next, table.device), self._dev(self.p_init, table.device)
-        if pn.dtype != p0.dtype:
-            pn, p0 = pn.to(torch.float64), p0.to(torch.float64)
         for name, p in (("p_next", pn), ("p_init", p0)):
             if p.dim() != 2 or p.shape[0] != table.N or p.shape[1] != table.nA:
                 raise ValueError(f"RowPolicy: {name} must be [{table.N}, {table.nA}] (one row per logged transition), got {tuple(p.shape)}")
+        if pn.dtype != p0.dtype:
+            pn, p0 = pn.to(torch.float64), p0.to(torch.float64)
+        return pn, p0
+
+    def row_tables(self, table, obs=None, next_obs=None):
+        pn, p0 = self.caller_tables(table)
         return gather_rows(pn, table.order), gather_rows(p0, table.init_orig)
 
 
@@ -217,6 +226,7 @@ class MLPValue(_MLPNet):
     """v = L_n(act(... act(L_1(obs)))) with one output unit -- spinup's MLPCritic (ppo.py:18-27: v = squeeze(v_net(obs), -1)) -- on the
     HIP forward (offsim_value_mlp), and the critic VectorPSRS.collect_ppo runs inside its kernel.  Layers, activations and limits are
     MLPPolicy's; the last layer has one output."""
+    _value = True
 
     def __init__(self, weights, activation="tanh", slope=0.01):
         super().__init__(weights, activation, slope)
@@ -231,24 +241,6 @@ class MLPValue(_MLPNet):
         if not isinstance(net, torch.nn.Sequential):
             raise TypeError(f"MLPValue.from_torch: needs an nn.Sequential (or an object with .v_net), got {type(m).__name__}")
         return cls(*_sequential_layers(net, "MLPValue"))
-
-    def forward(self, x, rows=None, out=None):
-        """v [M] f32 on x's device: x [n, dO] f32 / f16 device tensor, rows (optional) [M] int32 gather index into x."""
-        if x.dim() != 2 or x.shape[1] != self.dO:
-            raise ValueError(f"MLPValue: observations of width {self.dO} expected, got shape {tuple(x.shape)}")
-        if x.dtype not in (torch.float32, torch.float16):
-            x = x.to(torch.float32)
-        x = x.contiguous()
-        if rows is not None:
-            rows = rows.to(device=x.device, dtype=torch.int32).contiguous()
-        M = int(x.shape[0]) if rows is None else int(rows.numel())
-        if out is None:
-            out = torch.empty((M,), dtype=torch.float32, device=x.device)
-        ws, arr = self._device_weights(x.device)
-        L.check(L.load().offsim_value_mlp(L.ptr(x) if x.numel() else None, L.F32 if x.dtype == torch.float32 else L.F16, int(x.shape[0]),
-                                          self.dO, L.ptr(rows) if rows is not None and M else None, M, arr, len(ws), _ACT[self.activation],
-                                          self.slope, L.ptr(out) if M else None, L.stream_ptr()))
-        return out
 
 
 class RowValue:

@@ -26,6 +26,7 @@ import torch
 from .. import _lib as L
 from ..spaces import is_discrete
 from ..table import TransitionTable
+from .obs_policy import _ACT, MLPPolicy, MLPValue, ObsPolicy, RowPolicy, RowValue, obs_tensor
 from .psrs import BatchedPSRS
 
 try:
@@ -271,7 +272,6 @@ class VectorPSRS:
 
         Returns a PPOBatch of step-major [T, E] device tensors (flat() gives the loss inputs of ppo.py:_compute_loss_pi / _v).  The sampler
         state, observations and episode counters carry over exactly as for collect: the trajectory is collect's."""
-        from .obs_policy import MLPValue, RowValue
         from .ppo_buffer import PPOBatch, _advantages
         T = int(num_steps)
         if T < 0:
@@ -288,16 +288,7 @@ class VectorPSRS:
         pol, keep, f32 = self._collect_policy(actor, form)
         val = L.CollectValue()
         if isinstance(critic, MLPValue):
-            x_next, x_init = self._x_tables()
-            if critic.dO != x_next.shape[1]:
-                raise ValueError(f"collect_ppo: the critic takes observations of width {critic.dO}, the log's have {x_next.shape[1]}")
-            x_start = self.obs.reshape(E, -1).to(x_next.dtype).contiguous()
-            ws, arr = critic._device_weights(dev)
-            val.form, val.n_layers, val.layers_host = L.VALUE_MLP, len(ws), C.cast(arr, C.POINTER(L.MLPLayer))
-            val.activation, val.slope = _mlp_act(critic), critic.slope
-            val.x_dtype, val.dO = (L.F32 if x_next.dtype == torch.float32 else L.F16), critic.dO
-            val.x_start, val.x_next, val.x_init = L.ptr(x_start), L.ptr(x_next), L.ptr(x_init)
-            keep += [x_start, x_next, x_init, ws]
+            keep += self._collect_mlp(val, L.VALUE_MLP, critic, "collect_ppo: the critic")
         elif isinstance(critic, RowValue):
             vn, v0 = critic.tables(t.N, dev)
             val.form, val.v_next, val.v_init = L.VALUE_ROWS, L.ptr(vn), L.ptr(v0)
@@ -319,7 +310,6 @@ class VectorPSRS:
 
     def _collect_policy(self, policy, form):
         """offsim_collect_policy for collect / collect_ppo: (struct, tensors to keep alive, whether p_new is compared in f32)."""
-        from .obs_policy import MLPPolicy, ObsPolicy
         if form == "auto":
             form = "mlp" if isinstance(policy, MLPPolicy) else "rows" if isinstance(policy, ObsPolicy) else "tabular"
         t = self.table
@@ -327,16 +317,7 @@ class VectorPSRS:
         if form == "mlp":
             if not isinstance(policy, MLPPolicy):
                 raise TypeError(f"collect: form='mlp' needs an MLPPolicy, got {type(policy).__name__}")
-            x_next, x_init = self._x_tables()
-            if policy.dO != x_next.shape[1]:
-                raise ValueError(f"collect: the network takes observations of width {policy.dO}, the log's have {x_next.shape[1]}")
-            x_start = self.obs.reshape(self.num_envs, -1).to(x_next.dtype).contiguous()
-            ws, arr = policy._device_weights(t.device)
-            pol.form, pol.n_layers, pol.layers_host = L.COLLECT_MLP, len(ws), C.cast(arr, C.POINTER(L.MLPLayer))
-            pol.activation, pol.slope = _mlp_act(policy), policy.slope
-            pol.x_dtype, pol.dO = (L.F32 if x_next.dtype == torch.float32 else L.F16), policy.dO
-            pol.x_start, pol.x_next, pol.x_init = L.ptr(x_start), L.ptr(x_next), L.ptr(x_init)
-            keep += [x_start, x_next, x_init, ws]
+            keep += self._collect_mlp(pol, L.COLLECT_MLP, policy, "collect: the network")
             f32 = t.p_log.dtype == torch.float32
         elif form == "rows":
             if not isinstance(policy, ObsPolicy):
@@ -365,11 +346,24 @@ class VectorPSRS:
             raise ValueError(f"collect: form must be 'auto', 'mlp', 'rows' or 'tabular', got {form!r}")
         return pol, keep, f32
 
+    def _collect_mlp(self, c, form, net, what):
+        """The MLP form of an offsim_collect_policy / offsim_collect_value `c` from the _MLPNet `net` (`what` names it in the width
+        error); returns the tensors to keep alive."""
+        x_next, x_init = self._x_tables()
+        if net.dO != x_next.shape[1]:
+            raise ValueError(f"{what} takes observations of width {net.dO}, the log's have {x_next.shape[1]}")
+        x_start = self.obs.reshape(self.num_envs, -1).to(x_next.dtype).contiguous()
+        ws, arr = net._device_weights(self.table.device)
+        c.form, c.n_layers, c.layers_host = form, len(ws), C.cast(arr, C.POINTER(L.MLPLayer))
+        c.activation, c.slope = _ACT[net.activation], net.slope
+        c.x_dtype, c.dO = (L.F32 if x_next.dtype == torch.float32 else L.F16), net.dO
+        c.x_start, c.x_next, c.x_init = L.ptr(x_start), L.ptr(x_next), L.ptr(x_init)
+        return [x_start, x_next, x_init, ws]
+
     def _x_tables(self):
         """The log's observations as the in-kernel network reads them: next_obs / obs [N, dO], f16 kept, anything else f32 (MLPPolicy.forward's
         rule), made once."""
         if self._x_rows is None:
-            from .obs_policy import obs_tensor
             dev = self.table.device
             self._x_rows = (obs_tensor(self._next_obs, dev), obs_tensor(self._obs, dev))
         return self._x_rows
@@ -377,29 +371,19 @@ class VectorPSRS:
     def _caller_tables(self, policy):
         """p_next [N, nA] / p_init [N, nA] in CALLER row order: the policy at next_obs / obs of every logged row (offsim_collect_policy's
         ROWS form; only initial rows of p_init are read)."""
-        from .obs_policy import RowPolicy
         t = self.table
         if isinstance(policy, RowPolicy):
-            pn, p0 = policy._dev(policy.p_next, t.device), policy._dev(policy.p_init, t.device)
-            for name, p in (("p_next", pn), ("p_init", p0)):
-                if p.dim() != 2 or p.shape[0] != t.N or p.shape[1] != t.nA:
-                    raise ValueError(f"RowPolicy: {name} must be [{t.N}, {t.nA}] (one row per logged transition), got {tuple(p.shape)}")
-        else:
-            pg, pk = policy.row_tables(t, self._obs, self._next_obs)  # grouped order / initial-row order
-            pn = torch.zeros((t.N, t.nA), dtype=pg.dtype, device=t.device)
-            p0 = torch.zeros((t.N, t.nA), dtype=pk.dtype, device=t.device)
-            if t.N:
-                pn[t.order.to(torch.int64)] = pg
-            if t.N0:
-                p0[t.init_orig.to(torch.int64)] = pk
+            return policy.caller_tables(t)
+        pg, pk = policy.row_tables(t, self._obs, self._next_obs)  # grouped order / initial-row order
+        pn = torch.zeros((t.N, t.nA), dtype=pg.dtype, device=t.device)
+        p0 = torch.zeros((t.N, t.nA), dtype=pk.dtype, device=t.device)
+        if t.N:
+            pn[t.order.to(torch.int64)] = pg
+        if t.N0:
+            p0[t.init_orig.to(torch.int64)] = pk
         if pn.dtype != p0.dtype:
             pn, p0 = pn.to(torch.float64), p0.to(torch.float64)
         return pn.contiguous(), p0.contiguous()
 
 
 Collected = namedtuple("Collected", "obs probs row action reward next_obs terminated truncated reset alive final_obs status")
-
-
-def _mlp_act(policy):
-    from .obs_policy import _ACT
-    return _ACT[policy.activation]

@@ -220,6 +220,91 @@ def test_ppo_grad_and_update_validation_before_any_hip_call():
     assert upd(b=batch(M=3), trace=None) == L.EINVAL and upd(b=batch(M=3), stats=None) == L.EINVAL
 
 
+# One table of bad networks through every entry point that takes a network: pmlp_describe (csrc/policy_mlp.hpp) is the one validator, so
+# each refusal must come back with OFFSIM_EINVAL, that entry point's prefix and the same key word, before any HIP call (fake pointers).
+# A case: (what differs from the good network 4 -> 8 -> 2 | 1, the key word for an actor, for a critic (None: a good actor, not run)).
+_BAD_NETS = {
+    "five_layers": (dict(sizes=[4, 8, 8, 8, 8, None]), b"1 to 4", b"1 to 4"),
+    "null_W": (dict(null_w=1), b"W is NULL", b"W is NULL"),
+    "no_chain": (dict(sizes=[4, 8, None], in1=9), b"chain", b"chain"),
+    "hidden_257": (dict(sizes=[4, 257, None]), b"hidden", b"hidden"),
+    "outputs_17": (dict(sizes=[4, 8, 17]), b"16 actions", b"one output"),
+    "critic_2_outputs": (dict(sizes=[4, 8, 2]), None, b"one output"),
+    "activation_9": (dict(act=9), b"activation", b"activation"),
+    "x_dtype_f64": (dict(x_dtype="F64"), b"x_dtype", b"x_dtype"),
+    "dO_0": (dict(sizes=[0, 8, None], dO=0), b"observation width", b"observation width"),
+    "dO_129": (dict(sizes=[129, 8, None], dO=129), b"observation width", b"observation width"),
+}
+# entry point -> (error prefix, whether its network is a critic)
+_NET_ENTRIES = {
+    "policy_mlp": (b"policy_mlp: ", False), "value_mlp": (b"value_mlp: ", True),
+    "vector_collect": (b"vector_collect: ", False),
+    "vector_collect_ppo_actor": (b"vector_collect_ppo: ", False), "vector_collect_ppo_critic": (b"vector_collect_ppo critic: ", True),
+    "ppo_grad_actor": (b"ppo_grad: ", False), "ppo_grad_critic": (b"ppo_grad: ", True),
+    "ppo_update_actor": (b"ppo_update: ", False), "ppo_update_critic": (b"ppo_update: ", True),
+}
+
+
+def _call_with_net(entry, critic, sizes=(4, 8, None), act=1, x_dtype="F32", dO=4, null_w=None, in1=None):
+    """The entry point's return code for a network of these sizes (None: the good last width, 1 for a critic, 2 for an actor)."""
+    from rl_offline_simulation_amd import _lib as L
+    from test_collect import _args
+    lib, f = L.load(), 0x1000
+    sizes = [(1 if critic else 2) if w is None else w for w in sizes]
+    arr = _layers(sizes)
+    if null_w is not None:
+        arr[null_w].W = None
+    if in1 is not None:
+        setattr(arr[1], "in", in1)
+    n, xd, lp = len(sizes) - 1, getattr(L, x_dtype), ctypes.cast(arr, ctypes.POINTER(L.MLPLayer))
+    if entry in ("policy_mlp", "value_mlp"):
+        return getattr(lib, "offsim_" + entry)(f, xd, 10, dO, None, 0, arr, n, act, 0.01, f, None)
+    if entry.startswith("ppo_"):
+        net = L.PPONet(n_layers=n, activation=act, layers_host=lp, slope=0.01)
+        b = L.PPOBatchC(obs=f, x_dtype=xd, dO=dO, act=f, adv=f, logp=f, ret=f, valid=None, M=0)
+        kind = L.PPO_CRITIC if critic else L.PPO_ACTOR
+        if entry.startswith("ppo_grad"):
+            return lib.offsim_ppo_grad(ctypes.byref(net), kind, ctypes.byref(b), 0.2, f, f, f, None)
+        o = L.PPOAdam(m=f, v=f, t=f, lr=1e-3)
+        return lib.offsim_ppo_update(ctypes.byref(net), kind, ctypes.byref(b), 0.2, 0.01, 3, ctypes.byref(o), f, f, f, None)
+    t, ro, pol, st, out, _ = _args()  # a good MLP actor (4 -> 8 -> 2, the table's nA = 2)
+    bad = dict(n_layers=n, layers_host=lp, activation=act, x_dtype=xd, dO=dO)
+    if entry == "vector_collect_ppo_critic":
+        val = L.CollectValue(form=L.VALUE_MLP, x_start=f, x_next=f, x_init=f, **bad)
+    else:
+        for k, v in bad.items():
+            setattr(pol, k, v)
+        good = _layers([4, 8, 1])
+        val = L.CollectValue(form=L.VALUE_MLP, n_layers=2, layers_host=ctypes.cast(good, ctypes.POINTER(L.MLPLayer)), activation=1, x_dtype=xd, dO=4,
+                             x_start=f, x_next=f, x_init=f)
+    if entry == "vector_collect":
+        return lib.offsim_vector_collect(ctypes.byref(t), ctypes.byref(ro), ctypes.byref(pol), L.PROB_F64, L.REJECT_DEFAULT, 0, 0, ctypes.byref(st),
+                                         ctypes.byref(out), None)
+    ppo = L.CollectPPOOut(value=f, logp=f, final_value=f)
+    return lib.offsim_vector_collect_ppo(ctypes.byref(t), ctypes.byref(ro), ctypes.byref(pol), ctypes.byref(val), L.PROB_F64, L.REJECT_DEFAULT, 0, 0,
+                                         ctypes.byref(st), ctypes.byref(out), ctypes.byref(ppo), None)
+
+
+@pytest.mark.parametrize("entry", sorted(_NET_ENTRIES))
+def test_every_entry_point_accepts_the_good_network(entry):
+    from rl_offline_simulation_amd import _lib as L
+    assert _call_with_net(entry, _NET_ENTRIES[entry][1]) == L.OK, L.load().offsim_last_error()
+
+
+@pytest.mark.parametrize("entry,case", [(e, c) for e in sorted(_NET_ENTRIES) for c in sorted(_BAD_NETS)
+                                        if _BAD_NETS[c][2 if _NET_ENTRIES[e][1] else 1] is not None])
+def test_bad_network_refused_alike_by_every_entry_point(entry, case):
+    from rl_offline_simulation_amd import _lib as L
+    prefix, critic = _NET_ENTRIES[entry]
+    kw, word_actor, word_critic = _BAD_NETS[case]
+    word = word_critic if critic else word_actor
+    rc = _call_with_net(entry, critic, **kw)
+    err = L.load().offsim_last_error()
+    assert rc == L.EINVAL, (rc, err)
+    assert err.startswith(prefix), err
+    assert word in err, err
+
+
 def test_ppo_update_float_cap_and_work_size():
     from rl_offline_simulation_amd import _lib as L
     lib = L.load()
