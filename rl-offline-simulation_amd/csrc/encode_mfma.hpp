@@ -103,7 +103,7 @@ __global__ void __launch_bounds__(256) k_encode_mlp_mfma(const XT *__restrict__ 
             }
         // ---- bias, optional logits, argmax over z (first maximal index, as torch.max(dim=1)) ----
         float bv = -__builtin_inff();
-        int bz = 0x7fffffff;
+        int bz = 0;  // (a row without a logit above -inf -- all NaN -- encodes as 0, as in k_encode_mlp)
 #pragma unroll
         for (int zt = 0; zt < ZT; zt++)
 #pragma unroll
@@ -137,7 +137,8 @@ __global__ void __launch_bounds__(256) k_encode_mlp_mfma(const XT *__restrict__ 
 // W2[32 zt + col][32 t + cd_row(g, hi)].  So each lane keeps its HT half + ZT HT 16 weights (192 at 128-64-50) and the biases in
 // registers for the whole launch -- one wavefront per SIMD has 512 of them --, an observation row's half (k in [hi half, hi half +
 // half): contiguous) arrives as a few 16-byte loads issued a tile ahead, and the loop is MFMAs with conversions in their shadow.
-// The order of the k summation is the kernel's above, so the logits are the same bit for bit.
+// The order of the k summation is the kernel's above, but the accumulators start from the bias where the kernel above adds it last, so the
+// logits agree to rounding, not bit for bit (measured: most differ in the last bits, by at most 8e-8 of the sum of absolute terms).
 template <typename XT, int DO, int HT, int ZT, int WPE /* wavefronts per SIMD the registers are budgeted for */>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     k_encode_mlp_mfma_reg(const XT *__restrict__ x, int64_t N, const float *__restrict__ W1, const float *__restrict__ b1, int H,
@@ -268,7 +269,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, W
             }
         // ---- optional logits, argmax over z (first maximal index, as torch.max(dim=1): the z of a lane are walked downwards, >= wins) ----
         float bv = -__builtin_inff();
-        int bz = 0x7fffffff;
+        int bz = 0;  // (a row without a logit above -inf -- all NaN -- encodes as 0, as in k_encode_mlp)
 #pragma unroll
         for (int zt = ZT - 1; zt >= 0; zt--)
 #pragma unroll
@@ -530,7 +531,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, W
             }
         // ---- optional logits, argmax over z (first maximal index, as torch.max(dim=1)) ----
         float bv = -__builtin_inff();
-        int bz = 0x7fffffff;
+        int bz = 0;  // (a row without a logit above -inf -- all NaN -- encodes as 0, as in k_encode_mlp)
 #pragma unroll
         for (int zt = ZT - 1; zt >= 0; zt--)
 #pragma unroll

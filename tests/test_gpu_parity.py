@@ -312,7 +312,8 @@ def test_drop_in_facade(gpu):
 
 def test_mlp_encoder_shapes_vs_oracle(gpu):
     """MFMA encoder against the CPU oracle on shapes beyond the fixtures: odd input width, padded hidden/latent sizes,
-    fp16 observations (config C5), N not a multiple of 32, and a shape that takes the VALU fallback (H = 160 > 128 is refused)."""
+    fp16 observations (config C5), N not a multiple of 32, and a shape that takes the VALU fallback (H = 96: three hidden tiles, which the
+    MFMA kernels are not instantiated for; the refusals are in tests/test_gpu_encoder_matrix.py)."""
     from oracle import oracle as O
     from rl_offline_simulation_amd.encoders import HOMEREncoder
     g = np.random.default_rng(0)
