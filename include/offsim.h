@@ -135,6 +135,15 @@ int offsim_gather_rows(const void *src, const int32_t *order, int64_t N, int32_t
 /* np.random.default_rng(seed) for R seeds: SeedSequence -> PCG64 (psrs.py:20).  seeds, out on device. */
 int offsim_seed_streams(const uint64_t *seeds, int32_t R, uint64_t *rng_out /*[R,4]*/, void *stream);
 
+/* Debug view of where a chain of the sampler reset starts its draw stream (csrc/shuffle_wave.hpp; the jump tables of
+ * csrc/pcg64_jump_tab.hpp).  For every {seed, count, g in {0, 1}}, in that order, OFFSIM_PCG_PROBE_WORDS uint64: the PCG64 states
+ * (hi, lo) of the 64 lanes of G wavefront g -- lane l: the state q + 64 g + l + 1 steps behind default_rng(seed)'s, q = count (halve = 0)
+ * or count >> 1 (halve != 0: count is a number of 32-bit draws) -- then the jump by 128 steps as {mult hi, lo, plus hi, lo}.
+ * out_tab: from the tables, as the chains compute it; out_ref: from the squaring loop.  All pointers on the device. */
+#define OFFSIM_PCG_PROBE_WORDS 132
+int offsim_pcg_jump_probe(const uint64_t *seeds, int32_t n_seeds, const uint32_t *counts, int32_t n_counts, int32_t halve,
+                          uint64_t *out_tab /*[n_seeds,n_counts,2,132]*/, uint64_t *out_ref, void *stream);
+
 /* PSRS.reset_sampler(seed) queue shuffles (psrs.py:22-23,29-30) for n_perm seeds at once:
  * every state's queue and the init queue get a backward Fisher-Yates driven by a FRESH
  * default_rng(seed).  perm_out [n_perm,N] holds grouped rows, init_perm_out [n_perm,N0] indices. */

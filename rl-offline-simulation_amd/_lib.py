@@ -162,6 +162,7 @@ SIGNATURES = {
     "offsim_group_by_state": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "offsim_gather_rows": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp]),
     "offsim_seed_streams": (C.c_int, [_vp, _i32, _vp, _vp]),
+    "offsim_pcg_jump_probe": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
     "offsim_shuffle_queues": (C.c_int, [C.POINTER(Table), _vp, _i32, _vp, _vp, _vp]),
     "offsim_env_reset": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), _vp, _vp, _vp]),
     "offsim_env_set_state": (C.c_int, [C.POINTER(Rollouts), _vp, _vp, _vp]),

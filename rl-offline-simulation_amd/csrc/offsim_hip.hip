@@ -228,6 +228,41 @@ extern "C" int offsim_seed_streams(const uint64_t *seeds, int32_t R, uint64_t *r
     return OFFSIM_OK;
 }
 
+// What a chain of the sampler reset computes where it starts (shuffle_wave.hpp, chain_start), laid open for the tests: one wavefront per
+// {seed, count, G wavefront g}, the 64 lane states and the block jump from the build-time tables (pcg64_jump_tab.hpp) into out_tab and
+// the same from pcg_jump's squaring loop into out_ref.  halve != 0: counts are 32-bit draw counts as a cut launch finds them (the
+// stream position is count >> 1), otherwise positions in 64-bit outputs.
+__global__ void __launch_bounds__(64) k_pcg_jump_probe(const uint64_t *seeds, const uint32_t *counts, int32_t n_counts, int32_t halve,
+                                                       uint64_t *out_tab, uint64_t *out_ref) {
+    const uint32_t lane = threadIdx.x, g = blockIdx.x & 1u, ci = (blockIdx.x >> 1) % (uint32_t)n_counts, si = (blockIdx.x >> 1) / (uint32_t)n_counts;
+    const PcgJumpRow lane_row = pcg_lane_row(64u * g + lane + 1u);
+    const uint32_t q = sh_rfl(halve ? counts[ci] >> 1 : counts[ci]);
+    const PcgInit p = pcg_seed(seeds[si]);
+    const U128 st = pcg_chain_start(p, lane_row, q);
+    const Jump j128 = pcg_jump_lane(p.inc, 128u);
+    const U128 st_ref = pcg_apply(pcg_jump(p.inc, (uint64_t)q + 64ull * g + (uint64_t)lane + 1), p.state);
+    const Jump j_ref = pcg_jump(p.inc, 128);
+    uint64_t *ot = out_tab + (int64_t)blockIdx.x * OFFSIM_PCG_PROBE_WORDS, *orf = out_ref + (int64_t)blockIdx.x * OFFSIM_PCG_PROBE_WORDS;
+    ot[2u * lane] = st.hi;
+    ot[2u * lane + 1u] = st.lo;
+    orf[2u * lane] = st_ref.hi;
+    orf[2u * lane + 1u] = st_ref.lo;
+    if (lane == 0) {
+        ot[128] = j128.mult.hi, ot[129] = j128.mult.lo, ot[130] = j128.plus.hi, ot[131] = j128.plus.lo;
+        orf[128] = j_ref.mult.hi, orf[129] = j_ref.mult.lo, orf[130] = j_ref.plus.hi, orf[131] = j_ref.plus.lo;
+    }
+}
+extern "C" int offsim_pcg_jump_probe(const uint64_t *seeds, int32_t n_seeds, const uint32_t *counts, int32_t n_counts, int32_t halve,
+                                     uint64_t *out_tab, uint64_t *out_ref, void *stream) {
+    if (n_seeds < 0 || n_counts < 0 || !seeds || !counts || !out_tab || !out_ref) return fail(OFFSIM_EINVAL, "pcg_jump_probe: bad argument%s");
+    if ((int64_t)n_seeds * n_counts > (1 << 20)) return fail(OFFSIM_EINVAL, "pcg_jump_probe: at most 2^20 {seed, count} pairs%s");
+    if (n_seeds == 0 || n_counts == 0) return OFFSIM_OK;
+    hipLaunchKernelGGL(k_pcg_jump_probe, dim3(2u * (unsigned)n_seeds * (unsigned)n_counts), dim3(64), 0, (hipStream_t)stream, seeds, counts, n_counts, halve,
+                       out_tab, out_ref);
+    LAUNCH_CHECK();
+    return OFFSIM_OK;
+}
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per device and sticks: set once per (kernel, device), not per launch
 // (it sits on the single-step latency path otherwise)
 static hipError_t allow_big_lds_fn(const void *fn, int bytes) {

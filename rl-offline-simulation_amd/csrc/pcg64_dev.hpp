@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pcg64_jump_tab.hpp"
+
 namespace offsim {
 
 struct U128 {
@@ -71,6 +73,28 @@ __device__ inline Jump pcg_jump(U128 inc, uint64_t delta) {
 }
 __device__ __forceinline__ U128 pcg_apply(Jump j, U128 s) { return add128(mul128(j.mult, s), j.plus); }
 
+// The same maps from the build-time tables (pcg64_jump_tab.hpp): no squaring loop.  pcg_jump stays for every other caller and as the
+// reference these are tested against (offsim_pcg_jump_probe).
+// pcg_lane_row(k): the row of a jump by k = 1 .. 128 -- a load that depends on k alone, so it can be issued long before inc is known
+__device__ __forceinline__ PcgJumpRow pcg_lane_row(uint32_t k) { return g_pcg_lane_tab.row[k - 1u]; }
+__device__ __forceinline__ Jump pcg_jump_from_row(PcgJumpRow w, U128 inc) {
+    Jump j;
+    j.mult = u128(w.a_hi, w.a_lo);
+    j.plus = mul128(u128(w.s_hi, w.s_lo), inc);
+    return j;
+}
+__device__ __forceinline__ Jump pcg_jump_lane(U128 inc, uint32_t k) { return pcg_jump_from_row(pcg_lane_row(k), inc); }
+// the state q steps on: one table row per non-zero 6-bit digit of q.  With q the same in every lane (a chain's draw count) the digits,
+// the rows' addresses and the arithmetic are wave-uniform: scalar loads and the scalar ALU.
+__device__ __forceinline__ U128 pcg_apply_count(U128 state, U128 inc, uint32_t q) {
+#pragma unroll
+    for (uint32_t lv = 0; lv < OFFSIM_PCG_COUNT_LEVELS; lv++) {
+        const uint32_t d = (q >> (OFFSIM_PCG_COUNT_BITS * lv)) & (uint32_t)OFFSIM_PCG_COUNT_DIGITS;
+        if (d != 0u) state = pcg_apply(pcg_jump_from_row(g_pcg_count_tab.row[lv * OFFSIM_PCG_COUNT_DIGITS + d - 1u], inc), state);
+    }
+    return state;
+}
+
 // SeedSequence(seed).generate_state(4, uint64) followed by PCG64 seeding.
 struct PcgInit {
     U128 state, inc;
@@ -127,6 +151,12 @@ __device__ inline PcgInit pcg_seed(uint64_t seed) {
     s = pcg_step(s, r.inc);
     r.state = s;
     return r;
+}
+
+// The state behind a chain's first output in one lane: output k = 1 .. 128 of the block that starts q 64-bit outputs into the stream
+// (lane_row = pcg_lane_row(k)).  The jump by q first (wave-uniform), then the lane's own.
+__device__ __forceinline__ U128 pcg_chain_start(PcgInit p, PcgJumpRow lane_row, uint32_t q) {
+    return pcg_apply(pcg_jump_from_row(lane_row, p.inc), pcg_apply_count(p.state, p.inc, q));
 }
 
 // Sequential generator with NumPy's buffered 32-bit halves (next_uint32): used by the shuffles.

@@ -163,8 +163,8 @@ __global__ void __launch_bounds__(256)
                 // ---------------- G (two wavefronts, alternate blocks of 128 draws), as in shuffle_wave.hpp
                 const uint32_t g = wave == 0 ? 0u : 1u;
                 const PcgInit p = pcg_seed(seeds[r]);
-                const Jump j128 = pcg_jump(p.inc, 128);
-                U128 st = pcg_apply(pcg_jump(p.inc, 64ull * g + (uint64_t)lane + 1), p.state);
+                const Jump j128 = pcg_jump_lane(p.inc, 128u);  // (the build-time tables of pcg64_jump_tab.hpp: no squaring loop)
+                U128 st = pcg_apply(pcg_jump_lane(p.inc, 64u * g + (uint32_t)lane + 1u), p.state);
                 uint32_t blk = g, done_blocks = 0, cpub = 0;
                 for (;;) {
                     bool stop = false;

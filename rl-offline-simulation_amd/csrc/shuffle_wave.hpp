@@ -103,8 +103,10 @@ __device__ __forceinline__ int sh_rank(uint64_t m) {  // set bits of m in front 
 // every 16 bytes take a fifth dword (the first of the next 16) and go through v_alignbyte.  Reads stay inside the stream: the dword in
 // front of an odd start belongs to the entry before this chain's (the buffer itself is dword-aligned), the fifth dword of the last 16 bytes
 // ends with entry TOP, and every cut chain has more than TOP rows.
-template <uint32_t TOP>
-__device__ __forceinline__ void shuf_fill_from_stream(lds_vu16 *x16, const uint16_t *lc) {
+// mid() runs between the loads and the stores: work that needs nothing of the segment (the G wavefronts' chain start) goes where the
+// wavefront would otherwise only wait for HBM.
+template <uint32_t TOP, class MID>
+__device__ __forceinline__ void shuf_fill_from_stream(lds_vu16 *x16, const uint16_t *lc, MID mid) {
     typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     constexpr uint32_t VEC = TOP / 8u, J = VEC ? (VEC + 255u) / 256u : 1u;  // 16-byte pieces of the segment, per thread (TOP = 0: never called)
@@ -113,17 +115,20 @@ __device__ __forceinline__ void shuf_fill_from_stream(lds_vu16 *x16, const uint1
     const uint32_t *src = (const uint32_t *)(lc - (odd ? 1 : 0));
     __attribute__((address_space(3))) u32x4 *dst = (__attribute__((address_space(3))) u32x4 *)x16;
     u32x4 w[J];
-    if (odd) {
-        uint32_t e[J];
+    uint32_t e[J];
 #pragma unroll
-        for (uint32_t j = 0; j < J; j++) {
-            const uint32_t q = threadIdx.x + 256u * j;
-            if (VEC % 256u == 0u || q < VEC) {
-                w[j] = *(const u32x4_a4 *)(src + 4u * q);
-                e[j] = src[4u * q + 4u];
-            }
+    for (uint32_t j = 0; j < J; j++) {
+        const uint32_t q = threadIdx.x + 256u * j;
+        e[j] = 0u;
+        if (VEC % 256u == 0u || q < VEC) {
+            w[j] = *(const u32x4_a4 *)(src + 4u * q);
+            if (odd) e[j] = src[4u * q + 4u];
         }
-        __builtin_amdgcn_sched_barrier(0);  // (every load in front of the first use: no wait between the loads, whatever the register count)
+    }
+    __builtin_amdgcn_sched_barrier(0);  // (every load in front of the first use: no wait between the loads, whatever the register count)
+    mid();
+    __builtin_amdgcn_sched_barrier(0);
+    if (odd) {
 #pragma unroll
         for (uint32_t j = 0; j < J; j++) {
             const uint32_t q = threadIdx.x + 256u * j;
@@ -137,12 +142,6 @@ __device__ __forceinline__ void shuf_fill_from_stream(lds_vu16 *x16, const uint1
             }
         }
     } else {
-#pragma unroll
-        for (uint32_t j = 0; j < J; j++) {
-            const uint32_t q = threadIdx.x + 256u * j;
-            if (VEC % 256u == 0u || q < VEC) w[j] = *(const u32x4_a4 *)(src + 4u * q);
-        }
-        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (uint32_t j = 0; j < J; j++) {
             const uint32_t q = threadIdx.x + 256u * j;
@@ -260,14 +259,36 @@ __global__ void __launch_bounds__(256)
 
     if (threadIdx.x < 16u) ctrl[threadIdx.x] = threadIdx.x == SH_ATOP ? n - 1u : (threadIdx.x == SH_EM0 || threadIdx.x == SH_EM1) ? n_chunks : 0u;
     if (threadIdx.x < 64u) win[threadIdx.x] = 0;
+    // Where the chain's random stream starts, in the two G wavefronts: lane l of G wavefront g owns 64-bit output 64 g + l + 1 behind the
+    // c_start 32-bit draws the launches before this one used.  Nothing of it depends on the segment, and the classifier cannot start
+    // before G0's first block, so it runs in front of the barrier that closes the fill, while the fill's loads are on their way.  The
+    // lane's table row is requested before the fill's loads (vector loads return in order: the arithmetic then waits for the row, not for
+    // the fill); the seed and the draw count are scalar loads, which return in any order and are waited for together, so they go BEHIND
+    // the fill's loads -- in front they held those back by an HBM round trip.  Seed, count and the jump by the count are the same in all
+    // 64 lanes (scalar registers, scalar ALU); per lane: one table row and three 128-bit multiplies.
+    const bool is_g = wave == 0 || wave == 3;
+    const uint32_t g = wave == 0 ? 0u : 1u;
     uint32_t c_start = 0;  // 32-bit draws the launches before this one used
+    PcgJumpRow lane_row = {0, 0, 0, 0};
+    if (is_g) lane_row = pcg_lane_row(64u * g + (uint32_t)lane + 1u);
+    U128 st = u128(0, 0);
+    Jump j128;
+    j128.mult = j128.plus = u128(0, 0);
+    auto chain_start = [&]() __attribute__((always_inline)) {
+        if (FROM_STREAM) c_start = sh_rfl(dg[0]);
+        if (!is_g) return;
+        const PcgInit p = pcg_seed(seeds[r]);
+        j128 = pcg_jump_lane(p.inc, 128u);
+        st = pcg_chain_start(p, lane_row, c_start >> 1);
+    };
     if (FROM_STREAM) {  // the low positions as the previous launch left them, and its draw count
-        c_start = dg[0];
-        shuf_fill_from_stream<TOP>(x16, lc);
+        shuf_fill_from_stream<TOP>(x16, lc, chain_start);
     } else if (LDS16) {  // identity, two entries per lane and store
+        chain_start();
         __attribute__((address_space(3))) uint32_t *xw = (__attribute__((address_space(3))) uint32_t *)x16;
         for (uint32_t k = threadIdx.x; 2u * k < n; k += 256u) xw[k] = ((2u * k + 1u) << 16) | (2u * k);
     } else {
+        chain_start();
         for (uint32_t k = threadIdx.x; k < n; k += 256u) xg[k] = base_val + k;
     }
     __syncthreads();
@@ -297,10 +318,7 @@ __global__ void __launch_bounds__(256)
             // ---------------- G (two wavefronts, alternate blocks of 128 draws): raw draws.  In block k lane l owns 64-bit
             // output 64*k + l = 32-bit draws 2*(64*k + l) and +1 (next_uint32 hands out the low half first, then the
             // buffered high half).
-            const uint32_t g = wave == 0 ? 0u : 1u;
-            const PcgInit p = pcg_seed(seeds[r]);
-            const Jump j128 = pcg_jump(p.inc, 128);
-            U128 st = pcg_apply(pcg_jump(p.inc, (uint64_t)(c_start >> 1) + 64ull * g + (uint64_t)lane + 1), p.state);
+            // (st = the state of this lane's first output, j128 = the jump from block to block: chain_start above)
             uint32_t blk = g, done_blocks = 0, cpub = 0;  // blk = index of the block this wavefront writes next
             // Keyed form: a step of the chain never touches a position above its own, so the order is final from the top down
             // while the chain still runs.  The two G wavefronts are ahead of C most of the time; while they wait for room in
