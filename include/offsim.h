@@ -302,7 +302,8 @@ int offsim_eval_mc_rows_policy(const offsim_table *t, offsim_rollouts *ro, const
  * (r, s', done) and the accepted x-row gives x'.  ts / rs: table grouped by s and its rollout state (rng, cursors,
  * permutations, cur_slot = s); tx / rx: table grouped by x (only z_next and orig_idx are read) and its cursors,
  * permutations and cur_slot = x.  Build, shuffle and reset each with the ordinary entry points (same seeds).
- * out_row_s / out_row_x: caller-buffer rows of the accepted s- and x-elements (-1 on None / KeyError). */
+ * out_row_s / out_row_x: caller-buffer rows of the accepted s- and x-elements (-1 on None / KeyError).
+ * The draws are rs's stream, PCG64 only: rs->rng_kind = OFFSIM_STREAM_PHILOX is refused with OFFSIM_EUNSUPPORTED, nothing is stepped. */
 int offsim_step_exo(const offsim_table *ts, const offsim_table *tx, offsim_rollouts *rs, offsim_rollouts *rx,
                     const void *p_new, int32_t prob_mode, int32_t *out_row_s, int32_t *out_row_x, int32_t *out_status,
                     uint32_t *out_popped, void *stream);

@@ -354,8 +354,7 @@ static int collect_prepare(const char *who, const offsim_table *t, offsim_rollou
     int rc = check_table(t);
     if (rc) return rc;
     if (!ro || ro->R < 0 || !pol || !st || !out || T < 0 || max_episode_steps < 0) return fail(OFFSIM_EINVAL, "vector_collect: bad argument%s");
-    if (prob_mode != OFFSIM_PROB_F32 && prob_mode != OFFSIM_PROB_F64) return fail(OFFSIM_EINVAL, "vector_collect: bad prob_mode%s");
-    if (prob_mode == OFFSIM_PROB_F32 && t->plog_dtype != OFFSIM_F32) return fail(OFFSIM_EINVAL, "vector_collect: OFFSIM_PROB_F32 needs an f32 p_log%s");
+    if ((rc = check_prob_mode("vector_collect", t, prob_mode))) return rc;
     if (reject_mode != OFFSIM_REJECT_DEFAULT && reject_mode != OFFSIM_REJECT_NEVER) return fail(OFFSIM_EINVAL, "vector_collect: bad reject_mode%s");
     if (!st->ep_t || !st->obs_row || !st->alive || !st->obs || st->obs_bytes <= 0 || (t->N > 0 && (!st->obs_next || !st->obs_init)))
         return fail(OFFSIM_EINVAL, "vector_collect: bad state (ep_t, obs_row, alive, obs, obs_next, obs_init, obs_bytes)%s");
@@ -405,24 +404,20 @@ static int collect_launch(const offsim_table *t, offsim_rollouts *ro, int32_t fo
         if (x_dtype == OFFSIM_F32) LAUNCH_COLLECT(PL, PROB, FORM, float);                                         \
         else LAUNCH_COLLECT(PL, PROB, FORM, __half);                                                              \
     } while (0)
-#define LAUNCH_FORM(PL, PROB)                                                                                     \
-    do {                                                                                                          \
-        if (form == OFFSIM_COLLECT_MLP) LAUNCH_FORM_XT(PL, PROB, OFFSIM_COLLECT_MLP);                             \
-        else if constexpr (VF == OFFSIM_VALUE_MLP) {                                                              \
-            if (form == OFFSIM_COLLECT_ROWS) LAUNCH_FORM_XT(PL, PROB, OFFSIM_COLLECT_ROWS);                       \
-            else LAUNCH_FORM_XT(PL, PROB, OFFSIM_COLLECT_TABULAR);                                                \
-        } else if (form == OFFSIM_COLLECT_ROWS) LAUNCH_COLLECT(PL, PROB, OFFSIM_COLLECT_ROWS, float);             \
-        else LAUNCH_COLLECT(PL, PROB, OFFSIM_COLLECT_TABULAR, float);                                             \
-    } while (0)
-    if (prob_mode == OFFSIM_PROB_F32) LAUNCH_FORM(float, float);
-    else if (t->plog_dtype == OFFSIM_F32) LAUNCH_FORM(float, double);
-    else if (t->plog_dtype == OFFSIM_F64) LAUNCH_FORM(double, double);
-    else LAUNCH_FORM(__half, double);
-#undef LAUNCH_FORM
+    return with_plog_prob(t, prob_mode, [&](auto pl, auto prob) -> int {
+        using PL = decltype(pl);
+        using PROB = decltype(prob);
+        if (form == OFFSIM_COLLECT_MLP) LAUNCH_FORM_XT(PL, PROB, OFFSIM_COLLECT_MLP);
+        else if constexpr (VF == OFFSIM_VALUE_MLP) {
+            if (form == OFFSIM_COLLECT_ROWS) LAUNCH_FORM_XT(PL, PROB, OFFSIM_COLLECT_ROWS);
+            else LAUNCH_FORM_XT(PL, PROB, OFFSIM_COLLECT_TABULAR);
+        } else if (form == OFFSIM_COLLECT_ROWS) LAUNCH_COLLECT(PL, PROB, OFFSIM_COLLECT_ROWS, float);
+        else LAUNCH_COLLECT(PL, PROB, OFFSIM_COLLECT_TABULAR, float);
+        LAUNCH_CHECK();
+        return OFFSIM_OK;
+    });
 #undef LAUNCH_FORM_XT
 #undef LAUNCH_COLLECT
-    LAUNCH_CHECK();
-    return OFFSIM_OK;
 }
 
 extern "C" int offsim_vector_collect(const offsim_table *t, offsim_rollouts *ro, const offsim_collect_policy *pol, int32_t prob_mode,

@@ -22,6 +22,7 @@
 #include "discount.hpp"
 #include "pcg64_dev.hpp"
 #include "philox_dev.hpp"  // rocRAND's Philox4x32-10 on the device (the OFFSIM_STREAM_PHILOX provider)
+#include "stream_row.hpp"  // the layout of a rollout's draw-stream row: load, commit, the per-wave jump table
 
 extern "C" int offsim_lds_order_ok(void);
 #include "shuffle_wave.hpp"
@@ -58,7 +59,6 @@ extern "C" int offsim_device_count(void) {
     return n;
 }
 
-#define WAVE 64
 
 // ------------------------------------------------------------------------------------------------
 // Table construction: stable group-by-state (counting sort with per-chunk histograms)
@@ -812,22 +812,13 @@ __device__ __forceinline__ StepResult psrs_step(const offsim_table &t, const uin
 }
 
 // Fill the per-wave jump table and position lane k on draw k of the stream that starts at `base`.
-__device__ __forceinline__ void wave_rng_init(WaveRng &rng, Jump *table, U128 base, U128 inc, int kind = OFFSIM_STREAM_PCG64) {
-    const int lane = threadIdx.x & (WAVE - 1);
+__device__ __forceinline__ void wave_rng_init(WaveRng &rng, Jump *table, U128 base, U128 inc, int kind) {
     rng.table = table;
     rng.kind = kind;
-    rng.seed = base.hi;  // (Philox: the rng row is seed, draws consumed, 0, 0)
+    rng.seed = base.hi;
     rng.c = base.lo;
     if (kind == OFFSIM_STREAM_PHILOX) return;
-    Jump mine = pcg_jump(inc, (uint64_t)lane + 1);
-    table[lane + 1] = mine;
-    if (lane == 0) {
-        Jump id;
-        id.mult = u128(0, 1);
-        id.plus = u128(0, 0);
-        table[0] = id;
-    }
-    rng.lane_state = pcg_apply(mine, base);  // draw k is the output after k+1 steps
+    rng.lane_state = pcg_apply(jump_table_fill(table, inc), base);  // draw k is the output after k+1 steps
 }
 
 // ---- step_batch: one PSRS.step per rollout, cursors stay in global memory ----
@@ -1150,31 +1141,74 @@ static int check_table(const offsim_table *t) {
     return OFFSIM_OK;
 }
 
+// The one (p_log dtype, prob mode) -> <PL, PROB> choice of every kernel that runs psrs_step: F32 mode compares in float and needs an f32
+// p_log, F64 mode widens any p_log exactly.  check_prob_mode refuses everything else for entry point `who`; with_plog_prob calls
+// f(PL{}, PROB{}) -- a generic lambda that launches its kernel instance and returns the entry point's result.
+static int check_prob_mode(const char *who, const offsim_table *t, int32_t prob_mode) {
+    if (prob_mode != OFFSIM_PROB_F32 && prob_mode != OFFSIM_PROB_F64) return fail(OFFSIM_EINVAL, "%s: bad prob_mode", who);
+    if (prob_mode == OFFSIM_PROB_F32 && t->plog_dtype != OFFSIM_F32) return fail(OFFSIM_EINVAL, "%s: OFFSIM_PROB_F32 needs an f32 p_log", who);
+    return OFFSIM_OK;
+}
+template <typename F>
+static int with_plog(const offsim_table *t, F &&f) {  // (F64 mode: f(PL{}))
+    if (t->plog_dtype == OFFSIM_F32) return f(float{});
+    if (t->plog_dtype == OFFSIM_F64) return f(double{});
+    return f(__half{});
+}
+template <typename F>
+static int with_plog_prob(const offsim_table *t, int32_t prob_mode, F &&f) {
+    if (prob_mode == OFFSIM_PROB_F32) return f(float{}, float{});
+    return with_plog(t, [&](auto pl) -> int { return f(pl, double{}); });
+}
+
+// The three entry points of k_eval_mc: the required outputs and the discount table ...
+static int check_evalmc_out(const char *who, const offsim_evalmc_out *out, const double *gamma_pow, int64_t n_gamma_pow) {
+    if (!out->sum_g || !out->n_ep || !out->steps || !out->cand || !out->n_len || !out->status)
+        return fail(OFFSIM_EINVAL, "%s: required output is NULL", who);
+    if (n_gamma_pow > 0 && !gamma_pow) return fail(OFFSIM_EINVAL, "%s: gamma_pow is NULL", who);
+    return OFFSIM_OK;
+}
+// ... and the launch: 4 rollouts per workgroup, halved until the LDS carve fits 64 KiB; up to 160 KiB with one rollout.
+template <typename PL, typename PROB, bool TD, bool ROWP>
+static int evalmc_launch(const char *who, const offsim_table *t, offsim_rollouts *ro, const void *pi, int32_t reject_mode, double gamma,
+                         const double *gamma_pow, int64_t n_gamma_pow, int64_t max_episodes, const offsim_evalmc_out *out, const offsim_td &td,
+                         const RowPolicyArgs &rp, void *stream) {
+    const size_t pb = ROWP ? 0 : sizeof(PROB);  // (ROWP: no pi block)
+    int waves = 4;
+    while (waves > 1 && evalmc_lds_bytes(waves, t->n_slots, t->nA, pb, TD) > 64 * 1024) waves >>= 1;
+    const size_t lds = evalmc_lds_bytes(waves, t->n_slots, t->nA, pb, TD);
+    if (lds > 160 * 1024)
+        return fail(OFFSIM_EUNSUPPORTED, TD ? "%s: Q table, cursors and policy exceed 160 KiB of LDS" : ROWP ? "%s: per-state cursors exceed 160 KiB of LDS"
+                                                                                                              : "%s: per-state cursors and policy exceed 160 KiB of LDS", who);
+    if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_eval_mc<PL, PROB, TD, ROWP>), (int)lds));
+    hipLaunchKernelGGL((k_eval_mc<PL, PROB, TD, ROWP>), dim3((ro->R + waves - 1) / waves), dim3(waves * WAVE), lds, (hipStream_t)stream, *t, *ro,
+                       (const PROB *)pi, reject_mode, gamma, gamma_pow, n_gamma_pow, max_episodes, *out, td, rp);
+    LAUNCH_CHECK();
+    return OFFSIM_OK;
+}
+
 extern "C" int offsim_step_batch(const offsim_table *t, offsim_rollouts *ro, const void *p_new, int32_t prob_mode,
                                  int32_t reject_mode, int32_t advance, int32_t *out_row, int32_t *out_status,
                                  uint32_t *out_popped, void *stream) {
     int rc = check_table(t);
     if (rc) return rc;
     if (!ro || ro->R < 0 || !p_new) return fail(OFFSIM_EINVAL, "step_batch: bad argument%s");
+    if ((rc = check_prob_mode("step_batch", t, prob_mode))) return rc;
     if (ro->R == 0) return OFFSIM_OK;
-    if (prob_mode == OFFSIM_PROB_F32 && t->plog_dtype != OFFSIM_F32)
-        return fail(OFFSIM_EINVAL, "step_batch: OFFSIM_PROB_F32 needs an f32 p_log%s");
     hipStream_t st = (hipStream_t)stream;
     const int waves = 4;
     dim3 grid((ro->R + waves - 1) / waves), block(waves * WAVE);
     size_t lds = (size_t)waves * (WAVE + 1) * sizeof(Jump);
     uint32_t max_pop = 0;
     if (advance == 0 && reject_mode == OFFSIM_REJECT_NEVER) max_pop = 1;  // "pop one candidate" primitive
-#define LAUNCH_STEP(PL, PROB)                                                                                      \
-    hipLaunchKernelGGL((k_step_batch<PL, PROB>), grid, block, lds, st, *t, *ro, (const PROB *)p_new, reject_mode, \
-                       advance, max_pop, out_row, out_status, out_popped)
-    if (prob_mode == OFFSIM_PROB_F32) LAUNCH_STEP(float, float);
-    else if (t->plog_dtype == OFFSIM_F32) LAUNCH_STEP(float, double);
-    else if (t->plog_dtype == OFFSIM_F64) LAUNCH_STEP(double, double);
-    else LAUNCH_STEP(__half, double);
-#undef LAUNCH_STEP
-    LAUNCH_CHECK();
-    return OFFSIM_OK;
+    return with_plog_prob(t, prob_mode, [&](auto pl, auto prob) -> int {
+        using PL = decltype(pl);
+        using PROB = decltype(prob);
+        hipLaunchKernelGGL((k_step_batch<PL, PROB>), grid, block, lds, st, *t, *ro, (const PROB *)p_new, reject_mode, advance, max_pop, out_row,
+                           out_status, out_popped);
+        LAUNCH_CHECK();
+        return OFFSIM_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1226,15 +1260,7 @@ __global__ void __launch_bounds__(64) k_step_server(offsim_table t, offsim_rollo
     const U128 inc = u128(ro.rng[2], ro.rng[3]);
     const uint32_t *head = (const uint32_t *)mb;
     const bool pcg = ro.rng_kind != OFFSIM_STREAM_PHILOX;
-    if (pcg) {  // the jump table depends on the stream's increment only: built once, not per request
-        table[lane + 1] = pcg_jump(inc, (uint64_t)lane + 1);
-        if (lane == 0) {
-            Jump id;
-            id.mult = u128(0, 1);
-            id.plus = u128(0, 0);
-            table[0] = id;
-        }
-    }
+    if (pcg) jump_table_fill(table, inc);  // the jump table depends on the stream's increment only: built once, not per request
     server_touch_ahead<PL>(t, ro.perm, slot, ro.cursor);
     for (;;) {
         // One poll = ONE read of the mailbox's first 64 bytes (lane i: dword i): request number, command, reject mode, the first
@@ -1397,22 +1423,19 @@ extern "C" int offsim_step_server_start(const offsim_table *t, offsim_rollouts *
                                         uint32_t idle_polls, void *stream) {
     int rc = check_table(t);
     if (rc) return rc;
+    if ((rc = check_prob_mode("step_server_start", t, prob_mode))) return rc;
     if (!ro || ro->R != 1 || !mailbox) return fail(OFFSIM_EINVAL, "step_server_start: one rollout and a mailbox%s");
     if (ro->perm && ro->perm_stride < 0) return fail(OFFSIM_EINVAL, "step_server_start: bad perm%s");
     if (t->nA > OFFSIM_MAILBOX_MAX_ACTIONS) return fail(OFFSIM_EUNSUPPORTED, "step_server_start: more actions than the mailbox holds (use offsim_step_batch)%s");
-    if (prob_mode == OFFSIM_PROB_F32 && t->plog_dtype != OFFSIM_F32) return fail(OFFSIM_EINVAL, "step_server_start: OFFSIM_PROB_F32 needs an f32 p_log%s");
     void *dev_mb = nullptr;
     HIP_TRY(hipHostGetDevicePointer(&dev_mb, mailbox, 0));
     mailbox->state = OFFSIM_SERVER_STARTING;
     hipStream_t st = (hipStream_t)stream;
-#define LAUNCH_SERVER(PL, PROB) hipLaunchKernelGGL((k_step_server<PL, PROB>), dim3(1), dim3(WAVE), 0, st, *t, *ro, (offsim_step_mailbox *)dev_mb, idle_polls)
-    if (prob_mode == OFFSIM_PROB_F32) LAUNCH_SERVER(float, float);
-    else if (t->plog_dtype == OFFSIM_F32) LAUNCH_SERVER(float, double);
-    else if (t->plog_dtype == OFFSIM_F64) LAUNCH_SERVER(double, double);
-    else LAUNCH_SERVER(__half, double);
-#undef LAUNCH_SERVER
-    LAUNCH_CHECK();
-    return OFFSIM_OK;
+    return with_plog_prob(t, prob_mode, [&](auto pl, auto prob) -> int {
+        hipLaunchKernelGGL((k_step_server<decltype(pl), decltype(prob)>), dim3(1), dim3(WAVE), 0, st, *t, *ro, (offsim_step_mailbox *)dev_mb, idle_polls);
+        LAUNCH_CHECK();
+        return OFFSIM_OK;
+    });
 }
 
 extern "C" int offsim_eval_mc(const offsim_table *t, offsim_rollouts *ro, const void *pi, int32_t prob_mode,
@@ -1421,33 +1444,12 @@ extern "C" int offsim_eval_mc(const offsim_table *t, offsim_rollouts *ro, const 
     int rc = check_table(t);
     if (rc) return rc;
     if (!ro || ro->R < 0 || !pi || !out) return fail(OFFSIM_EINVAL, "eval_mc: bad argument%s");
-    if (!out->sum_g || !out->n_ep || !out->steps || !out->cand || !out->n_len || !out->status)
-        return fail(OFFSIM_EINVAL, "eval_mc: required output is NULL%s");
+    if ((rc = check_evalmc_out("eval_mc", out, gamma_pow, n_gamma_pow)) || (rc = check_prob_mode("eval_mc", t, prob_mode))) return rc;
     if (ro->R == 0) return OFFSIM_OK;
-    if (prob_mode == OFFSIM_PROB_F32 && t->plog_dtype != OFFSIM_F32)
-        return fail(OFFSIM_EINVAL, "eval_mc: OFFSIM_PROB_F32 needs an f32 p_log%s");
-    if (n_gamma_pow > 0 && !gamma_pow) return fail(OFFSIM_EINVAL, "eval_mc: gamma_pow is NULL%s");
-    hipStream_t st = (hipStream_t)stream;
-    size_t pb = prob_mode == OFFSIM_PROB_F32 ? 4 : 8;
-    int waves = 4;
-    while (waves > 1 && evalmc_lds_bytes(waves, t->n_slots, t->nA, pb) > 64 * 1024) waves >>= 1;
-    size_t lds = evalmc_lds_bytes(waves, t->n_slots, t->nA, pb);
-    if (lds > 160 * 1024) return fail(OFFSIM_EUNSUPPORTED, "eval_mc: per-state cursors and policy exceed 160 KiB of LDS%s");
-    dim3 grid((ro->R + waves - 1) / waves), block(waves * WAVE);
-#define LAUNCH_MC(PL, PROB)                                                                                          \
-    do {                                                                                                             \
-        if (lds > 64 * 1024)                                                                                         \
-            HIP_TRY(allow_big_lds((k_eval_mc<PL, PROB, false>), (int)lds)); \
-        hipLaunchKernelGGL((k_eval_mc<PL, PROB, false>), grid, block, lds, st, *t, *ro, (const PROB *)pi, reject_mode, gamma, \
-                           gamma_pow, n_gamma_pow, max_episodes, *out, offsim_td{}, RowPolicyArgs{});                \
-    } while (0)
-    if (prob_mode == OFFSIM_PROB_F32) LAUNCH_MC(float, float);
-    else if (t->plog_dtype == OFFSIM_F32) LAUNCH_MC(float, double);
-    else if (t->plog_dtype == OFFSIM_F64) LAUNCH_MC(double, double);
-    else LAUNCH_MC(__half, double);
-#undef LAUNCH_MC
-    LAUNCH_CHECK();
-    return OFFSIM_OK;
+    return with_plog_prob(t, prob_mode, [&](auto pl, auto prob) -> int {
+        return evalmc_launch<decltype(pl), decltype(prob), false, false>("eval_mc", t, ro, pi, reject_mode, gamma, gamma_pow, n_gamma_pow, max_episodes, out,
+                                                                         offsim_td{}, RowPolicyArgs{}, stream);
+    });
 }
 
 // ---- evalMC_psrs for a policy over observations (psrs.py:241-271 with pi[S] at S = the observation, psrs.py:255): the loop of
@@ -1461,34 +1463,13 @@ extern "C" int offsim_eval_mc_rows_policy(const offsim_table *t, offsim_rollouts
     if (!ro || ro->R < 0 || !out) return fail(OFFSIM_EINVAL, "eval_mc_rows_policy: bad argument%s");
     if ((t->N > 0 && !p_next) || (t->N0 > 0 && !p_init)) return fail(OFFSIM_EINVAL, "eval_mc_rows_policy: p_next / p_init is NULL%s");
     if (t->N0 > 0 && (!t->init_slot || !t->init_orig)) return fail(OFFSIM_EINVAL, "eval_mc_rows_policy: table has no init rows%s");
-    if (!out->sum_g || !out->n_ep || !out->steps || !out->cand || !out->n_len || !out->status)
-        return fail(OFFSIM_EINVAL, "eval_mc_rows_policy: required output is NULL%s");
+    if ((rc = check_evalmc_out("eval_mc_rows_policy", out, gamma_pow, n_gamma_pow)) || (rc = check_prob_mode("eval_mc_rows_policy", t, prob_mode))) return rc;
     if (ro->R == 0) return OFFSIM_OK;
-    if (prob_mode != OFFSIM_PROB_F32 && prob_mode != OFFSIM_PROB_F64) return fail(OFFSIM_EINVAL, "eval_mc_rows_policy: bad prob_mode%s");
-    if (prob_mode == OFFSIM_PROB_F32 && t->plog_dtype != OFFSIM_F32)
-        return fail(OFFSIM_EINVAL, "eval_mc_rows_policy: OFFSIM_PROB_F32 needs an f32 p_log%s");
-    if (n_gamma_pow > 0 && !gamma_pow) return fail(OFFSIM_EINVAL, "eval_mc_rows_policy: gamma_pow is NULL%s");
-    hipStream_t st = (hipStream_t)stream;
-    int waves = 4;
-    while (waves > 1 && evalmc_lds_bytes(waves, t->n_slots, t->nA, 0) > 64 * 1024) waves >>= 1;
-    size_t lds = evalmc_lds_bytes(waves, t->n_slots, t->nA, 0);  // (no pi block)
-    if (lds > 160 * 1024) return fail(OFFSIM_EUNSUPPORTED, "eval_mc_rows_policy: per-state cursors exceed 160 KiB of LDS%s");
-    dim3 grid((ro->R + waves - 1) / waves), block(waves * WAVE);
     const RowPolicyArgs rp{p_next, p_init, out_obs_row};
-#define LAUNCH_MC(PL, PROB)                                                                                          \
-    do {                                                                                                             \
-        if (lds > 64 * 1024)                                                                                         \
-            HIP_TRY(allow_big_lds((k_eval_mc<PL, PROB, false, true>), (int)lds));                                     \
-        hipLaunchKernelGGL((k_eval_mc<PL, PROB, false, true>), grid, block, lds, st, *t, *ro, (const PROB *)nullptr, \
-                           reject_mode, gamma, gamma_pow, n_gamma_pow, max_episodes, *out, offsim_td{}, rp);          \
-    } while (0)
-    if (prob_mode == OFFSIM_PROB_F32) LAUNCH_MC(float, float);
-    else if (t->plog_dtype == OFFSIM_F32) LAUNCH_MC(float, double);
-    else if (t->plog_dtype == OFFSIM_F64) LAUNCH_MC(double, double);
-    else LAUNCH_MC(__half, double);
-#undef LAUNCH_MC
-    LAUNCH_CHECK();
-    return OFFSIM_OK;
+    return with_plog_prob(t, prob_mode, [&](auto pl, auto prob) -> int {
+        return evalmc_launch<decltype(pl), decltype(prob), false, true>("eval_mc_rows_policy", t, ro, nullptr, reject_mode, gamma, gamma_pow, n_gamma_pow,
+                                                                        max_episodes, out, offsim_td{}, rp, stream);
+    });
 }
 
 // ---- one driver iteration of the batched evaluator in ONE launch (VectorPSRS.step_and_reset): PSRS.step with the environment's own
@@ -1579,7 +1560,7 @@ extern "C" int offsim_vector_step(const offsim_table *t, offsim_rollouts *ro, co
     if (!ro || ro->R < 0 || !p_new || n_step_cols < 0 || n_step_cols > 8 || n_reset_cols < 0 || n_reset_cols > 8 ||
         (n_step_cols > 0 && !step_cols) || (n_reset_cols > 0 && !reset_cols))
         return fail(OFFSIM_EINVAL, "vector_step: bad argument%s");
-    if (prob_mode == OFFSIM_PROB_F32 && t->plog_dtype != OFFSIM_F32) return fail(OFFSIM_EINVAL, "vector_step: OFFSIM_PROB_F32 needs an f32 p_log%s");
+    if ((rc = check_prob_mode("vector_step", t, prob_mode))) return rc;
     VecCols sc, rcols;
     memset(&sc, 0, sizeof(sc));
     memset(&rcols, 0, sizeof(rcols));
@@ -1596,16 +1577,14 @@ extern "C" int offsim_vector_step(const offsim_table *t, offsim_rollouts *ro, co
     const int waves = 4;
     dim3 grid((ro->R + waves - 1) / waves), block(waves * WAVE);
     const size_t lds = (size_t)waves * (WAVE + 1) * sizeof(Jump);
-#define LAUNCH_VS(PL, PROB)                                                                                                         \
-    hipLaunchKernelGGL((k_vector_step<PL, PROB>), grid, block, lds, st, *t, *ro, (const PROB *)p_new, reject_mode, sc, n_step_cols, rcols, \
-                       n_reset_cols, alive, out_row, out_status)
-    if (prob_mode == OFFSIM_PROB_F32) LAUNCH_VS(float, float);
-    else if (t->plog_dtype == OFFSIM_F32) LAUNCH_VS(float, double);
-    else if (t->plog_dtype == OFFSIM_F64) LAUNCH_VS(double, double);
-    else LAUNCH_VS(__half, double);
-#undef LAUNCH_VS
-    LAUNCH_CHECK();
-    return OFFSIM_OK;
+    return with_plog_prob(t, prob_mode, [&](auto pl, auto prob) -> int {
+        using PL = decltype(pl);
+        using PROB = decltype(prob);
+        hipLaunchKernelGGL((k_vector_step<PL, PROB>), grid, block, lds, st, *t, *ro, (const PROB *)p_new, reject_mode, sc, n_step_cols, rcols,
+                           n_reset_cols, alive, out_row, out_status);
+        LAUNCH_CHECK();
+        return OFFSIM_OK;
+    });
 }
 
 // ---- PSRS_Exo.step (psrs.py:99-117): two queue families, endogenous state s and exogenous state x.  Every candidate
@@ -1633,9 +1612,8 @@ __global__ void __launch_bounds__(256) k_step_exo(offsim_table ts, offsim_table 
         else {
             Jump *table = (Jump *)lds_raw + wave * (WAVE + 1);
             WaveRng rng;
-            const U128 base = u128(rs.rng[4 * r + 0], rs.rng[4 * r + 1]);
-            const U128 inc = u128(rs.rng[4 * r + 2], rs.rng[4 * r + 3]);
-            wave_rng_init(rng, table, base, inc);
+            const U128 base = stream_row_base(rs.rng, r), inc = stream_row_inc(rs.rng, r);
+            wave_rng_init(rng, table, base, inc, OFFSIM_STREAM_PCG64);
             __builtin_amdgcn_s_waitcnt(0xc07f);
             uint32_t cur_s = rs.cursor[(int64_t)r * ts.n_slots + ss], cur_x = rx.cursor[(int64_t)r * tx.n_slots + xs];
             const uint32_t *perm_s = rs.perm ? rs.perm + (int64_t)r * rs.perm_stride : nullptr;
@@ -1681,11 +1659,7 @@ __global__ void __launch_bounds__(256) k_step_exo(offsim_table ts, offsim_table 
             if (lane == 0) {
                 rs.cursor[(int64_t)r * ts.n_slots + ss] = cur_s;
                 rx.cursor[(int64_t)r * tx.n_slots + xs] = cur_x;
-                if (consumed) {
-                    U128 nb = pcg_apply(pcg_jump(inc, consumed), base);
-                    rs.rng[4 * r + 0] = nb.hi;
-                    rs.rng[4 * r + 1] = nb.lo;
-                }
+                stream_row_commit(rs.rng, r, OFFSIM_STREAM_PCG64, base, inc, consumed);
                 if (status == OFFSIM_ST_OK) {  // psrs.py:116
                     rs.cur_slot[r] = ns;
                     rx.cur_slot[r] = nx;
@@ -1709,21 +1683,22 @@ extern "C" int offsim_step_exo(const offsim_table *ts, const offsim_table *tx, o
     rc = check_table(tx);
     if (rc) return rc;
     if (!rs || !rx || rs->R != rx->R || rs->R < 0 || !p_new) return fail(OFFSIM_EINVAL, "step_exo: bad argument%s");
+    if ((rc = check_prob_mode("step_exo", ts, prob_mode))) return rc;
+    if (rs->rng_kind == OFFSIM_STREAM_PHILOX)  // (the draws are rs's: k_step_exo never reads rx's stream)
+        return fail(OFFSIM_EUNSUPPORTED, "step_exo: the rejection stream must be OFFSIM_STREAM_PCG64 (k_step_exo has no Philox draw)%s");
     if (rs->R == 0) return OFFSIM_OK;
-    if (prob_mode == OFFSIM_PROB_F32 && ts->plog_dtype != OFFSIM_F32) return fail(OFFSIM_EINVAL, "step_exo: OFFSIM_PROB_F32 needs an f32 p_log%s");
     hipStream_t st = (hipStream_t)stream;
     const int waves = 4;
     dim3 grid((rs->R + waves - 1) / waves), block(waves * WAVE);
     size_t lds = (size_t)waves * (WAVE + 1) * sizeof(Jump);
-#define LAUNCH_EXO(PL, PROB) \
-    hipLaunchKernelGGL((k_step_exo<PL, PROB>), grid, block, lds, st, *ts, *tx, *rs, *rx, (const PROB *)p_new, out_row_s, out_row_x, out_status, out_popped)
-    if (prob_mode == OFFSIM_PROB_F32) LAUNCH_EXO(float, float);
-    else if (ts->plog_dtype == OFFSIM_F32) LAUNCH_EXO(float, double);
-    else if (ts->plog_dtype == OFFSIM_F64) LAUNCH_EXO(double, double);
-    else LAUNCH_EXO(__half, double);
-#undef LAUNCH_EXO
-    LAUNCH_CHECK();
-    return OFFSIM_OK;
+    return with_plog_prob(ts, prob_mode, [&](auto pl, auto prob) -> int {
+        using PL = decltype(pl);
+        using PROB = decltype(prob);
+        hipLaunchKernelGGL((k_step_exo<PL, PROB>), grid, block, lds, st, *ts, *tx, *rs, *rx, (const PROB *)p_new, out_row_s, out_row_x, out_status,
+                           out_popped);
+        LAUNCH_CHECK();
+        return OFFSIM_OK;
+    });
 }
 
 // qlearn_psrs / expSARSA_psrs (psrs.py:119-239) with a state-independent behaviour policy: evalMC's loop plus the
@@ -1734,34 +1709,17 @@ extern "C" int offsim_eval_td(const offsim_table *t, offsim_rollouts *ro, const 
     int rc = check_table(t);
     if (rc) return rc;
     if (!ro || ro->R < 0 || !pi || !out || !td) return fail(OFFSIM_EINVAL, "eval_td: bad argument%s");
-    if (!out->sum_g || !out->n_ep || !out->steps || !out->cand || !out->n_len || !out->status)
-        return fail(OFFSIM_EINVAL, "eval_td: required output is NULL%s");
+    if ((rc = check_evalmc_out("eval_td", out, gamma_pow, n_gamma_pow))) return rc;
     if ((td->mode != OFFSIM_TD_QLEARN && td->mode != OFFSIM_TD_EXPSARSA) || !td->q) return fail(OFFSIM_EINVAL, "eval_td: bad td mode or NULL q%s");
     if (td->behaviour != OFFSIM_BEHAVIOUR_FIXED && td->behaviour != OFFSIM_BEHAVIOUR_EPS_GREEDY && td->behaviour != OFFSIM_BEHAVIOUR_SOFT_GREEDY)
         return fail(OFFSIM_EINVAL, "eval_td: bad behaviour%s");
     if ((td->alpha_ep || td->epsilon_ep) && td->n_sched <= 0) return fail(OFFSIM_EINVAL, "eval_td: schedules need n_sched > 0%s");
     if (td->q_snap && (td->snap_stride <= 0 || td->snap_cap < 0)) return fail(OFFSIM_EINVAL, "eval_td: bad snapshot stride / capacity%s");
-    if (n_gamma_pow > 0 && !gamma_pow) return fail(OFFSIM_EINVAL, "eval_td: gamma_pow is NULL%s");
     if (ro->R == 0) return OFFSIM_OK;
-    hipStream_t st = (hipStream_t)stream;
-    int waves = 4;
-    while (waves > 1 && evalmc_lds_bytes(waves, t->n_slots, t->nA, 8, true) > 64 * 1024) waves >>= 1;
-    size_t lds = evalmc_lds_bytes(waves, t->n_slots, t->nA, 8, true);
-    if (lds > 160 * 1024) return fail(OFFSIM_EUNSUPPORTED, "eval_td: Q table, cursors and policy exceed 160 KiB of LDS%s");
-    dim3 grid((ro->R + waves - 1) / waves), block(waves * WAVE);
-#define LAUNCH_TD(PL)                                                                                                   \
-    do {                                                                                                                \
-        if (lds > 64 * 1024)                                                                                            \
-            HIP_TRY(allow_big_lds((k_eval_mc<PL, double, true>), (int)lds)); \
-        hipLaunchKernelGGL((k_eval_mc<PL, double, true>), grid, block, lds, st, *t, *ro, pi, reject_mode, gamma, gamma_pow, \
-                           n_gamma_pow, max_episodes, *out, *td, RowPolicyArgs{});                                      \
-    } while (0)
-    if (t->plog_dtype == OFFSIM_F32) LAUNCH_TD(float);
-    else if (t->plog_dtype == OFFSIM_F64) LAUNCH_TD(double);
-    else LAUNCH_TD(__half);
-#undef LAUNCH_TD
-    LAUNCH_CHECK();
-    return OFFSIM_OK;
+    return with_plog(t, [&](auto pl) -> int {
+        return evalmc_launch<decltype(pl), double, true, false>("eval_td", t, ro, pi, reject_mode, gamma, gamma_pow, n_gamma_pow, max_episodes, out, *td,
+                                                                RowPolicyArgs{}, stream);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------

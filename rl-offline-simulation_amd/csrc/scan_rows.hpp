@@ -221,7 +221,7 @@ __device__ __forceinline__ uint32_t row_min16(uint32_t x) {
 
 // k53 of the draw that needs n_steps LCG steps from the stream's start (exact tie decisions only)
 __device__ __noinline__ uint64_t rows_exact53(const uint64_t *__restrict__ rng4, uint64_t n_steps) {
-    const U128 base = u128(rng4[0], rng4[1]), inc = u128(rng4[2], rng4[3]);
+    const U128 base = stream_row_base(rng4, 0), inc = stream_row_inc(rng4, 0);
     return pcg_output(pcg_apply(pcg_jump(inc, n_steps), base)) >> 11;
 }
 
@@ -331,11 +331,11 @@ __global__ void __launch_bounds__(HELPER ? 512 : 256)
     constexpr bool philox = RNG == OFFSIM_STREAM_PHILOX;
     U128 lane_state = u128(0, 0);
     U128 plus16 = u128(0, 0);
-    // Philox: the rng row is (seed, draws consumed so far, 0, 0); lanes 0..7 of a row each own one block = two draws per round of 16
-    // (lanes 8..15 repeat them: one instruction stream for the wavefront)
+    // Philox (csrc/stream_row.hpp: base.hi, base.lo): lanes 0..7 of a row each own one block = two draws per round of 16 (lanes 8..15
+    // repeat them: one instruction stream for the wavefront)
     const uint64_t ph_seed = philox ? rng4[0] : 0ull, ph_c0 = philox ? rng4[1] : 0ull;
     if (owns_draws && !philox) {
-        const U128 base = u128(rng4[0], rng4[1]), inc = u128(rng4[2], rng4[3]);
+        const U128 base = stream_row_base(rng4, 0), inc = stream_row_inc(rng4, 0);
         plus16 = pcg_jump(inc, 16).plus;
         lane_state = pcg_apply(pcg_jump(inc, (uint64_t)li + 1), base);  // yields draw li
     }
@@ -1694,13 +1694,9 @@ __global__ void __launch_bounds__(HELPER ? 512 : 256)
         if (li == 0u) {
             ro.init_cursor[r] = ic;
             ro.cur_slot[r] = (int32_t)z;
-            if (c && philox) {
-                ro.rng[4 * r + 1] = ph_c0 + c;  // (seed, draws consumed so far, 0, 0)
-            } else if (c) {
-                const U128 base = u128(rng4[0], rng4[1]), inc = u128(rng4[2], rng4[3]);
-                const U128 nb = pcg_apply(pcg_jump(inc, c), base);
-                ro.rng[4 * r + 0] = nb.hi;
-                ro.rng[4 * r + 1] = nb.lo;
+            if (c) {
+                if constexpr (philox) stream_row_commit(ro.rng, r, RNG, u128(ph_seed, ph_c0), u128(0, 0), c);
+                else stream_row_commit(ro.rng, r, RNG, stream_row_base(rng4, 0), stream_row_inc(rng4, 0), c);  // (read again: not kept across the chain loop)
             }
             if (!HELPER) {  // (HELPER: the helper wavefront owns the sums and writes them)
                 out.sum_g[r] = sum_g;

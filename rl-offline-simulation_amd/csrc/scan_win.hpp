@@ -186,10 +186,9 @@ __global__ void __launch_bounds__(256, 4)
     Jump j64;
     j64.mult = u128(0, 1);
     j64.plus = u128(0, 0);
-    const uint64_t ph_seed = philox ? ro.rng[4 * r + 0] : 0ull, ph_c0 = philox ? ro.rng[4 * r + 1] : 0ull;  // Philox: (seed, draws consumed so far, 0, 0)
+    const uint64_t ph_seed = philox ? ro.rng[4 * r + 0] : 0ull, ph_c0 = philox ? ro.rng[4 * r + 1] : 0ull;  // (csrc/stream_row.hpp: base.hi, base.lo)
     if (!philox) {
-        const U128 base = u128(ro.rng[4 * r + 0], ro.rng[4 * r + 1]);
-        const U128 inc = u128(ro.rng[4 * r + 2], ro.rng[4 * r + 3]);
+        const U128 base = stream_row_base(ro.rng, r), inc = stream_row_inc(ro.rng, r);
         j64 = pcg_jump(inc, 64);
         lane_state = pcg_apply(pcg_jump(inc, (uint64_t)lane + 1), base);  // yields draw `lane`
     }
@@ -221,9 +220,7 @@ __global__ void __launch_bounds__(256, 4)
         if constexpr (philox) {
             return offsim_philox_k(ph_seed, ph_c0 + (uint64_t)n_steps - 1ull);
         } else {
-            const U128 base = u128(ro.rng[4 * r + 0], ro.rng[4 * r + 1]);
-            const U128 inc = u128(ro.rng[4 * r + 2], ro.rng[4 * r + 3]);
-            return pcg_output(pcg_apply(pcg_jump(inc, n_steps), base)) >> 11;
+            return exact_draw53(stream_row_base(ro.rng, r), stream_row_inc(ro.rng, r), n_steps);
         }
     };
 
@@ -599,14 +596,9 @@ __global__ void __launch_bounds__(256, 4)
     if (lane == 0) {
         ro.init_cursor[r] = ic;
         ro.cur_slot[r] = slot;
-        if (c && philox) {
-            ro.rng[4 * r + 1] = ph_c0 + c;  // (seed, draws consumed so far, 0, 0)
-        } else if (c) {
-            const U128 base = u128(ro.rng[4 * r + 0], ro.rng[4 * r + 1]);
-            const U128 inc = u128(ro.rng[4 * r + 2], ro.rng[4 * r + 3]);
-            U128 nb = pcg_apply(pcg_jump(inc, c), base);
-            ro.rng[4 * r + 0] = nb.hi;
-            ro.rng[4 * r + 1] = nb.lo;
+        if (c) {
+            if constexpr (philox) stream_row_commit(ro.rng, r, RNG, u128(ph_seed, ph_c0), u128(0, 0), c);
+            else stream_row_commit(ro.rng, r, RNG, stream_row_base(ro.rng, r), stream_row_inc(ro.rng, r), c);  // (read again: not kept across the chain loop)
         }
         out.sum_g[r] = sum_g;
         out.n_ep[r] = ep_acc;
