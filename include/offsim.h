@@ -718,6 +718,81 @@ int offsim_ppo_grad(const offsim_ppo_net *net, int32_t kind, const offsim_ppo_ba
 int offsim_ppo_update(const offsim_ppo_net *net, int32_t kind, const offsim_ppo_batch *batch, double clip_ratio, double target_kl,
                       int32_t iters, const offsim_ppo_adam *opt, double *stats, double *trace, double *work, void *stream);
 
+/* ---- HOMER encoder training (HOMEREncoder.train, loss_grad) ------------------------------------------------------------------------
+ * The model of offsim4rl/encoders/models.py: obs_encoder = Linear(dO,H) -> LeakyReLU -> Linear(H,nZ), classifier =
+ * Linear(2 nZ + nA, H) -> LeakyReLU -> Linear(H,2), the action embedding a frozen identity (a one-hot of the action).  One record m of a
+ * batch is (i = idx_real[m], j = idx_impo[m], noise g[m][0..3][nZ]); the loss is HOMEREncoder._calc_loss (homer.py:170-184):
+ *   e_prev = enc(obs[i]);  e_real = enc(next_obs[i]);  e_impo = enc(next_obs[j])
+ *   z0 = softmax((e_prev + g0) / tau)   z1 = softmax((e_real + g1) / tau)
+ *   z2 = softmax((e_prev + g2) / tau)   z3 = softmax((e_impo + g3) / tau)
+ *   lp_real = log_softmax(cls([z0, onehot(act[i]), z1]));  lp_impo = log_softmax(cls([z2, onehot(act[i]), z3]))
+ *   loss = (mean_m(-lp_real[m][1]) + mean_m(-lp_impo[m][0])) / 2
+ * The noise and the indices are inputs: nothing is drawn on the device.  hard != 0: every z is F.gumbel_softmax(hard=True)'s forward
+ * value, (onehot(argmax) - y_soft) + y_soft; forward only.  A record whose i or j lies outside [0, n_rows) or whose act[i] lies outside
+ * [0, nA) is invalid: it is excluded from n and contributes nothing, and its noise may hold anything.
+ * f32 arithmetic per record (fmaf chains in k order); per-workgroup partial gradients in f32 over a fixed assignment of tiles to at
+ * most OFFSIM_HOMER_MAX_BLOCKS workgroups, summed in block order in f64: no float atomics, two calls on the same input give the same
+ * bits.  All weights and one tile of records must fit 160 KiB of LDS and P <= OFFSIM_HOMER_MAX_FLOATS, otherwise OFFSIM_EUNSUPPORTED.
+ *
+ * offsim_homer_grad: one pass.  grad [P] f32 or NULL (forward only): the gradient of the loss, unclipped, flat in the order encoder
+ * L1 W [H,dO], b, L2 W [nZ,H], b, classifier L1 W [H, 2 nZ + nA], b, L2 W [2,H], b.  stats [2] f64: n (valid records), loss.
+ * hard != 0 requires grad == NULL.  Two launches.
+ *
+ * offsim_homer_step: one pass, then torch.nn.utils.clip_grad_norm_ over all trainable parameters of both networks
+ * (total = sqrt(sum g^2), coef = min(1, max_grad_norm / (total + 1e-6)), g *= coef) and torch.optim.Adam's step with L2 weight decay
+ * (g += weight_decay * p before the moments; b1 = 0.9, b2 = 0.999, eps = 1e-8), in place on the net's tensors, with
+ * offsim_ppo_update's arithmetic: each line in f64 from the f32 state and the f32 gradient, m and v rounded to f32 before the last line
+ * reads them.  adam: m, v [P] f32 (flat as grad) and t [1] i64 on the device, zero before the first call.  stats [3] f64: n, loss,
+ * total_norm.  A batch without a valid record changes nothing (t included).  Three launches.
+ *
+ * work: OFFSIM_HOMER_WORK_DOUBLES(P) doubles of device scratch (offsim_homer_work_doubles computes P from the net; a negative return is
+ * an error code).  Argument validation happens before any HIP call (tau <= 0, nZ < 2, a negative slope, NULL pointers, widths outside
+ * dO <= 128, H <= 256, nZ <= 256, nA <= 16: OFFSIM_EINVAL); M = 0 launches nothing.  Asynchronous on `stream`, capturable. */
+#define OFFSIM_HOMER_MAX_BLOCKS 128
+#define OFFSIM_HOMER_MAX_FLOATS 20480
+#define OFFSIM_HOMER_WORK_DOUBLES(P) \
+    (OFFSIM_HOMER_MAX_BLOCKS * 2 + 8 + ((P) + 255) / 256 + ((P) + 1) / 2 + OFFSIM_HOMER_MAX_BLOCKS * (((P) + 1) / 2))
+typedef struct offsim_homer_net {      /* state_dict layout, writable device pointers: offsim_homer_step steps them in place */
+    float *enc_W1;                     /* obs_encoder.0.weight [H, dO]                              */
+    float *enc_b1;                     /* obs_encoder.0.bias   [H]                                  */
+    float *enc_W2;                     /* obs_encoder.2.weight [nZ, H]                              */
+    float *enc_b2;                     /* obs_encoder.2.bias   [nZ]                                 */
+    float *cls_W1;                     /* classifier.0.weight  [H, 2 nZ + nA]                       */
+    float *cls_b1;                     /* classifier.0.bias    [H]                                  */
+    float *cls_W2;                     /* classifier.2.weight  [2, H]                               */
+    float *cls_b2;                     /* classifier.2.bias    [2]                                  */
+    int32_t dO;
+    int32_t nA;
+    int32_t nZ;
+    int32_t H;
+    float slope;                       /* LeakyReLU's negative slope (torch's default: 0.01)        */
+    int32_t reserved;
+} offsim_homer_net;
+typedef struct offsim_homer_batch {
+    const void *obs;                   /* [n_rows, dO] f32 or f16 (x_dtype)                         */
+    const void *next_obs;              /* [n_rows, dO]                                              */
+    int32_t x_dtype;
+    int32_t reserved;
+    const int32_t *act;                /* [n_rows]                                                  */
+    int64_t n_rows;
+    const int32_t *idx_real;           /* [M]                                                       */
+    const int32_t *idx_impo;           /* [M]                                                       */
+    const float *noise;                /* [M, 4, nZ], or NULL: zeros                                */
+    int64_t M;
+} offsim_homer_batch;
+typedef struct offsim_homer_adam {
+    float *m;                          /* [P] in/out                                                */
+    float *v;                          /* [P] in/out                                                */
+    int64_t *t;                        /* [1] in/out: Adam's step count                             */
+    double lr;
+    double weight_decay;
+} offsim_homer_adam;
+int64_t offsim_homer_work_doubles(const offsim_homer_net *net);
+int offsim_homer_grad(const offsim_homer_net *net, const offsim_homer_batch *batch, double tau, int32_t hard, float *grad, double *stats,
+                      double *work, void *stream);
+int offsim_homer_step(const offsim_homer_net *net, const offsim_homer_batch *batch, double tau, double max_grad_norm,
+                      const offsim_homer_adam *adam, double *stats, double *work, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,36 @@ class PPOAdam(C.Structure):
     _fields_ = [("m", _vp), ("v", _vp), ("t", _vp), ("lr", C.c_double)]
 
 
+HOMER_MAX_BLOCKS, HOMER_MAX_FLOATS = 128, 20480
+
+
+def homer_params(dO, nA, nZ, H):
+    """the number of trainable parameters of the HOMER model: offsim_homer_grad's P"""
+    return dO * H + H + H * nZ + nZ + (2 * nZ + nA) * H + H + 2 * H + 2
+
+
+def homer_work_doubles(P):
+    """include/offsim.h: OFFSIM_HOMER_WORK_DOUBLES(P)"""
+    return HOMER_MAX_BLOCKS * 2 + 8 + (P + 255) // 256 + (P + 1) // 2 + HOMER_MAX_BLOCKS * ((P + 1) // 2)
+
+
+class HomerNet(C.Structure):
+    """struct offsim_homer_net"""
+    _fields_ = [("enc_W1", _vp), ("enc_b1", _vp), ("enc_W2", _vp), ("enc_b2", _vp), ("cls_W1", _vp), ("cls_b1", _vp), ("cls_W2", _vp),
+                ("cls_b2", _vp), ("dO", _i32), ("nA", _i32), ("nZ", _i32), ("H", _i32), ("slope", C.c_float), ("reserved", _i32)]
+
+
+class HomerBatch(C.Structure):
+    """struct offsim_homer_batch"""
+    _fields_ = [("obs", _vp), ("next_obs", _vp), ("x_dtype", _i32), ("reserved", _i32), ("act", _vp), ("n_rows", _i64), ("idx_real", _vp),
+                ("idx_impo", _vp), ("noise", _vp), ("M", _i64)]
+
+
+class HomerAdam(C.Structure):
+    """struct offsim_homer_adam"""
+    _fields_ = [("m", _vp), ("v", _vp), ("t", _vp), ("lr", C.c_double), ("weight_decay", C.c_double)]
+
+
 MAILBOX_MAX_ACTIONS = 24
 SERVER_CMD_STEP, SERVER_CMD_POP_ONE, SERVER_CMD_EXIT, SERVER_CMD_RESET = 1, 2, 3, 4
 SERVER_STARTING, SERVER_RUNNING, SERVER_EXITED = 1, 2, 3
@@ -208,6 +238,9 @@ SIGNATURES = {
     "offsim_ppo_grad": (C.c_int, [C.POINTER(PPONet), _i32, C.POINTER(PPOBatchC), C.c_double, _vp, _vp, _vp, _vp]),
     "offsim_ppo_update": (C.c_int, [C.POINTER(PPONet), _i32, C.POINTER(PPOBatchC), C.c_double, C.c_double, _i32, C.POINTER(PPOAdam), _vp, _vp,
                                     _vp, _vp]),
+    "offsim_homer_work_doubles": (_i64, [C.POINTER(HomerNet)]),
+    "offsim_homer_grad": (C.c_int, [C.POINTER(HomerNet), C.POINTER(HomerBatch), C.c_double, _i32, _vp, _vp, _vp, _vp]),
+    "offsim_homer_step": (C.c_int, [C.POINTER(HomerNet), C.POINTER(HomerBatch), C.c_double, C.c_double, C.POINTER(HomerAdam), _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -2290,3 +2290,6 @@ extern "C" int offsim_value_mlp(const void *x, int32_t x_dtype, int64_t n_x, int
 
 // ---- the PPO update: fused forward / loss / backward, reduce + Adam, early stop on the device (csrc/ppo_update.hpp) ----
 #include "ppo_update.hpp"
+
+// ---- HOMER encoder training: fused forward / loss / backward, reduce, clip + Adam (csrc/homer_train.hpp) ----
+#include "homer_train.hpp"
