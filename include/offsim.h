@@ -620,6 +620,22 @@ int offsim_vector_collect_ppo(const offsim_table *t, offsim_rollouts *ro, const 
                               int32_t prob_mode, int32_t reject_mode, int64_t T, int32_t max_episode_steps, const offsim_collect_state *st,
                               const offsim_collect_out *out, const offsim_collect_ppo_out *ppo, void *stream);
 
+/* offsim_vector_collect_ppo_pop: offsim_vector_collect_ppo for a population of L independent learners in the same ONE launch.  `ro` holds
+ * R = L * E environments, learner-major: environment r belongs to learner r / E and is run with that learner's actor and critic.  The
+ * networks are stacked: every layer's W is [L, out, in] and b is [L, out], contiguous; pol->layers_host and val->layers_host describe
+ * learner 0, and learner l's tensors are at W + l * out * in and b + l * out.  All learners share the architecture, the activation and
+ * the observations' type.  Only pol->form = OFFSIM_COLLECT_MLP with val->form = OFFSIM_VALUE_MLP is supported (anything else:
+ * OFFSIM_EUNSUPPORTED); the actor's and the critic's floats of ONE learner together are at most OFFSIM_COLLECT_MLP_MAX_FLOATS.
+ * The grid is (ceil(E / 8), L): a workgroup stages one learner's two networks into LDS for up to eight of that learner's environments,
+ * so E need not be a multiple of 8 and no workgroup serves two learners.  Everything else -- the step, the reset, the records [T, R]
+ * (step-major: learner l's buffer is the columns l * E .. (l + 1) * E - 1), the carried state, x_start [R, dO] -- is
+ * offsim_vector_collect_ppo's, and every environment's records and state equal, bit for bit, what offsim_vector_collect_ppo gives for
+ * that environment with its learner's networks.  L in 1..65535, E >= 1, ro->R = L * E (otherwise OFFSIM_EINVAL).
+ * Argument validation happens before any HIP call; T = 0 launches nothing. */
+int offsim_vector_collect_ppo_pop(const offsim_table *t, offsim_rollouts *ro, const offsim_collect_policy *pol, const offsim_collect_value *val,
+                                  int32_t L, int32_t E, int32_t prob_mode, int32_t reject_mode, int64_t T, int32_t max_episode_steps,
+                                  const offsim_collect_state *st, const offsim_collect_out *out, const offsim_collect_ppo_out *ppo, void *stream);
+
 /* offsim_ppo_advantages: GAE-lambda advantages and rewards-to-go over step-major [T,E] records, with the path rules of the reference's
  * agent, and spinup's advantage normalisation (spinup PPOBuffer.finish_path / get, driven by offsim4rl/agents/ppo.py:106-158; E
  * environments = E MPI processes of local_steps_per_epoch = T).  Per environment e, over its valid steps t (flags & OFFSIM_COLLECT_SERVED):
@@ -641,6 +657,18 @@ int offsim_vector_collect_ppo(const offsim_table *t, offsim_rollouts *ro, const 
 int offsim_ppo_advantages(const float *rew, const float *value, const uint8_t *flags, const float *final_value, const float *v_trunc,
                           int64_t T, int64_t E, double gamma, double lam, int32_t bootstrap, float *adv, float *ret, float *adv_norm,
                           double *stats, double *work, void *stream);
+
+/* offsim_ppo_advantages_pop: offsim_ppo_advantages over the step-major [T, L * E] records of a population of L learners with E
+ * environments each (learner-major columns, as offsim_vector_collect_ppo_pop leaves them; final_value [L * E]).  GAE-lambda and
+ * rewards-to-go run per environment exactly as in offsim_ppo_advantages.  adv_norm, mean and std are PER LEARNER, over that learner's
+ * [T, E] entries, each sum in the fixed order offsim_ppo_advantages uses on a contiguous [T, E] input: the same bits.  stats [L, 2] =
+ * (mean, std) per learner; a learner without a valid entry gets std = 0 and adv_norm = adv.  work: OFFSIM_PPO_WORK_DOUBLES_POP(L, E)
+ * doubles.  The same launches as offsim_ppo_advantages, on a grid (ceil(E / 256), L).  L in 1..65535, E >= 1.
+ * Argument validation happens before any HIP call. */
+#define OFFSIM_PPO_WORK_DOUBLES_POP(L, E) ((L) * OFFSIM_PPO_WORK_DOUBLES(E))
+int offsim_ppo_advantages_pop(const float *rew, const float *value, const uint8_t *flags, const float *final_value, const float *v_trunc,
+                              int64_t T, int32_t L, int64_t E, double gamma, double lam, int32_t bootstrap, float *adv, float *ret,
+                              float *adv_norm, double *stats, double *work, void *stream);
 
 /* ---- the PPO update (PPOLearner.update, ppo_grad) --------------------------------------------------------------------------------
  * PPOAgentRevealed.adapt (offsim4rl/agents/ppo.py:162-223) over M records -- a PPO buffer as offsim_vector_collect_ppo and
@@ -717,6 +745,39 @@ int offsim_ppo_grad(const offsim_ppo_net *net, int32_t kind, const offsim_ppo_ba
                     double *work, void *stream);
 int offsim_ppo_update(const offsim_ppo_net *net, int32_t kind, const offsim_ppo_batch *batch, double clip_ratio, double target_kl,
                       int32_t iters, const offsim_ppo_adam *opt, double *stats, double *trace, double *work, void *stream);
+
+/* offsim_ppo_grad_pop / offsim_ppo_update_pop: offsim_ppo_grad / offsim_ppo_update for a population of L independent learners, in the
+ * same number of launches as for one (the learner is the grid's y dimension).  batch: the step-major [T, L * E] buffer as it is, M =
+ * T * L * E records (a multiple of L * E); learner l sees its records in the flat order m' = t * E + e, read at memory index
+ * t * L * E + l * E + e -- its buffer is never copied out.  net: the stacked networks, W [L, out, in] and b [L, out] per layer,
+ * layers_host describing learner 0 (learner l's tensors at W + l * out * in, b + l * out).  Per learner, the tile size, the assignment
+ * of tiles to min(tiles, OFFSIM_PPO_MAX_BLOCKS) workgroups and the f64 block-order reduction are those of offsim_ppo_grad /
+ * offsim_ppo_update on a contiguous [T * E] batch, so every learner's results equal the single call's bit for bit.
+ *   offsim_ppo_grad_pop    grad [L, P] f32, stats [L, 5] f64; clip_ratio: a HOST array [L].
+ *   offsim_ppo_update_pop  clip_ratio, target_kl and opt->lr: HOST arrays [L] (they ride to the device as kernel arguments: no copy the
+ *                          host waits for); iters is shared.  opt->m, v [L, P] f32 and t [L] i64 on the device; stats [L, 6], trace
+ *                          [L, iters, 2] f64.  Every learner has its own stop flag: one whose KL stop fires goes quiet while the others
+ *                          keep stepping, and t[l] moves by learner l's own steps.  A learner without a valid record changes nothing of
+ *                          its own (weights, m, v, t; StopIter = 0, zeros) and does not disturb the others.
+ * No float atomics, no cooperative launch; no kernel waits for another workgroup.
+ * work: offsim_ppo_update_work_doubles_pop(net, L, M) doubles of device scratch, M = T * E the records of ONE learner: per learner
+ * OFFSIM_PPO_UPDATE_WORK_DOUBLES_NB(P, nb) for the nb = min(tiles, OFFSIM_PPO_MAX_BLOCKS) workgroups the learner really has (a caller
+ * that does not know M passes INT64_MAX and gets the size for OFFSIM_PPO_MAX_BLOCKS); a negative return is an error code.  L in
+ * 1..65535, E >= 1.  Argument validation happens before any HIP call (every learner's clip_ratio in [0, 1), target_kl >= 0, lr >= 0);
+ * M = 0 or iters = 0 launches nothing. */
+#define OFFSIM_PPO_UPDATE_WORK_DOUBLES_NB(P, NB) ((NB) * 8 + 8 + (NB) * (((P) + 1) / 2))
+typedef struct offsim_ppo_adam_pop {
+    float *m;                          /* [L,P] in/out                                              */
+    float *v;                          /* [L,P] in/out                                              */
+    int64_t *t;                        /* [L] in/out: every learner's Adam step count               */
+    const double *lr;                  /* [L] HOST array                                            */
+} offsim_ppo_adam_pop;
+int64_t offsim_ppo_update_work_doubles_pop(const offsim_ppo_net *net, int32_t L, int64_t M);
+int offsim_ppo_grad_pop(const offsim_ppo_net *net, int32_t kind, const offsim_ppo_batch *batch, int32_t L, int32_t E, const double *clip_ratio,
+                        float *grad, double *stats, double *work, void *stream);
+int offsim_ppo_update_pop(const offsim_ppo_net *net, int32_t kind, const offsim_ppo_batch *batch, int32_t L, int32_t E,
+                          const double *clip_ratio, const double *target_kl, int32_t iters, const offsim_ppo_adam_pop *opt, double *stats,
+                          double *trace, double *work, void *stream);
 
 /* ---- HOMER encoder training (HOMEREncoder.train, loss_grad) ------------------------------------------------------------------------
  * The model of offsim4rl/encoders/models.py: obs_encoder = Linear(dO,H) -> LeakyReLU -> Linear(H,nZ), classifier =

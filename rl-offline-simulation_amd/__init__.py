@@ -6,4 +6,11 @@ from .data import OfflineDataset, ProbDistribution, Transition  # noqa: F401
 from .core import RevealedRandomnessEnv  # noqa: F401
 from . import spaces, synth  # noqa: F401
 
-__all__ = ["OfflineDataset", "ProbDistribution", "Transition", "RevealedRandomnessEnv", "spaces", "synth"]
+__all__ = ["OfflineDataset", "ProbDistribution", "Transition", "RevealedRandomnessEnv", "spaces", "synth", "PPOPopulation"]
+
+
+def __getattr__(name):  # the evaluators import torch: loaded when first asked for
+    if name == "PPOPopulation":
+        from .evaluators import PPOPopulation
+        return PPOPopulation
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

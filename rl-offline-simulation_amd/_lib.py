@@ -135,6 +135,16 @@ class PPOAdam(C.Structure):
     _fields_ = [("m", _vp), ("v", _vp), ("t", _vp), ("lr", C.c_double)]
 
 
+class PPOAdamPop(C.Structure):
+    """struct offsim_ppo_adam_pop"""
+    _fields_ = [("m", _vp), ("v", _vp), ("t", _vp), ("lr", C.POINTER(C.c_double))]
+
+
+def ppo_update_work_doubles_nb(P, nb):
+    """include/offsim.h: OFFSIM_PPO_UPDATE_WORK_DOUBLES_NB(P, NB)"""
+    return nb * 8 + 8 + nb * ((P + 1) // 2)
+
+
 HOMER_MAX_BLOCKS, HOMER_MAX_FLOATS = 128, 20480
 
 
@@ -238,6 +248,13 @@ SIGNATURES = {
     "offsim_ppo_grad": (C.c_int, [C.POINTER(PPONet), _i32, C.POINTER(PPOBatchC), C.c_double, _vp, _vp, _vp, _vp]),
     "offsim_ppo_update": (C.c_int, [C.POINTER(PPONet), _i32, C.POINTER(PPOBatchC), C.c_double, C.c_double, _i32, C.POINTER(PPOAdam), _vp, _vp,
                                     _vp, _vp]),
+    "offsim_vector_collect_ppo_pop": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), C.POINTER(CollectPolicy), C.POINTER(CollectValue), _i32, _i32,
+                                                _i32, _i32, _i64, _i32, C.POINTER(CollectState), C.POINTER(CollectOut), C.POINTER(CollectPPOOut), _vp]),
+    "offsim_ppo_advantages_pop": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, C.c_double, C.c_double, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "offsim_ppo_update_work_doubles_pop": (_i64, [C.POINTER(PPONet), _i32, _i64]),
+    "offsim_ppo_grad_pop": (C.c_int, [C.POINTER(PPONet), _i32, C.POINTER(PPOBatchC), _i32, _i32, C.POINTER(C.c_double), _vp, _vp, _vp, _vp]),
+    "offsim_ppo_update_pop": (C.c_int, [C.POINTER(PPONet), _i32, C.POINTER(PPOBatchC), _i32, _i32, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32,
+                                        C.POINTER(PPOAdamPop), _vp, _vp, _vp, _vp]),
     "offsim_homer_work_doubles": (_i64, [C.POINTER(HomerNet)]),
     "offsim_homer_grad": (C.c_int, [C.POINTER(HomerNet), C.POINTER(HomerBatch), C.c_double, _i32, _vp, _vp, _vp, _vp]),
     "offsim_homer_step": (C.c_int, [C.POINTER(HomerNet), C.POINTER(HomerBatch), C.c_double, C.c_double, C.POINTER(HomerAdam), _vp, _vp, _vp]),

@@ -20,6 +20,10 @@
 //
 // An in-LDS network, the actor's or the critic's, is ONE descriptor (CollectMlp, filled by collect_mlp from policy_mlp.hpp's PmlpNet),
 // staged by pmlp_stage and evaluated by collect_forward; where an environment's observation row is, is collect_obs_row.
+//
+// A population (offsim_vector_collect_ppo_pop) is the VF = OFFSIM_VALUE_MLP instance of the MLP form on a grid (ceil(E / 8), L): the
+// workgroups of row l stage learner l's actor and critic out of the stacked weights and serve environments l * E + [0, E), so no
+// workgroup holds two learners' environments.  One learner is the row l = 0 with E = R: the launch and the code of before.
 #pragma once
 
 #include <type_traits>
@@ -48,6 +52,7 @@ struct CollectMlp {
 struct CollectValue {
     CollectMlp mlp;
     uint32_t off_w;
+    int envs;  // environments per learner: workgroups (x, l) serve l * envs + [0, envs), with learner l's networks (one learner: ro->R)
     const float *v_next, *v_init;
     offsim_collect_ppo_out rec;
 };
@@ -142,18 +147,24 @@ __global__ void __launch_bounds__(COLLECT_WAVES * WAVE) k_collect(offsim_table t
     float *pf_lds = (float *)(lds_raw + A.off_pf) + wave * PMLP_MAX_ACTIONS;
     float *act_lds = (float *)(lds_raw + A.off_act) + (size_t)wave * 2 * A.mlp.w_max;
     if constexpr (FORM == OFFSIM_COLLECT_MLP) {
-        pmlp_stage(w_lds, A.mlp, A.mlp.out, threadIdx.x, blockDim.x);
+        if constexpr (VF == COLLECT_VF_NONE) pmlp_stage(w_lds, A.mlp, A.mlp.out, threadIdx.x, blockDim.x);
+        else pmlp_stage(w_lds, A.mlp, A.mlp.out, threadIdx.x, blockDim.x, (int)blockIdx.y);
     } else if constexpr (FORM == OFFSIM_COLLECT_TABULAR) {
         for (int i = threadIdx.x; i < t.n_slots * nA; i += blockDim.x) pi_lds[i] = ((const PROB *)A.pi)[i];
     }
     float *v_lds = nullptr;  // the critic's W^T / b (VF = OFFSIM_VALUE_MLP)
     if constexpr (VF == OFFSIM_VALUE_MLP) {
         v_lds = (float *)(lds_raw + A.V.off_w);
-        pmlp_stage(v_lds, A.V.mlp, A.V.mlp.out, threadIdx.x, blockDim.x);
+        pmlp_stage(v_lds, A.V.mlp, A.V.mlp.out, threadIdx.x, blockDim.x, (int)blockIdx.y);
     }
     __syncthreads();
-    const int r = blockIdx.x * waves + wave;
-    if (r >= ro.R) return;
+    int r = blockIdx.x * waves + wave;
+    if constexpr (VF == COLLECT_VF_NONE) {
+        if (r >= ro.R) return;
+    } else {  // the tail of each learner's environments
+        if (r >= A.V.envs) return;
+        r += (int)blockIdx.y * A.V.envs;
+    }
     const int64_t R = ro.R, ob = A.st.obs_bytes;
 
     int slot = ro.cur_slot[r];
@@ -389,11 +400,12 @@ static int collect_prepare(const char *who, const offsim_table *t, offsim_rollou
 }
 
 // One launch of k_collect<..., VF> for the actor's form and the observations' type (XT: the in-kernel networks' input; float where none is).
+// L learners of E environments each (one learner: L = 1, E = ro->R).
 template <int VF>
 static int collect_launch(const offsim_table *t, offsim_rollouts *ro, int32_t form, int32_t x_dtype, int32_t prob_mode, size_t lds,
-                          const CollectKArgs<VF> &A, void *stream) {
+                          const CollectKArgs<VF> &A, void *stream, int L, int E) {
     hipStream_t s = (hipStream_t)stream;
-    dim3 grid((unsigned)((ro->R + COLLECT_WAVES - 1) / COLLECT_WAVES)), block(COLLECT_WAVES * WAVE);
+    dim3 grid((unsigned)((E + COLLECT_WAVES - 1) / COLLECT_WAVES), (unsigned)L), block(COLLECT_WAVES * WAVE);
 #define LAUNCH_COLLECT(PL, PROB, FORM, XT)                                                               \
     do {                                                                                                  \
         if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_collect<PL, PROB, FORM, XT, VF>), (int)lds));      \
@@ -430,45 +442,69 @@ extern "C" int offsim_vector_collect(const offsim_table *t, offsim_rollouts *ro,
     const size_t lds = collect_lds_layout(COLLECT_WAVES, shared, A.mlp.w_max, A);
     if (lds > 160 * 1024) return fail(OFFSIM_EUNSUPPORTED, "vector_collect: the policy table and per-wave scratch exceed 160 KiB of LDS%s");
     if (ro->R == 0 || T == 0) return OFFSIM_OK;
-    return collect_launch<COLLECT_VF_NONE>(t, ro, pol->form, pol->form == OFFSIM_COLLECT_MLP ? pol->x_dtype : OFFSIM_F32, prob_mode, lds, A, stream);
+    return collect_launch<COLLECT_VF_NONE>(t, ro, pol->form, pol->form == OFFSIM_COLLECT_MLP ? pol->x_dtype : OFFSIM_F32, prob_mode, lds, A, stream,
+                                           1, ro->R);
 }
 
-extern "C" int offsim_vector_collect_ppo(const offsim_table *t, offsim_rollouts *ro, const offsim_collect_policy *pol, const offsim_collect_value *val,
-                                         int32_t prob_mode, int32_t reject_mode, int64_t T, int32_t max_episode_steps, const offsim_collect_state *st,
-                                         const offsim_collect_out *out, const offsim_collect_ppo_out *ppo, void *stream) {
+// offsim_vector_collect_ppo (L = 1, E = ro->R) and offsim_vector_collect_ppo_pop: L learners' stacked networks, E environments each.
+// `who` / `who_critic` name the entry point in the error text.
+static int collect_ppo_run(const char *who, const char *who_critic, const offsim_table *t, offsim_rollouts *ro, const offsim_collect_policy *pol,
+                           const offsim_collect_value *val, int L, int E, int32_t prob_mode, int32_t reject_mode, int64_t T,
+                           int32_t max_episode_steps, const offsim_collect_state *st, const offsim_collect_out *out,
+                           const offsim_collect_ppo_out *ppo, void *stream) {
     CollectPpoArgs A;
     size_t shared;
-    int rc = collect_prepare("vector_collect_ppo", t, ro, pol, prob_mode, reject_mode, T, max_episode_steps, st, out, A, shared);
+    int rc = collect_prepare(who, t, ro, pol, prob_mode, reject_mode, T, max_episode_steps, st, out, A, shared);
     if (rc) return rc;
     memset(&A.V, 0, sizeof(A.V));
-    if (!val || !ppo) return fail(OFFSIM_EINVAL, "vector_collect_ppo: val / ppo is NULL%s");
-    if (T > 0 && (!ppo->value || !ppo->logp || !ppo->final_value))
-        return fail(OFFSIM_EINVAL, "vector_collect_ppo: ppo->value / logp / final_value is NULL%s");
+    if (!val || !ppo) return fail(OFFSIM_EINVAL, "%s: val / ppo is NULL", who);
+    if (T > 0 && (!ppo->value || !ppo->logp || !ppo->final_value)) return fail(OFFSIM_EINVAL, "%s: ppo->value / logp / final_value is NULL", who);
     CollectValue &V = A.V;
     int x_dtype = pol->form == OFFSIM_COLLECT_MLP ? pol->x_dtype : OFFSIM_F32;
     if (val->form == OFFSIM_VALUE_MLP) {
-        rc = collect_mlp("vector_collect_ppo critic", t, *val, 1, V.mlp);
+        rc = collect_mlp(who_critic, t, *val, 1, V.mlp);
         if (rc) return rc;
         if (pol->form == OFFSIM_COLLECT_MLP && val->x_dtype != pol->x_dtype)
-            return fail(OFFSIM_EINVAL, "vector_collect_ppo: the actor and the critic read observations of different types%s");
+            return fail(OFFSIM_EINVAL, "%s: the actor and the critic read observations of different types", who);
         if (A.mlp.floats + V.mlp.floats > OFFSIM_COLLECT_MLP_MAX_FLOATS)
-            return fail(OFFSIM_EUNSUPPORTED, "vector_collect_ppo: the actor's and the critic's weights exceed OFFSIM_COLLECT_MLP_MAX_FLOATS (64 KiB of LDS)%s");
+            return fail(OFFSIM_EUNSUPPORTED, "%s: the actor's and the critic's weights exceed OFFSIM_COLLECT_MLP_MAX_FLOATS (64 KiB of LDS)", who);
         x_dtype = val->x_dtype;
         if (V.mlp.w_max > A.mlp.w_max) A.mlp.w_max = V.mlp.w_max;
         const size_t actor = (shared + 15) & ~(size_t)15;
         V.off_w = (uint32_t)((size_t)COLLECT_WAVES * (WAVE + 1) * sizeof(Jump) + actor);
         shared = actor + (size_t)V.mlp.floats * sizeof(float);
     } else if (val->form == OFFSIM_VALUE_ROWS) {
-        if (t->N > 0 && (!val->v_next || !val->v_init)) return fail(OFFSIM_EINVAL, "vector_collect_ppo: v_next / v_init is NULL%s");
+        if (t->N > 0 && (!val->v_next || !val->v_init)) return fail(OFFSIM_EINVAL, "%s: v_next / v_init is NULL", who);
         V.v_next = val->v_next;
         V.v_init = val->v_init;
     } else {
-        return fail(OFFSIM_EINVAL, "vector_collect_ppo: unknown critic form%s");
+        return fail(OFFSIM_EINVAL, "%s: unknown critic form", who);
     }
     V.rec = *ppo;
+    V.envs = E;
     const size_t lds = collect_lds_layout(COLLECT_WAVES, shared, A.mlp.w_max, A);
-    if (lds > 160 * 1024) return fail(OFFSIM_EUNSUPPORTED, "vector_collect_ppo: the policy table, the critic and per-wave scratch exceed 160 KiB of LDS%s");
+    if (lds > 160 * 1024) return fail(OFFSIM_EUNSUPPORTED, "%s: the policy table, the critic and per-wave scratch exceed 160 KiB of LDS", who);
     if (ro->R == 0 || T == 0) return OFFSIM_OK;
-    if (val->form == OFFSIM_VALUE_MLP) return collect_launch<OFFSIM_VALUE_MLP>(t, ro, pol->form, x_dtype, prob_mode, lds, A, stream);
-    return collect_launch<OFFSIM_VALUE_ROWS>(t, ro, pol->form, x_dtype, prob_mode, lds, A, stream);
+    if (val->form == OFFSIM_VALUE_MLP) return collect_launch<OFFSIM_VALUE_MLP>(t, ro, pol->form, x_dtype, prob_mode, lds, A, stream, L, E);
+    return collect_launch<OFFSIM_VALUE_ROWS>(t, ro, pol->form, x_dtype, prob_mode, lds, A, stream, L, E);
+}
+
+extern "C" int offsim_vector_collect_ppo(const offsim_table *t, offsim_rollouts *ro, const offsim_collect_policy *pol, const offsim_collect_value *val,
+                                         int32_t prob_mode, int32_t reject_mode, int64_t T, int32_t max_episode_steps, const offsim_collect_state *st,
+                                         const offsim_collect_out *out, const offsim_collect_ppo_out *ppo, void *stream) {
+    return collect_ppo_run("vector_collect_ppo", "vector_collect_ppo critic", t, ro, pol, val, 1, ro ? ro->R : 0, prob_mode, reject_mode, T,
+                           max_episode_steps, st, out, ppo, stream);
+}
+
+extern "C" int offsim_vector_collect_ppo_pop(const offsim_table *t, offsim_rollouts *ro, const offsim_collect_policy *pol,
+                                             const offsim_collect_value *val, int32_t L, int32_t E, int32_t prob_mode, int32_t reject_mode, int64_t T,
+                                             int32_t max_episode_steps, const offsim_collect_state *st, const offsim_collect_out *out,
+                                             const offsim_collect_ppo_out *ppo, void *stream) {
+    if (L <= 0 || E <= 0 || L > 65535) return fail(OFFSIM_EINVAL, "vector_collect_ppo_pop: L must be in 1..65535 and E >= 1%s");
+    if (!ro || !pol || !val) return fail(OFFSIM_EINVAL, "vector_collect_ppo_pop: ro / pol / val is NULL%s");
+    if ((int64_t)L * E != (int64_t)ro->R) return fail(OFFSIM_EINVAL, "vector_collect_ppo_pop: ro->R must be L * E%s");
+    if (pol->form != OFFSIM_COLLECT_MLP || val->form != OFFSIM_VALUE_MLP)
+        return fail(OFFSIM_EUNSUPPORTED, "vector_collect_ppo_pop: only OFFSIM_COLLECT_MLP actors and OFFSIM_VALUE_MLP critics%s");
+    return collect_ppo_run("vector_collect_ppo_pop", "vector_collect_ppo_pop critic", t, ro, pol, val, L, E, prob_mode, reject_mode, T,
+                           max_episode_steps, st, out, ppo, stream);
 }

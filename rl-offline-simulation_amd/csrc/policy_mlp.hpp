@@ -129,17 +129,18 @@ __device__ __forceinline__ float pmlp_in<__half>(const __half *x, int64_t i) { r
 // Stages a network for a kernel that keeps all of it in LDS (k_collect, k_ppo_grad), all nt threads of the workgroup striding: per layer
 // W [out][in] (read coalesced) -> W^T [in][ld[l]] at dst + woff[l], then b at dst + boff[l] (boff < 0: no bias).  N: that kernel's
 // descriptor, with W, b, in, out, woff, boff and n; nt: the workgroup's size as that kernel has it (blockDim.x, or its constant).
+// lrn: which network of a stacked population (W [L][out][in], b [L][out]; the descriptor is learner 0's); 0 for a single network.
 template <typename NET, typename NT>
-__device__ __forceinline__ void pmlp_stage(float *dst, const NET &N, const int *ld, int tid, NT nt) {
+__device__ __forceinline__ void pmlp_stage(float *dst, const NET &N, const int *ld, int tid, NT nt, int lrn = 0) {
     for (int l = 0; l < N.n; l++) {
         const int in = N.in[l], out = N.out[l], ldw = ld[l];
-        const float *__restrict__ W = N.W[l];
+        const float *__restrict__ W = N.W[l] + (size_t)lrn * in * out;
         for (int e = tid; e < in * out; e += nt) {
             const int j = e / in, k = e - j * in;
             dst[N.woff[l] + k * ldw + j] = W[e];
         }
         if (N.boff[l] >= 0)
-            for (int j = tid; j < out; j += nt) dst[N.boff[l] + j] = N.b[l][j];
+            for (int j = tid; j < out; j += nt) dst[N.boff[l] + j] = N.b[l][(size_t)lrn * out + j];
     }
 }
 

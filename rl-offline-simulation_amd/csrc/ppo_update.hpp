@@ -21,6 +21,12 @@
 //   k_ppo_finish          t += the steps taken.
 // Early stop: an actor pass whose kl exceeds 1.5 * target_kl sets a flag in scratch instead of stepping; every later launch reads the
 // flag first and returns.  Nothing waits on anything inside a kernel.
+//
+// A population (offsim_ppo_grad_pop, offsim_ppo_update_pop; POP instances of the same kernels) puts L independent learners on gridDim.y.
+// Learner l = blockIdx.y has the stacked network l (pmlp_stage's lrn), the records m' = t * E + e of its E environments at memory index
+// t * ld + l * E + e of the step-major [T, L * E] buffer (ppou_rec), its own scratch block (sized by the workgroups a learner really has,
+// ppou_pop_stride) with its own stop flag and hyperparameters (k_ppo_pop_init writes them), and its own rows of m, v, t, stats and
+// trace.  Tiles, their assignment to workgroups and every sum are those of the single learner on a contiguous [T * E] batch: same bits.
 #pragma once
 
 #define PPOU_THREADS 512
@@ -48,11 +54,26 @@ struct PpoBatchArgs {
     int64_t M;
     int dO, TM;
     float clip_lo, clip_hi;
+    int E;       // POP: environments per learner (M = T * E records per learner)
+    int64_t ld;  // POP: the records' row stride, L * E
 };
 
 // scratch (doubles): [OFFSIM_PPO_MAX_BLOCKS][8] partial sums | 8 control | partial gradients f32 [OFFSIM_PPO_MAX_BLOCKS][P]
 #define PPOU_CTRL (OFFSIM_PPO_MAX_BLOCKS * 8)
 #define PPOU_GPART (PPOU_CTRL + 8)
+// a population's scratch: per learner the same three parts for its nb workgroups, [nb][8] | 8 control | f32 [nb][P].  Control: the stop
+// flag (u32), then lr, kl_limit (f64) and clip_lo, clip_hi (two f32 in one double's place).
+__host__ __device__ __forceinline__ int64_t ppou_pop_stride(int nb, int P) { return OFFSIM_PPO_UPDATE_WORK_DOUBLES_NB(P, nb); }
+
+// memory index of a learner's record m
+template <bool POP>
+__device__ __forceinline__ int64_t ppou_rec(const PpoBatchArgs &B, int64_t m, int lrn) {
+    if constexpr (!POP) return m;
+    else {
+        const int64_t t = m / B.E;
+        return t * B.ld + (int64_t)lrn * B.E + (m - t * B.E);
+    }
+}
 
 __device__ __forceinline__ float ppou_dact(float h, int act, float slope) {  // the activation's derivative, from its output
     switch (act) {
@@ -63,9 +84,17 @@ __device__ __forceinline__ float ppou_dact(float h, int act, float slope) {  // 
     }
 }
 
-template <int KIND, typename XT>
+template <int KIND, typename XT, bool POP = false>
 __global__ void __launch_bounds__(PPOU_THREADS) k_ppo_grad(PpoNet N, PpoBatchArgs B, double *__restrict__ work) {
-    if (*(volatile const uint32_t *)(work + PPOU_CTRL) != 0u) return;  // the update stopped at an earlier pass
+    const int lrn = POP ? (int)blockIdx.y : 0;
+    const int ctrl = POP ? 8 * (int)gridDim.x : PPOU_CTRL;
+    if constexpr (POP) work += (size_t)lrn * ppou_pop_stride((int)gridDim.x, N.P);
+    if (*(volatile const uint32_t *)(work + ctrl) != 0u) return;  // the update stopped at an earlier pass
+    float clip_lo = B.clip_lo, clip_hi = B.clip_hi;
+    if constexpr (POP) {
+        clip_lo = ((const float *)(work + ctrl + 3))[0];
+        clip_hi = ((const float *)(work + ctrl + 3))[1];
+    }
     extern __shared__ __align__(16) unsigned char lds_raw[];
     float *w_lds = (float *)lds_raw;
     float *A = w_lds + N.w_floats;
@@ -74,7 +103,7 @@ __global__ void __launch_bounds__(PPOU_THREADS) k_ppo_grad(PpoNet N, PpoBatchArg
     const int tid = threadIdx.x, TM = B.TM, lda = N.lda, ldd = N.ldd, nl = N.n;
     const int nout = N.out[nl - 1];
 
-    pmlp_stage(w_lds, N, N.ldw, tid, PPOU_THREADS);
+    pmlp_stage(w_lds, N, N.ldw, tid, PPOU_THREADS, lrn);
     for (int e = tid; e < TM * lda; e += PPOU_THREADS) A[e] = 0.0f;
     for (int e = tid; e < TM * ldd; e += PPOU_THREADS) D[e] = 0.0f;
     __syncthreads();
@@ -113,28 +142,30 @@ __global__ void __launch_bounds__(PPOU_THREADS) k_ppo_grad(PpoNet N, PpoBatchArg
         // the tile's observations (0 past the end; an invalid record's row is zeros, whatever its obs holds)
         for (int e = tid; e < TM * B.dO; e += PPOU_THREADS) {
             const int m = e / B.dO, k = e - m * B.dO;
-            bool ok = m < tm && (!B.valid || B.valid[m0 + m]);
+            const int64_t mi = m < tm ? ppou_rec<POP>(B, m0 + m, lrn) : 0;
+            bool ok = m < tm && (!B.valid || B.valid[mi]);
             if constexpr (KIND == OFFSIM_PPO_ACTOR) {  // (an act outside [0, nA) makes the record invalid: its row is zeroed as well)
                 if (ok) {
-                    const int am = B.act[m0 + m];
+                    const int am = B.act[mi];
                     ok = am >= 0 && am < nout;
                 }
             }
-            A[m * lda + k] = ok ? pmlp_in<XT>((const XT *)B.obs, (m0 + m) * B.dO + k) : 0.0f;
+            A[m * lda + k] = ok ? pmlp_in<XT>((const XT *)B.obs, mi * B.dO + k) : 0.0f;
         }
         // the O thread's record
         bool ok = false;
         int a = 0;
         float adv = 0.0f, lpo = 0.0f, ret = 0.0f;
         if (tid < tm) {
-            ok = !B.valid || B.valid[m0 + tid];
+            const int64_t mi = ppou_rec<POP>(B, m0 + tid, lrn);
+            ok = !B.valid || B.valid[mi];
             if constexpr (KIND == OFFSIM_PPO_ACTOR) {
-                a = B.act[m0 + tid];
-                adv = B.adv[m0 + tid];
-                lpo = B.logp[m0 + tid];
+                a = B.act[mi];
+                adv = B.adv[mi];
+                lpo = B.logp[mi];
                 if (a < 0 || a >= nout) ok = false;
             } else {
-                ret = B.ret[m0 + tid];
+                ret = B.ret[mi];
             }
         }
         __syncthreads();
@@ -179,9 +210,9 @@ __global__ void __launch_bounds__(PPOU_THREADS) k_ppo_grad(PpoNet N, PpoBatchArg
                 const float lse = mx + logf(s);
                 const float logp = z[a] - lse;
                 const float ratio = expf(logp - lpo);
-                const float rc = fminf(fmaxf(ratio, B.clip_lo), B.clip_hi);
+                const float rc = fminf(fmaxf(ratio, clip_lo), clip_hi);
                 const float x = ratio * adv, y = rc * adv;
-                const bool inside = ratio >= B.clip_lo && ratio <= B.clip_hi;
+                const bool inside = ratio >= clip_lo && ratio <= clip_hi;
                 // d min(x, y) / d ratio: adv through x where x < y (or both, halved, where they are equal), through y inside the clip range
                 const float gr = (inside || x < y) ? adv : 0.0f;
                 const float dlogp = -gr * ratio;
@@ -244,7 +275,7 @@ __global__ void __launch_bounds__(PPOU_THREADS) k_ppo_grad(PpoNet N, PpoBatchArg
         }
         __syncthreads();
     }
-    float *gpart = (float *)(work + PPOU_GPART) + (size_t)blockIdx.x * N.P;
+    float *gpart = (float *)(work + ctrl + 8) + (size_t)blockIdx.x * N.P;
 #pragma unroll
     for (int i = 0; i < PPOU_OWN; i++) {
         const int p = tid + PPOU_THREADS * i;
@@ -272,13 +303,30 @@ struct PpoAdamArgs {
     double *stats, *trace;  // update: stats [6], trace [iters][2]; grad: stats [5]
     float *grad_out;
     int iter, kind, nblocks;
+    int iters;  // POP: the rows of a learner's trace
 };
 
 #define PPOU_ADAM_BLOCK 256
 
-template <bool STEP>
+template <bool STEP, bool POP = false>
 __global__ void __launch_bounds__(PPOU_ADAM_BLOCK) k_ppo_adam(PpoNet N, PpoAdamArgs O, double *__restrict__ work) {
-    volatile uint32_t *stop_flag = (volatile uint32_t *)(work + PPOU_CTRL);
+    const int lrn = POP ? (int)blockIdx.y : 0;
+    const int ctrl = POP ? 8 * O.nblocks : PPOU_CTRL;
+    if constexpr (POP) {  // the learner's scratch, hyperparameters and rows of the outputs and the optimiser state
+        work += (size_t)lrn * ppou_pop_stride(O.nblocks, N.P);
+        O.lr = work[ctrl + 1];
+        O.kl_limit = work[ctrl + 2];
+        O.stats += (size_t)lrn * (STEP ? 6 : 5);
+        if (STEP) {
+            O.trace += (size_t)lrn * O.iters * 2;
+            O.m += (size_t)lrn * N.P;
+            O.v += (size_t)lrn * N.P;
+            O.t += lrn;
+        } else {
+            O.grad_out += (size_t)lrn * N.P;
+        }
+    }
+    volatile uint32_t *stop_flag = (volatile uint32_t *)(work + ctrl);
     if (STEP && *stop_flag != 0u) return;
     __shared__ double sh[5];
     if (threadIdx.x < 5) {
@@ -314,7 +362,7 @@ __global__ void __launch_bounds__(PPOU_ADAM_BLOCK) k_ppo_adam(PpoNet N, PpoAdamA
     if (stop) return;
     const int p = blockIdx.x * PPOU_ADAM_BLOCK + threadIdx.x;
     if (p >= N.P) return;
-    const float *gpart = (const float *)(work + PPOU_GPART);
+    const float *gpart = (const float *)(work + ctrl + 8);
     double gs = 0.0;
     for (int b = 0; b < O.nblocks; b++) gs += (double)gpart[(size_t)b * N.P + p];
     const double gd = n > 0.0 ? gs / n : 0.0;
@@ -324,7 +372,7 @@ __global__ void __launch_bounds__(PPOU_ADAM_BLOCK) k_ppo_adam(PpoNet N, PpoAdamA
         int l = 0;
         while (l + 1 < N.n && p >= N.goff[l + 1]) l++;
         const int e = p - N.goff[l], nw = N.in[l] * N.out[l];
-        float *q = e < nw ? N.W[l] + e : N.b[l] + (e - nw);
+        float *q = e < nw ? N.W[l] + (size_t)lrn * nw + e : N.b[l] + (size_t)lrn * N.out[l] + (e - nw);
         // torch.optim.Adam, defaults: b1 = 0.9, b2 = 0.999, eps = 1e-8, no weight decay; f64 arithmetic on the f32 state
         const double b1 = 0.9, b2 = 0.999, eps = 1e-8;
         const double t = (double)(*O.t + O.iter + 1);
@@ -343,6 +391,32 @@ __global__ void __launch_bounds__(PPOU_ADAM_BLOCK) k_ppo_adam(PpoNet N, PpoAdamA
 __global__ void k_ppo_finish(int64_t *t, const double *stats, const double *work, int iters) {
     const bool stopped = *(const uint32_t *)(work + PPOU_CTRL) != 0u;
     *t += stopped ? (int64_t)stats[5] : (int64_t)iters;
+}
+// the same for every learner of a population (its flag at work + l * stride + ctrl)
+__global__ void k_ppo_finish_pop(int64_t *t, const double *stats, const double *work, int iters, int L, int64_t stride, int ctrl) {
+    const int l = blockIdx.x * blockDim.x + threadIdx.x;
+    if (l >= L) return;
+    const bool stopped = *(const uint32_t *)(work + (size_t)l * stride + ctrl) != 0u;
+    t[l] += stopped ? (int64_t)stats[6 * (size_t)l + 5] : (int64_t)iters;
+}
+
+// A population's control blocks: the stop flags cleared and the learners' hyperparameters, PPOU_POP_CHUNK learners per launch by value
+// (host arrays reach the device without a copy the host would have to wait for).
+#define PPOU_POP_CHUNK 64
+struct PpoPopHyper {
+    double lr[PPOU_POP_CHUNK], kl_limit[PPOU_POP_CHUNK];
+    float clip_lo[PPOU_POP_CHUNK], clip_hi[PPOU_POP_CHUNK];
+    int l0, n;
+};
+__global__ void k_ppo_pop_init(PpoPopHyper H, double *work, int64_t stride, int ctrl) {
+    const int i = threadIdx.x;
+    if (i >= H.n) return;
+    double *c = work + (size_t)(H.l0 + i) * stride + ctrl;
+    *(uint64_t *)c = 0ull;
+    c[1] = H.lr[i];
+    c[2] = H.kl_limit[i];
+    ((float *)(c + 3))[0] = H.clip_lo[i];
+    ((float *)(c + 3))[1] = H.clip_hi[i];
 }
 
 // The network (pmlp_describe's checks) and the batch of an update, and k_ppo_grad's / k_ppo_adam's layouts of them.
@@ -412,16 +486,18 @@ static int ppou_prepare(const char *who, const offsim_ppo_net *net, int32_t kind
 }
 
 static unsigned ppou_blocks(const PpoBatchArgs &B) {
-    const int64_t nt = (B.M + B.TM - 1) / B.TM;
+    const int64_t nt = B.M / B.TM + (B.M % B.TM != 0);  // (no overflow at any M: the sizing function takes INT64_MAX)
     return (unsigned)(nt < OFFSIM_PPO_MAX_BLOCKS ? nt : OFFSIM_PPO_MAX_BLOCKS);
 }
 
-static int ppou_launch_grad(int32_t kind, int32_t x_dtype, const PpoNet &N, const PpoBatchArgs &B, size_t lds, double *work, hipStream_t s) {
-    dim3 grid(ppou_blocks(B)), block(PPOU_THREADS);
-#define LAUNCH_PPOU(KIND, XT)                                                                \
-    do {                                                                                     \
-        if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_ppo_grad<KIND, XT>), (int)lds));       \
-        hipLaunchKernelGGL((k_ppo_grad<KIND, XT>), grid, block, lds, s, N, B, work);         \
+// POP: L learners on gridDim.y (B.M, B.E, B.ld: a learner's records)
+template <bool POP = false>
+static int ppou_launch_grad(int32_t kind, int32_t x_dtype, const PpoNet &N, const PpoBatchArgs &B, size_t lds, double *work, hipStream_t s, int L = 1) {
+    dim3 grid(ppou_blocks(B), (unsigned)L), block(PPOU_THREADS);
+#define LAUNCH_PPOU(KIND, XT)                                                                     \
+    do {                                                                                          \
+        if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_ppo_grad<KIND, XT, POP>), (int)lds));       \
+        hipLaunchKernelGGL((k_ppo_grad<KIND, XT, POP>), grid, block, lds, s, N, B, work);         \
     } while (0)
     if (kind == OFFSIM_PPO_ACTOR) {
         if (x_dtype == OFFSIM_F32) LAUNCH_PPOU(OFFSIM_PPO_ACTOR, float);
@@ -515,6 +591,136 @@ extern "C" int offsim_ppo_update(const offsim_ppo_net *net, int32_t kind, const 
         LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(k_ppo_finish, dim3(1), dim3(1), 0, s, opt->t, (const double *)stats, (const double *)work, (int)iters);
+    LAUNCH_CHECK();
+    return OFFSIM_OK;
+}
+
+// ---- a population of L learners (include/offsim.h: offsim_ppo_grad_pop, offsim_ppo_update_pop) ----
+
+// ppou_prepare for a population: batch->M = T * L * E records of the step-major [T, L * E] buffer; B describes ONE learner's T * E.
+static int ppou_prepare_pop(const char *who, const offsim_ppo_net *net, int32_t kind, const offsim_ppo_batch *bt, int32_t L, int32_t E, PpoNet &N,
+                            PpoBatchArgs &B, size_t &lds) {
+    if (L <= 0 || E <= 0 || L > 65535) return fail(OFFSIM_EINVAL, "%s: L must be in 1..65535 and E >= 1", who);
+    int rc = ppou_prepare(who, net, kind, bt, N, B, lds);
+    if (rc) return rc;
+    if (bt->M % ((int64_t)L * E) != 0) return fail(OFFSIM_EINVAL, "%s: M must be T * L * E", who);
+    B.M = bt->M / L;
+    B.E = E;
+    B.ld = (int64_t)L * E;
+    return OFFSIM_OK;
+}
+
+// the control blocks of all learners; lr / target_kl NULL (offsim_ppo_grad_pop): zeros
+static int ppou_pop_init(int L, const double *lr, const double *clip_ratio, const double *target_kl, double *work, int64_t stride, int ctrl, hipStream_t s) {
+    for (int l0 = 0; l0 < L; l0 += PPOU_POP_CHUNK) {
+        PpoPopHyper H;
+        memset(&H, 0, sizeof(H));
+        H.l0 = l0;
+        H.n = L - l0 < PPOU_POP_CHUNK ? L - l0 : PPOU_POP_CHUNK;
+        for (int i = 0; i < H.n; i++) {
+            H.lr[i] = lr ? lr[l0 + i] : 0.0;
+            H.kl_limit[i] = target_kl ? 1.5 * target_kl[l0 + i] : 0.0;
+            H.clip_lo[i] = (float)(1.0 - clip_ratio[l0 + i]);
+            H.clip_hi[i] = (float)(1.0 + clip_ratio[l0 + i]);
+        }
+        hipLaunchKernelGGL(k_ppo_pop_init, dim3(1), dim3(PPOU_POP_CHUNK), 0, s, H, work, stride, ctrl);
+        LAUNCH_CHECK();
+    }
+    return OFFSIM_OK;
+}
+
+extern "C" int64_t offsim_ppo_update_work_doubles_pop(const offsim_ppo_net *net, int32_t L, int64_t M) {
+    if (!net || !net->layers_host || net->n_layers < 1) return fail(OFFSIM_EINVAL, "ppo_update_work_doubles_pop: net is NULL or has no layers%s");
+    if (L <= 0 || M < 0) return fail(OFFSIM_EINVAL, "ppo_update_work_doubles_pop: L must be >= 1 and M >= 0%s");
+    offsim_ppo_batch bt;
+    memset(&bt, 0, sizeof(bt));
+    bt.x_dtype = OFFSIM_F32;
+    bt.dO = net->layers_host[0].in;
+    PpoNet N;
+    PpoBatchArgs B;
+    size_t lds;
+    int rc = ppou_prepare("ppo_update_work_doubles_pop", net, OFFSIM_PPO_ACTOR, &bt, N, B, lds);  // (any last width up to 16: a critic's too)
+    if (rc) return rc;
+    B.M = M;
+    const unsigned nb = ppou_blocks(B);
+    return (int64_t)L * ppou_pop_stride(nb ? (int)nb : 1, N.P);
+}
+
+extern "C" int offsim_ppo_grad_pop(const offsim_ppo_net *net, int32_t kind, const offsim_ppo_batch *batch, int32_t L, int32_t E,
+                                   const double *clip_ratio, float *grad, double *stats, double *work, void *stream) {
+    PpoNet N;
+    PpoBatchArgs B;
+    size_t lds;
+    int rc = ppou_prepare_pop("ppo_grad_pop", net, kind, batch, L, E, N, B, lds);
+    if (rc) return rc;
+    if (!clip_ratio) return fail(OFFSIM_EINVAL, "ppo_grad_pop: clip_ratio is NULL%s");
+    for (int l = 0; l < L; l++)
+        if (!ppou_clip_ok(clip_ratio[l])) return fail(OFFSIM_EINVAL, "ppo_grad_pop: every clip_ratio must be in [0, 1)%s");
+    if (B.M == 0) return OFFSIM_OK;
+    if (!grad || !stats || !work) return fail(OFFSIM_EINVAL, "ppo_grad_pop: grad / stats / work is NULL%s");
+    hipStream_t s = (hipStream_t)stream;
+    const int nb = (int)ppou_blocks(B);
+    const int64_t stride = ppou_pop_stride(nb, N.P);
+    rc = ppou_pop_init(L, nullptr, clip_ratio, nullptr, work, stride, 8 * nb, s);
+    if (rc) return rc;
+    rc = ppou_launch_grad<true>(kind, batch->x_dtype, N, B, lds, work, s, L);
+    if (rc) return rc;
+    PpoAdamArgs O;
+    memset(&O, 0, sizeof(O));
+    O.stats = stats;
+    O.grad_out = grad;
+    O.kind = kind;
+    O.nblocks = nb;
+    hipLaunchKernelGGL((k_ppo_adam<false, true>), dim3((N.P + PPOU_ADAM_BLOCK - 1) / PPOU_ADAM_BLOCK, (unsigned)L), dim3(PPOU_ADAM_BLOCK), 0, s, N, O,
+                       work);
+    LAUNCH_CHECK();
+    return OFFSIM_OK;
+}
+
+extern "C" int offsim_ppo_update_pop(const offsim_ppo_net *net, int32_t kind, const offsim_ppo_batch *batch, int32_t L, int32_t E,
+                                     const double *clip_ratio, const double *target_kl, int32_t iters, const offsim_ppo_adam_pop *opt, double *stats,
+                                     double *trace, double *work, void *stream) {
+    PpoNet N;
+    PpoBatchArgs B;
+    size_t lds;
+    int rc = ppou_prepare_pop("ppo_update_pop", net, kind, batch, L, E, N, B, lds);
+    if (rc) return rc;
+    if (!clip_ratio || !target_kl || !opt || !opt->lr) return fail(OFFSIM_EINVAL, "ppo_update_pop: clip_ratio / target_kl / opt / opt->lr is NULL%s");
+    for (int l = 0; l < L; l++) {
+        if (!ppou_clip_ok(clip_ratio[l])) return fail(OFFSIM_EINVAL, "ppo_update_pop: every clip_ratio must be in [0, 1)%s");
+        if (!(target_kl[l] >= 0.0)) return fail(OFFSIM_EINVAL, "ppo_update_pop: every target_kl must be >= 0%s");
+        if (!(opt->lr[l] >= 0.0)) return fail(OFFSIM_EINVAL, "ppo_update_pop: every lr must be >= 0%s");
+    }
+    if (iters < 0) return fail(OFFSIM_EINVAL, "ppo_update_pop: iters must be >= 0%s");
+    if (B.M == 0 || iters == 0) return OFFSIM_OK;
+    if (!opt->m || !opt->v || !opt->t) return fail(OFFSIM_EINVAL, "ppo_update_pop: opt->m / v / t is NULL%s");
+    if (!stats || !trace || !work) return fail(OFFSIM_EINVAL, "ppo_update_pop: stats / trace / work is NULL%s");
+    hipStream_t s = (hipStream_t)stream;
+    const int nb = (int)ppou_blocks(B);
+    const int64_t stride = ppou_pop_stride(nb, N.P);
+    rc = ppou_pop_init(L, opt->lr, clip_ratio, target_kl, work, stride, 8 * nb, s);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(trace, 0xff, (size_t)L * iters * 2 * sizeof(double), s));  // passes that never ran stay NaN
+    PpoAdamArgs O;
+    memset(&O, 0, sizeof(O));
+    O.m = opt->m;
+    O.v = opt->v;
+    O.t = opt->t;
+    O.stats = stats;
+    O.trace = trace;
+    O.kind = kind;
+    O.nblocks = nb;
+    O.iters = iters;
+    const dim3 agrid((N.P + PPOU_ADAM_BLOCK - 1) / PPOU_ADAM_BLOCK, (unsigned)L);
+    for (int i = 0; i < iters; i++) {
+        rc = ppou_launch_grad<true>(kind, batch->x_dtype, N, B, lds, work, s, L);
+        if (rc) return rc;
+        O.iter = i;
+        hipLaunchKernelGGL((k_ppo_adam<true, true>), agrid, dim3(PPOU_ADAM_BLOCK), 0, s, N, O, work);
+        LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_ppo_finish_pop, dim3((L + 255) / 256), dim3(256), 0, s, opt->t, (const double *)stats, (const double *)work, (int)iters, (int)L,
+                       stride, 8 * nb);
     LAUNCH_CHECK();
     return OFFSIM_OK;
 }

@@ -7,3 +7,4 @@ from .vector_env import VectorPSRS  # noqa: F401
 from .obs_policy import MLPPolicy, RowPolicy, CallablePolicy, MLPValue, RowValue  # noqa: F401
 from .ppo_buffer import PPOBatch, ppo_advantages  # noqa: F401
 from .ppo_learner import PPOLearner, PPOUpdateInfo, ppo_grad  # noqa: F401
+from .ppo_population import PPOPopulation, ppo_grad_population  # noqa: F401

@@ -20,7 +20,9 @@ class PPOBatch(namedtuple("PPOBatch", "obs act rew val logp adv adv_raw ret vali
     obs (the observation the actor was asked at), act, rew (f32), val (v(obs)), logp (of act), adv (normalised when collect_ppo's
     normalize, else adv_raw), adv_raw, ret, valid (a transition was served), final_value [E] (v at the observation each environment
     holds after the call: the bootstrap of its open path), v_trunc (bootstrap="spinup": v(next_obs) at truncating steps, else None),
-    adv_mean / adv_std (0-dim f64: mpi_statistics_scalar of adv_raw; 0 / 0 without normalize) and collected (collect's Collected)."""
+    adv_mean / adv_std (0-dim f64: mpi_statistics_scalar of adv_raw; 0 / 0 without normalize) and collected (collect's Collected).
+    From VectorPSRS.collect_ppo_population the E axis holds L learners' environments, learner-major, adv is normalised per learner and
+    adv_mean / adv_std are [L]."""
 
     def flat(self):
         """The valid entries, environment-major then time -- E spinup buffers concatenated, what PPOBuffer.get hands to
@@ -33,10 +35,13 @@ class PPOBatch(namedtuple("PPOBatch", "obs act rew val logp adv adv_raw ret vali
         return out
 
 
-def _advantages(rew, val, flags, final_value, v_trunc, gamma, lam, normalize, bootstrap):
-    """offsim_ppo_advantages on [T, E] device tensors: (adv_raw, ret, adv (normalised or adv_raw), mean, std)."""
+def _advantages(rew, val, flags, final_value, v_trunc, gamma, lam, normalize, bootstrap, learners=None):
+    """offsim_ppo_advantages on [T, E] device tensors: (adv_raw, ret, adv (normalised or adv_raw), mean, std).  learners = L: the columns
+    are L learners' environments, learner-major, normalised per learner (offsim_ppo_advantages_pop); mean and std are then [L]."""
     T, E = int(rew.shape[0]), int(rew.shape[1])
     dev = rew.device
+    if learners is not None:
+        return _advantages_pop(rew, val, flags, final_value, v_trunc, gamma, lam, normalize, bootstrap, T, int(learners), E // int(learners))
     adv_raw = torch.empty((T, E), dtype=torch.float32, device=dev)
     ret = torch.empty((T, E), dtype=torch.float32, device=dev)
     adv = torch.empty((T, E), dtype=torch.float32, device=dev) if normalize else adv_raw
@@ -51,6 +56,22 @@ def _advantages(rew, val, flags, final_value, v_trunc, gamma, lam, normalize, bo
     if normalize and not n:  # (nothing launched: no valid entry, mean = std = 0)
         stats.zero_()
     return adv_raw, ret, adv, stats[0], stats[1]
+
+
+def _advantages_pop(rew, val, flags, final_value, v_trunc, gamma, lam, normalize, bootstrap, T, nl, E):
+    dev = rew.device
+    adv_raw = torch.empty((T, nl * E), dtype=torch.float32, device=dev)
+    ret = torch.empty((T, nl * E), dtype=torch.float32, device=dev)
+    adv = torch.empty((T, nl * E), dtype=torch.float32, device=dev) if normalize else adv_raw
+    stats = torch.zeros((nl, 2), dtype=torch.float64, device=dev)
+    work = torch.empty(nl * L.ppo_work_doubles(E), dtype=torch.float64, device=dev) if normalize else None
+    n = T * E
+    L.check(L.load().offsim_ppo_advantages_pop(L.ptr(rew) if n else None, L.ptr(val) if n else None, L.ptr(flags) if n else None,
+                                               L.ptr(final_value), L.ptr(v_trunc) if v_trunc is not None and n else None, T, nl, E,
+                                               float(gamma), float(lam), _BOOT[bootstrap], L.ptr(adv_raw) if n else None, L.ptr(ret) if n else None,
+                                               L.ptr(adv) if normalize and n else None, L.ptr(stats) if normalize else None,
+                                               L.ptr(work) if normalize else None, L.stream_ptr()))
+    return adv_raw, ret, adv, stats[:, 0], stats[:, 1]
 
 
 PPOAdvantages = namedtuple("PPOAdvantages", "adv adv_raw ret mean std")

@@ -215,9 +215,10 @@ class VectorPSRS:
         pol, keep, f32 = self._collect_policy(policy, form)
         return self._collect_launch(pol, keep, f32, T, cap, record_obs, record_probs)
 
-    def _collect_launch(self, pol, keep, f32, T, cap, record_obs, record_probs, ppo=None):
-        """offsim_vector_collect (ppo None) or offsim_vector_collect_ppo (ppo = (offsim_collect_value, offsim_collect_ppo_out)) over T steps;
-        returns the Collected records."""
+    def _collect_launch(self, pol, keep, f32, T, cap, record_obs, record_probs, ppo=None, learners=None):
+        """offsim_vector_collect (ppo None) or offsim_vector_collect_ppo (ppo = (offsim_collect_value, offsim_collect_ppo_out)) over T steps --
+        offsim_vector_collect_ppo_pop where the environments are those of `learners` learners with stacked networks; returns the
+        Collected records."""
         env, t = self.env, self.table
         E, dev = self.num_envs, t.device
         row = torch.empty((T, E), dtype=torch.int32, device=dev)
@@ -234,6 +235,10 @@ class VectorPSRS:
         if ppo is None:
             L.check(L.load().offsim_vector_collect(C.byref(t.c), C.byref(env.state.c), C.byref(pol), L.PROB_F32 if f32 else L.PROB_F64,
                                                    env.reject_mode, T, cap, C.byref(st), C.byref(out), L.stream_ptr()))
+        elif learners is not None:
+            L.check(L.load().offsim_vector_collect_ppo_pop(C.byref(t.c), C.byref(env.state.c), C.byref(pol), C.byref(ppo[0]), learners, E // learners,
+                                                           L.PROB_F32 if f32 else L.PROB_F64, env.reject_mode, T, cap, C.byref(st), C.byref(out),
+                                                           C.byref(ppo[1]), L.stream_ptr()))
         else:
             L.check(L.load().offsim_vector_collect_ppo(C.byref(t.c), C.byref(env.state.c), C.byref(pol), C.byref(ppo[0]),
                                                        L.PROB_F32 if f32 else L.PROB_F64, env.reject_mode, T, cap, C.byref(st), C.byref(out),
@@ -272,7 +277,6 @@ class VectorPSRS:
 
         Returns a PPOBatch of step-major [T, E] device tensors (flat() gives the loss inputs of ppo.py:_compute_loss_pi / _v).  The sampler
         state, observations and episode counters carry over exactly as for collect: the trajectory is collect's."""
-        from .ppo_buffer import PPOBatch, _advantages
         T = int(num_steps)
         if T < 0:
             raise ValueError(f"collect_ppo: num_steps must be >= 0, got {num_steps}")
@@ -282,7 +286,7 @@ class VectorPSRS:
         if bootstrap not in ("reference", "spinup"):
             raise ValueError(f"collect_ppo: bootstrap must be 'reference' or 'spinup', got {bootstrap!r}")
         env, t = self.env, self.table
-        E, dev = self.num_envs, t.device
+        dev = t.device
         env._quiesce()
         env._orders_for_generic()
         pol, keep, f32 = self._collect_policy(actor, form)
@@ -295,18 +299,58 @@ class VectorPSRS:
             keep += [vn, v0]
         else:
             raise TypeError(f"collect_ppo: the critic must be an MLPValue or a RowValue, got {type(critic).__name__}")
+        return self._collect_ppo_records(pol, val, keep, f32, T, cap, gamma, lam, normalize, bootstrap)
+
+    def _collect_ppo_records(self, pol, val, keep, f32, T, cap, gamma, lam, normalize, bootstrap, learners=None):
+        """The launch and the advantages of collect_ppo / collect_ppo_population from the actor's and the critic's descriptors."""
+        from .ppo_buffer import PPOBatch, _advantages
+        E, dev = self.num_envs, self.table.device
         value = torch.zeros((T, E), dtype=torch.float32, device=dev)
         logp = torch.zeros((T, E), dtype=torch.float32, device=dev)
         final_value = torch.zeros((E,), dtype=torch.float32, device=dev)
         v_trunc = torch.zeros((T, E), dtype=torch.float32, device=dev) if bootstrap == "spinup" else None
         out = L.CollectPPOOut(value=L.ptr(value), logp=L.ptr(logp), final_value=L.ptr(final_value), v_trunc=L.ptr(v_trunc))
-        c = self._collect_launch(pol, keep, f32, T, cap, True, True, ppo=(val, out))
+        c = self._collect_launch(pol, keep, f32, T, cap, True, True, ppo=(val, out), learners=learners)
         rew = c.reward.to(torch.float32)
         flags = ((c.row >= 0).to(torch.uint8) * L.COLLECT_SERVED + c.terminated.to(torch.uint8) * L.COLLECT_TERMINATED
                  + c.truncated.to(torch.uint8) * L.COLLECT_TRUNCATED).to(torch.uint8)
-        adv_raw, ret, adv, mean, std = _advantages(rew, value, flags, final_value, v_trunc, gamma, lam, normalize, bootstrap)
+        adv_raw, ret, adv, mean, std = _advantages(rew, value, flags, final_value, v_trunc, gamma, lam, normalize, bootstrap, learners)
         return PPOBatch(obs=c.obs, act=c.action, rew=rew, val=value, logp=logp, adv=adv, adv_raw=adv_raw, ret=ret, valid=c.row >= 0,
                         final_value=final_value, v_trunc=v_trunc, adv_mean=mean, adv_std=std, collected=c)
+
+    def collect_ppo_population(self, population, num_steps, max_episode_steps=500, gamma=0.99, lam=0.97, normalize=True, bootstrap="reference",
+                               form="auto"):
+        """collect_ppo for a PPOPopulation of L learners in the same launches (offsim_vector_collect_ppo_pop, offsim_ppo_advantages_pop): the
+        num_envs = L * E environments are the learners', learner-major -- environment r belongs to learner r // E and runs that learner's
+        actor and critic out of the population's stacked device weights.  The keyword arguments are collect_ppo's (form: "auto" or "mlp",
+        the networks run inside the kernel).  Returns a PPOBatch over [T, L * E]: learner l's buffer is the columns l * E .. (l + 1) * E - 1,
+        adv is normalised per learner, and adv_mean / adv_std are [L]; PPOPopulation.update consumes it as it is.  Every environment's
+        records and carried state are those of collect_ppo with its learner's networks, bit for bit; the sampler state, observations and
+        episode counters carry over as for collect_ppo, so the call mixes with reset, collect and the rest."""
+        from .ppo_population import PPOPopulation
+        if not isinstance(population, PPOPopulation):
+            raise TypeError(f"collect_ppo_population: needs a PPOPopulation, got {type(population).__name__}")
+        nl = population.L
+        if self.num_envs % nl or self.num_envs == 0:
+            raise ValueError(f"collect_ppo_population: num_envs = {self.num_envs} must be a positive multiple of the population's {nl} learners")
+        T = int(num_steps)
+        if T < 0:
+            raise ValueError(f"collect_ppo_population: num_steps must be >= 0, got {num_steps}")
+        cap = 0 if max_episode_steps is None else int(max_episode_steps)
+        if cap < 0 or cap >= 1 << 31:
+            raise ValueError(f"collect_ppo_population: max_episode_steps must be None or in [0, 2**31), got {max_episode_steps} (0 = no limit)")
+        if bootstrap not in ("reference", "spinup"):
+            raise ValueError(f"collect_ppo_population: bootstrap must be 'reference' or 'spinup', got {bootstrap!r}")
+        if form not in ("auto", "mlp"):
+            raise ValueError(f"collect_ppo_population: form must be 'auto' or 'mlp', got {form!r}")
+        env, t = self.env, self.table
+        env._quiesce()
+        env._orders_for_generic()
+        pi, v = population._stacks(t.device)
+        pol, val = L.CollectPolicy(), L.CollectValue()
+        keep = self._collect_mlp(pol, L.COLLECT_MLP, pi, "collect_ppo_population: the actors") + \
+            self._collect_mlp(val, L.VALUE_MLP, v, "collect_ppo_population: the critics")
+        return self._collect_ppo_records(pol, val, keep, t.p_log.dtype == torch.float32, T, cap, gamma, lam, normalize, bootstrap, learners=nl)
 
     def _collect_policy(self, policy, form):
         """offsim_collect_policy for collect / collect_ppo: (struct, tensors to keep alive, whether p_new is compared in f32)."""
@@ -353,7 +397,7 @@ class VectorPSRS:
         if net.dO != x_next.shape[1]:
             raise ValueError(f"{what} takes observations of width {net.dO}, the log's have {x_next.shape[1]}")
         x_start = self.obs.reshape(self.num_envs, -1).to(x_next.dtype).contiguous()
-        ws, arr = net._device_weights(self.table.device)
+        ws, arr = net._device_weights(self.table.device)  # (a population's stack: learner 0's descriptor of the stacked tensors)
         c.form, c.n_layers, c.layers_host = form, len(ws), C.cast(arr, C.POINTER(L.MLPLayer))
         c.activation, c.slope = _ACT[net.activation], net.slope
         c.x_dtype, c.dO = (L.F32 if x_next.dtype == torch.float32 else L.F16), net.dO
