@@ -854,6 +854,56 @@ int offsim_homer_grad(const offsim_homer_net *net, const offsim_homer_batch *bat
 int offsim_homer_step(const offsim_homer_net *net, const offsim_homer_batch *batch, double tau, double max_grad_norm,
                       const offsim_homer_adam *adam, double *stats, double *work, void *stream);
 
+/* offsim_homer_grad_pop / offsim_homer_step_pop: offsim_homer_grad / offsim_homer_step for a population of L independent encoders of one
+ * architecture, in the same number of launches as for one (the learner is the grid's y dimension).  net: the stacked networks, every
+ * tensor with a leading learner axis (enc_W1 [L, H, dO], enc_b1 [L, H], ..., cls_b2 [L, 2]); the struct describes learner 0 and learner
+ * l's tensor is at base + l * numel.  batch: obs / next_obs / act / n_rows are shared by all learners; every learner has its own M
+ * records, idx_real / idx_impo [L, M] i32 and noise [L, M, 4, nZ] f32 (or NULL: zeros) with an explicit learner stride in records,
+ * idx_stride >= M: learner l's record m is at idx[l * idx_stride + m] and its noise at (l * idx_stride + m) * 4 * nZ, so a batch is a
+ * column slice [:, lo:hi] of an epoch's arrays with no copy.  tau and hard are shared.  active: [L] u8 on the device, or NULL for all
+ * active; every launch of learner l reads active[l] first and returns when it is 0, and nothing of that learner is written (weights,
+ * m, v, t, its rows of grad and stats).  Per learner, the tile size, the assignment of tiles to min(tiles, OFFSIM_HOMER_MAX_BLOCKS)
+ * workgroups, the f32 partials, the f64 block-order reduction, the norm tree and the Adam arithmetic are those of the single call on the
+ * same M, so every learner's results equal the single call's bit for bit.  The LDS budget and OFFSIM_HOMER_MAX_FLOATS are per learner.
+ *   offsim_homer_grad_pop  grad [L, P] f32 or NULL (forward only; hard != 0 requires NULL), stats [L, 2] f64.  Two launches.
+ *   offsim_homer_step_pop  adam: m, v [L, P] f32, t [L] i64, and lr, weight_decay, max_grad_norm [L] f64, all on the DEVICE (the caller
+ *                          keeps them >= 0); stats [L, 3] f64.  A learner whose batch has no valid record changes nothing of its own
+ *                          (t[l] included) and does not disturb the others.  Three launches.
+ * No float atomics, no cooperative launch; no kernel waits for another workgroup.
+ * work: offsim_homer_work_doubles_pop(net, L, M) doubles of device scratch, M the records of ONE learner: per learner
+ * OFFSIM_HOMER_WORK_DOUBLES_NB(P, nb) for the nb = min(tiles, OFFSIM_HOMER_MAX_BLOCKS) workgroups the learner really has at that M (a
+ * caller that does not know M passes INT64_MAX and gets the size for OFFSIM_HOMER_MAX_BLOCKS, which serves every M); a negative return
+ * is an error code.  L in 1..65535.  Argument validation happens before any HIP call (L, idx_stride < M, hard with a grad pointer, and
+ * all that offsim_homer_grad refuses: OFFSIM_EINVAL; the budgets: OFFSIM_EUNSUPPORTED); M = 0 launches nothing.  Asynchronous on
+ * `stream`, capturable. */
+#define OFFSIM_HOMER_WORK_DOUBLES_NB(P, NB) ((NB) * 2 + 8 + ((P) + 255) / 256 + ((P) + 1) / 2 + (NB) * (((P) + 1) / 2))
+typedef struct offsim_homer_batch_pop {
+    const void *obs;                   /* [n_rows, dO] f32 or f16 (x_dtype), shared                 */
+    const void *next_obs;              /* [n_rows, dO], shared                                      */
+    int32_t x_dtype;
+    int32_t reserved;
+    const int32_t *act;                /* [n_rows], shared                                          */
+    int64_t n_rows;
+    const int32_t *idx_real;           /* [L, M], rows idx_stride apart                             */
+    const int32_t *idx_impo;           /* [L, M], rows idx_stride apart                             */
+    const float *noise;                /* [L, M, 4, nZ], learners idx_stride records apart, or NULL */
+    int64_t M;                         /* records per learner                                       */
+    int64_t idx_stride;                /* >= M, in records                                          */
+} offsim_homer_batch_pop;
+typedef struct offsim_homer_adam_pop {
+    float *m;                          /* [L,P] in/out                                              */
+    float *v;                          /* [L,P] in/out                                              */
+    int64_t *t;                        /* [L] in/out: every learner's Adam step count               */
+    const double *lr;                  /* [L] device array                                          */
+    const double *weight_decay;        /* [L] device array                                          */
+    const double *max_grad_norm;       /* [L] device array                                          */
+} offsim_homer_adam_pop;
+int64_t offsim_homer_work_doubles_pop(const offsim_homer_net *net, int32_t L, int64_t M);
+int offsim_homer_grad_pop(const offsim_homer_net *net, const offsim_homer_batch_pop *batch, int32_t L, double tau, int32_t hard,
+                          const uint8_t *active, float *grad, double *stats, double *work, void *stream);
+int offsim_homer_step_pop(const offsim_homer_net *net, const offsim_homer_batch_pop *batch, int32_t L, double tau,
+                          const offsim_homer_adam_pop *adam, const uint8_t *active, double *stats, double *work, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

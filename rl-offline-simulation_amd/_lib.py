@@ -175,6 +175,22 @@ class HomerAdam(C.Structure):
     _fields_ = [("m", _vp), ("v", _vp), ("t", _vp), ("lr", C.c_double), ("weight_decay", C.c_double)]
 
 
+def homer_work_doubles_nb(P, nb):
+    """include/offsim.h: OFFSIM_HOMER_WORK_DOUBLES_NB(P, NB)"""
+    return nb * 2 + 8 + (P + 255) // 256 + (P + 1) // 2 + nb * ((P + 1) // 2)
+
+
+class HomerBatchPop(C.Structure):
+    """struct offsim_homer_batch_pop"""
+    _fields_ = [("obs", _vp), ("next_obs", _vp), ("x_dtype", _i32), ("reserved", _i32), ("act", _vp), ("n_rows", _i64), ("idx_real", _vp),
+                ("idx_impo", _vp), ("noise", _vp), ("M", _i64), ("idx_stride", _i64)]
+
+
+class HomerAdamPop(C.Structure):
+    """struct offsim_homer_adam_pop"""
+    _fields_ = [("m", _vp), ("v", _vp), ("t", _vp), ("lr", _vp), ("weight_decay", _vp), ("max_grad_norm", _vp)]
+
+
 MAILBOX_MAX_ACTIONS = 24
 SERVER_CMD_STEP, SERVER_CMD_POP_ONE, SERVER_CMD_EXIT, SERVER_CMD_RESET = 1, 2, 3, 4
 SERVER_STARTING, SERVER_RUNNING, SERVER_EXITED = 1, 2, 3
@@ -258,6 +274,10 @@ SIGNATURES = {
     "offsim_homer_work_doubles": (_i64, [C.POINTER(HomerNet)]),
     "offsim_homer_grad": (C.c_int, [C.POINTER(HomerNet), C.POINTER(HomerBatch), C.c_double, _i32, _vp, _vp, _vp, _vp]),
     "offsim_homer_step": (C.c_int, [C.POINTER(HomerNet), C.POINTER(HomerBatch), C.c_double, C.c_double, C.POINTER(HomerAdam), _vp, _vp, _vp]),
+    "offsim_homer_work_doubles_pop": (_i64, [C.POINTER(HomerNet), _i32, _i64]),
+    "offsim_homer_grad_pop": (C.c_int, [C.POINTER(HomerNet), C.POINTER(HomerBatchPop), _i32, C.c_double, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "offsim_homer_step_pop": (C.c_int, [C.POINTER(HomerNet), C.POINTER(HomerBatchPop), _i32, C.c_double, C.POINTER(HomerAdamPop), _vp, _vp, _vp,
+                                        _vp]),
 }
 
 _lib = None

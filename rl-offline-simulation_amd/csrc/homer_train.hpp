@@ -21,6 +21,14 @@
 //   k_homer_adam           every block sums the blocks' squares in the same order -> total_norm, coef; then one thread per parameter:
 //                          clip, weight decay, Adam (k_ppo_adam's arithmetic), in place.
 // No float atomics, no cooperative launch, nothing waits on another workgroup.
+//
+// A population (offsim_homer_grad_pop, offsim_homer_step_pop; the POP instances of the same three kernels) puts L independent encoders
+// on gridDim.y.  Learner l = blockIdx.y has the stacked network l (pmlp_stage's lrn; k_homer_adam steps W + l * out * in, b + l * out),
+// its own records (idx_real / idx_impo at l * idx_stride + m, noise at (l * idx_stride + m) * 4 * nZ) over the shared obs / next_obs /
+// act, its own scratch block (ht_pop_stride: sized by the nb workgroups a learner really has), its own lr / weight_decay /
+// max_grad_norm (f64 device arrays) and its own rows of grad, m, v, t and stats.  Every launch of row l reads active[l] first and
+// returns when it is 0.  Per learner TM, the tiles of a workgroup, the partials, the reduction order, the norm tree and Adam are the
+// single call's on the same M, so learner l's results are the single call's bit for bit.  The POP = false instances carry none of this.
 #pragma once
 
 #define HT_THREADS 512
@@ -46,13 +54,26 @@ struct HomerBatchArgs {
     int64_t n_rows, M;
     int TM, hard;
     float tau;
+    int64_t idx_stride;     // POP: the learner stride of idx_real / idx_impo / noise, in records
+    const uint8_t *active;  // POP: [L] or NULL (all active)
 };
 
-// scratch (doubles): [MAX_BLOCKS][2] partial (n, sum -log p) | 8 spare | squares [ceil(P / 256)] | gradient f32 [P] | partials f32 [MAX_BLOCKS][P]
-#define HT_SQ (OFFSIM_HOMER_MAX_BLOCKS * 2 + 8)
+// scratch (doubles): [NB][2] partial (n, sum -log p) | 8 spare | squares [ceil(P / 256)] | gradient f32 [P] | partials f32 [NB][P], with
+// NB = OFFSIM_HOMER_MAX_BLOCKS for the single call; POP: one such block per learner, NB = the nb workgroups a learner really has
 __host__ __device__ __forceinline__ int ht_nred(int P) { return (P + HT_RED_BLOCK - 1) / HT_RED_BLOCK; }
-__host__ __device__ __forceinline__ size_t ht_gflat(int P) { return HT_SQ + ht_nred(P); }
-__host__ __device__ __forceinline__ size_t ht_gpart(int P) { return ht_gflat(P) + (P + 1) / 2; }
+__host__ __device__ __forceinline__ size_t ht_pop_stride(int nb, int P) { return OFFSIM_HOMER_WORK_DOUBLES_NB(P, nb); }
+template <bool POP>
+__host__ __device__ __forceinline__ size_t ht_sq(int nb) {
+    return (size_t)(POP ? nb : OFFSIM_HOMER_MAX_BLOCKS) * 2 + 8;
+}
+template <bool POP>
+__host__ __device__ __forceinline__ size_t ht_gflat(int nb, int P) {
+    return ht_sq<POP>(nb) + ht_nred(P);
+}
+template <bool POP>
+__host__ __device__ __forceinline__ size_t ht_gpart(int nb, int P) {
+    return ht_gflat<POP>(nb, P) + (P + 1) / 2;
+}
 
 // y[r][j] = act?(sum_k x[r][k] W^T[k][j] + b[j]) for R rows (a multiple of HT_RB): thread = (HT_RB rows, one unit), one fmaf chain per row
 __device__ __forceinline__ void ht_layer_fwd(const float *x, int ldx, float *y, int ldy, const float *wt, int ldw, const float *bias, int in, int out, int R,
@@ -101,9 +122,17 @@ __device__ __forceinline__ void ht_layer_bwd(const float *dn, int ldn, float *dp
     }
 }
 
-template <typename XT, bool BWD>
+template <typename XT, bool BWD, bool POP = false>
 __global__ void __launch_bounds__(HT_THREADS) k_homer_grad(HomerNet N, HomerBatchArgs B, double *__restrict__ work) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
+    const int lrn = POP ? (int)blockIdx.y : 0;
+    if constexpr (POP) {  // the learner's records and scratch; a quiet learner's workgroups leave before the first barrier
+        if (B.active && !B.active[lrn]) return;
+        work += (size_t)lrn * ht_pop_stride((int)gridDim.x, N.P);
+        B.idx_real += (int64_t)lrn * B.idx_stride;
+        B.idx_impo += (int64_t)lrn * B.idx_stride;
+        if (B.noise) B.noise += (int64_t)lrn * B.idx_stride * 4 * N.nZ;
+    }
     const int tid = threadIdx.x, TM = B.TM, dO = N.dO, nA = N.nA, nZ = N.nZ, H = N.H, K = N.K;
     const int lda_e = N.lda_e, ldd_e = N.ldd_e, lda_c = N.lda_c, ldd_c = N.ldd_c;
     float *w_lds = (float *)lds_raw;
@@ -114,7 +143,7 @@ __global__ void __launch_bounds__(HT_THREADS) k_homer_grad(HomerNet N, HomerBatc
     int *rec = (int *)(Dc + (size_t)2 * TM * ldd_c);  // [3][TM]: i, j, act (act < 0: the record is invalid)
     double *red = (double *)(rec + 4 * TM);            // [2 TM][2]  (all sizes above are multiples of 2 floats: ld* odd times TM even)
 
-    pmlp_stage(w_lds, N, N.ldw, tid, HT_THREADS);
+    pmlp_stage(w_lds, N, N.ldw, tid, HT_THREADS, lrn);
     for (int e = tid; e < 3 * TM * lda_e; e += HT_THREADS) Ae[e] = 0.0f;
     for (int e = tid; e < 3 * TM * ldd_e; e += HT_THREADS) De[e] = 0.0f;
     for (int e = tid; e < 2 * TM * lda_c; e += HT_THREADS) Ac[e] = 0.0f;
@@ -285,7 +314,7 @@ __global__ void __launch_bounds__(HT_THREADS) k_homer_grad(HomerNet N, HomerBatc
         }
     }
     if constexpr (BWD) {
-        float *gpart = (float *)(work + ht_gpart(N.P)) + (size_t)blockIdx.x * N.P;
+        float *gpart = (float *)(work + ht_gpart<POP>((int)gridDim.x, N.P)) + (size_t)blockIdx.x * N.P;
 #pragma unroll
         for (int i = 0; i < HT_OWN; i++) {
             const int p = tid + HT_THREADS * i;
@@ -311,6 +340,10 @@ struct HomerOptArgs {
     double *stats;
     float *grad_out;
     int nblocks, bwd;
+    // POP: [L] device arrays, the width of a stats row, and the active bytes ([L] or NULL)
+    const double *lr_p, *weight_decay_p, *max_norm_p;
+    const uint8_t *active;
+    int stats_ld;
 };
 
 // the batch's n and mean loss from the workgroups' partial sums, the same way in every block that asks
@@ -324,10 +357,18 @@ __device__ __forceinline__ void ht_sums(const double *work, int nblocks, double 
     loss = sn > 0.0 ? sl / (2.0 * sn) : 0.0;
 }
 
-template <bool STEP>
+template <bool STEP, bool POP = false>
 __global__ void __launch_bounds__(HT_RED_BLOCK) k_homer_reduce(HomerNet N, HomerOptArgs O, double *__restrict__ work) {
     __shared__ double sq[HT_RED_BLOCK];
     __shared__ double sh[2];
+    if constexpr (POP) {  // the learner's scratch and rows of the outputs and of the step count
+        const int lrn = (int)blockIdx.y;
+        if (O.active && !O.active[lrn]) return;
+        work += (size_t)lrn * ht_pop_stride(O.nblocks, N.P);
+        O.stats += (size_t)lrn * O.stats_ld;
+        if (STEP) O.t += lrn;
+        if (O.grad_out) O.grad_out += (size_t)lrn * N.P;
+    }
     if (threadIdx.x == 0) ht_sums(work, O.nblocks, sh[0], sh[1]);
     __syncthreads();
     const double n = sh[0];
@@ -340,11 +381,11 @@ __global__ void __launch_bounds__(HT_RED_BLOCK) k_homer_reduce(HomerNet N, Homer
     const int p = blockIdx.x * HT_RED_BLOCK + threadIdx.x;
     float gf = 0.0f;
     if (p < N.P) {
-        const float *gpart = (const float *)(work + ht_gpart(N.P));
+        const float *gpart = (const float *)(work + ht_gpart<POP>(O.nblocks, N.P));
         double gs = 0.0;
         for (int b = 0; b < O.nblocks; b++) gs += (double)gpart[(size_t)b * N.P + p];
         gf = (float)(n > 0.0 ? gs / (2.0 * n) : 0.0);
-        ((float *)(work + ht_gflat(N.P)))[p] = gf;
+        ((float *)(work + ht_gflat<POP>(O.nblocks, N.P)))[p] = gf;
         if (O.grad_out) O.grad_out[p] = gf;
     }
     sq[threadIdx.x] = (double)gf * (double)gf;
@@ -353,16 +394,29 @@ __global__ void __launch_bounds__(HT_RED_BLOCK) k_homer_reduce(HomerNet N, Homer
         if ((int)threadIdx.x < s) sq[threadIdx.x] += sq[threadIdx.x + s];
         __syncthreads();
     }
-    if (threadIdx.x == 0) work[HT_SQ + blockIdx.x] = sq[0];
+    if (threadIdx.x == 0) work[ht_sq<POP>(O.nblocks) + blockIdx.x] = sq[0];
 }
 
+template <bool POP = false>
 __global__ void __launch_bounds__(HT_RED_BLOCK) k_homer_adam(HomerNet N, HomerOptArgs O, double *__restrict__ work) {
     __shared__ double sh[2];
+    const int lrn = POP ? (int)blockIdx.y : 0;
+    if constexpr (POP) {  // the learner's scratch, hyperparameters and rows of the outputs and of the optimiser state
+        if (O.active && !O.active[lrn]) return;
+        work += (size_t)lrn * ht_pop_stride(O.nblocks, N.P);
+        O.stats += (size_t)lrn * O.stats_ld;
+        O.m += (size_t)lrn * N.P;
+        O.v += (size_t)lrn * N.P;
+        O.t += lrn;
+        O.lr = O.lr_p[lrn];
+        O.weight_decay = O.weight_decay_p[lrn];
+        O.max_norm = O.max_norm_p[lrn];
+    }
     if (threadIdx.x == 0) {
         double n, loss, s = 0.0;
         ht_sums(work, O.nblocks, n, loss);
         const int nr = ht_nred(N.P);
-        for (int b = 0; b < nr; b++) s += work[HT_SQ + b];
+        for (int b = 0; b < nr; b++) s += work[ht_sq<POP>(O.nblocks) + b];
         sh[0] = n;
         sh[1] = sqrt(s);
     }
@@ -378,11 +432,11 @@ __global__ void __launch_bounds__(HT_RED_BLOCK) k_homer_adam(HomerNet N, HomerOp
     int l = 0;
     while (l + 1 < 4 && p >= N.goff[l + 1]) l++;
     const int e = p - N.goff[l], nw = N.in[l] * N.out[l];
-    float *q = e < nw ? N.W[l] + e : N.b[l] + (e - nw);
+    float *q = e < nw ? N.W[l] + (size_t)lrn * nw + e : N.b[l] + (size_t)lrn * N.out[l] + (e - nw);
     // torch.optim.Adam with L2 weight decay: b1 = 0.9, b2 = 0.999, eps = 1e-8; f64 arithmetic on the f32 state (k_ppo_adam's)
     const double b1 = 0.9, b2 = 0.999, eps = 1e-8;
     const double t = (double)*O.t;
-    const double gd = (double)((const float *)(work + ht_gflat(N.P)))[p] * coef + O.weight_decay * (double)*q;
+    const double gd = (double)((const float *)(work + ht_gflat<POP>(O.nblocks, N.P)))[p] * coef + O.weight_decay * (double)*q;
     const float mf = (float)(b1 * (double)O.m[p] + (1.0 - b1) * gd);
     const float vf = (float)(b2 * (double)O.v[p] + (1.0 - b2) * gd * gd);
     const double step = O.lr / (1.0 - pow(b1, t));
@@ -480,12 +534,14 @@ static unsigned ht_blocks(const HomerBatchArgs &B) {
     return (unsigned)(nt < OFFSIM_HOMER_MAX_BLOCKS ? nt : OFFSIM_HOMER_MAX_BLOCKS);
 }
 
-static int ht_launch_grad(int32_t x_dtype, bool bwd, const HomerNet &N, const HomerBatchArgs &B, size_t lds, double *work, hipStream_t s) {
-    dim3 grid(ht_blocks(B)), block(HT_THREADS);
-#define LAUNCH_HT(XT, BWD)                                                                 \
-    do {                                                                                   \
-        if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_homer_grad<XT, BWD>), (int)lds));    \
-        hipLaunchKernelGGL((k_homer_grad<XT, BWD>), grid, block, lds, s, N, B, work);      \
+// POP: L learners on gridDim.y (B.M: one learner's records)
+template <bool POP = false>
+static int ht_launch_grad(int32_t x_dtype, bool bwd, const HomerNet &N, const HomerBatchArgs &B, size_t lds, double *work, hipStream_t s, int L = 1) {
+    dim3 grid(ht_blocks(B), (unsigned)L), block(HT_THREADS);
+#define LAUNCH_HT(XT, BWD)                                                                      \
+    do {                                                                                        \
+        if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_homer_grad<XT, BWD, POP>), (int)lds));    \
+        hipLaunchKernelGGL((k_homer_grad<XT, BWD, POP>), grid, block, lds, s, N, B, work);      \
     } while (0)
     if (x_dtype == OFFSIM_F32) {
         if (bwd) LAUNCH_HT(float, true);
@@ -560,7 +616,116 @@ extern "C" int offsim_homer_step(const offsim_homer_net *net, const offsim_homer
     const dim3 grid(ht_nred(N.P));
     hipLaunchKernelGGL((k_homer_reduce<true>), grid, dim3(HT_RED_BLOCK), 0, s, N, O, work);
     LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_homer_adam, grid, dim3(HT_RED_BLOCK), 0, s, N, O, work);
+    hipLaunchKernelGGL((k_homer_adam<false>), grid, dim3(HT_RED_BLOCK), 0, s, N, O, work);
+    LAUNCH_CHECK();
+    return OFFSIM_OK;
+}
+
+// ---- a population of L encoders (include/offsim.h: offsim_homer_grad_pop, offsim_homer_step_pop) ----
+
+// ht_prepare for a population: B describes ONE learner's M records, of the [L, idx_stride] arrays
+static int ht_prepare_pop(const char *who, const offsim_homer_net *net, const offsim_homer_batch_pop *bt, int32_t L, double tau, HomerNet &N,
+                          HomerBatchArgs &B, size_t &lds) {
+    if (L <= 0 || L > 65535) return fail(OFFSIM_EINVAL, "%s: L must be in 1..65535", who);
+    if (!bt) return fail(OFFSIM_EINVAL, "%s: batch is NULL", who);
+    if (bt->M >= 0 && bt->idx_stride < bt->M) return fail(OFFSIM_EINVAL, "%s: idx_stride must be >= M", who);
+    offsim_homer_batch one;
+    memset(&one, 0, sizeof(one));
+    one.obs = bt->obs;
+    one.next_obs = bt->next_obs;
+    one.x_dtype = bt->x_dtype;
+    one.act = bt->act;
+    one.n_rows = bt->n_rows;
+    one.idx_real = bt->idx_real;
+    one.idx_impo = bt->idx_impo;
+    one.noise = bt->noise;
+    one.M = bt->M;
+    int rc = ht_prepare(who, net, &one, tau, N, B, lds);
+    if (rc) return rc;
+    B.idx_stride = bt->idx_stride;
+    return OFFSIM_OK;
+}
+
+extern "C" int64_t offsim_homer_work_doubles_pop(const offsim_homer_net *net, int32_t L, int64_t M) {
+    if (L <= 0 || M < 0) return fail(OFFSIM_EINVAL, "homer_work_doubles_pop: L must be >= 1 and M >= 0%s");
+    // ht_prepare's TM for M records: every M from 32 * OFFSIM_HOMER_MAX_BLOCKS on has the same TM and OFFSIM_HOMER_MAX_BLOCKS workgroups
+    offsim_homer_batch bt;
+    memset(&bt, 0, sizeof(bt));
+    bt.x_dtype = OFFSIM_F32;
+    bt.M = M < (int64_t)32 * OFFSIM_HOMER_MAX_BLOCKS ? M : (int64_t)32 * OFFSIM_HOMER_MAX_BLOCKS;
+    bt.obs = bt.next_obs = &bt;  // (never read: ht_prepare only refuses NULL)
+    bt.act = bt.idx_real = bt.idx_impo = (const int32_t *)&bt;
+    HomerNet N;
+    HomerBatchArgs B;
+    size_t lds;
+    int rc = ht_prepare("homer_work_doubles_pop", net, &bt, 1.0, N, B, lds);
+    if (rc) return rc;
+    const unsigned nb = ht_blocks(B);
+    return (int64_t)L * (int64_t)ht_pop_stride(nb ? (int)nb : 1, N.P);
+}
+
+extern "C" int offsim_homer_grad_pop(const offsim_homer_net *net, const offsim_homer_batch_pop *batch, int32_t L, double tau, int32_t hard,
+                                     const uint8_t *active, float *grad, double *stats, double *work, void *stream) {
+    HomerNet N;
+    HomerBatchArgs B;
+    size_t lds;
+    int rc = ht_prepare_pop("homer_grad_pop", net, batch, L, tau, N, B, lds);
+    if (rc) return rc;
+    if (hard && grad) return fail(OFFSIM_EINVAL, "homer_grad_pop: hard is forward only: grad must be NULL%s");
+    if (B.M == 0) return OFFSIM_OK;
+    if (!stats || !work) return fail(OFFSIM_EINVAL, "homer_grad_pop: stats / work is NULL%s");
+    B.hard = hard ? 1 : 0;
+    B.active = active;
+    hipStream_t s = (hipStream_t)stream;
+    rc = ht_launch_grad<true>(batch->x_dtype, grad != nullptr, N, B, lds, work, s, L);
+    if (rc) return rc;
+    HomerOptArgs O;
+    memset(&O, 0, sizeof(O));
+    O.stats = stats;
+    O.stats_ld = 2;
+    O.grad_out = grad;
+    O.nblocks = (int)ht_blocks(B);
+    O.bwd = grad != nullptr;
+    O.active = active;
+    hipLaunchKernelGGL((k_homer_reduce<false, true>), dim3(O.bwd ? ht_nred(N.P) : 1, (unsigned)L), dim3(HT_RED_BLOCK), 0, s, N, O, work);
+    LAUNCH_CHECK();
+    return OFFSIM_OK;
+}
+
+extern "C" int offsim_homer_step_pop(const offsim_homer_net *net, const offsim_homer_batch_pop *batch, int32_t L, double tau,
+                                     const offsim_homer_adam_pop *adam, const uint8_t *active, double *stats, double *work, void *stream) {
+    HomerNet N;
+    HomerBatchArgs B;
+    size_t lds;
+    int rc = ht_prepare_pop("homer_step_pop", net, batch, L, tau, N, B, lds);
+    if (rc) return rc;
+    if (!adam) return fail(OFFSIM_EINVAL, "homer_step_pop: adam is NULL%s");
+    if (B.M == 0) return OFFSIM_OK;
+    if (!adam->m || !adam->v || !adam->t) return fail(OFFSIM_EINVAL, "homer_step_pop: adam->m / v / t is NULL%s");
+    if (!adam->lr || !adam->weight_decay || !adam->max_grad_norm)
+        return fail(OFFSIM_EINVAL, "homer_step_pop: adam->lr / weight_decay / max_grad_norm is NULL%s");
+    if (!stats || !work) return fail(OFFSIM_EINVAL, "homer_step_pop: stats / work is NULL%s");
+    B.active = active;
+    hipStream_t s = (hipStream_t)stream;
+    rc = ht_launch_grad<true>(batch->x_dtype, true, N, B, lds, work, s, L);
+    if (rc) return rc;
+    HomerOptArgs O;
+    memset(&O, 0, sizeof(O));
+    O.m = adam->m;
+    O.v = adam->v;
+    O.t = adam->t;
+    O.lr_p = adam->lr;
+    O.weight_decay_p = adam->weight_decay;
+    O.max_norm_p = adam->max_grad_norm;
+    O.stats = stats;
+    O.stats_ld = 3;
+    O.nblocks = (int)ht_blocks(B);
+    O.bwd = 1;
+    O.active = active;
+    const dim3 grid(ht_nred(N.P), (unsigned)L);
+    hipLaunchKernelGGL((k_homer_reduce<true, true>), grid, dim3(HT_RED_BLOCK), 0, s, N, O, work);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL((k_homer_adam<true>), grid, dim3(HT_RED_BLOCK), 0, s, N, O, work);
     LAUNCH_CHECK();
     return OFFSIM_OK;
 }
