@@ -44,8 +44,8 @@ def flat_dev(enc):
     return torch.cat([t.reshape(-1) for t in enc._params()]).cpu().numpy().astype(np.float64)
 
 
-def torch_ref(model, obs, act, nxt, i, j, noise, tau, hard=False, dtype=torch.float32):
-    """torch on the CPU in `dtype`: (loss, flat autograd gradient or None) over the valid records"""
+def torch_ref(model, obs, act, nxt, i, j, noise, tau, hard=False, dtype=torch.float32, slope=HH.SLOPE):
+    """torch on the CPU in `dtype`: (loss, flat autograd gradient or None) over the valid records; slope: leaky_relu's"""
     ps = [torch.tensor(np.asarray(t), dtype=dtype, requires_grad=not hard) for t in model]
     W1, b1, W2, b2, V1, c1, V2, c2 = ps
     nZ, nA = W2.shape[0], V1.shape[1] - 2 * W2.shape[0]
@@ -53,13 +53,13 @@ def torch_ref(model, obs, act, nxt, i, j, noise, tau, hard=False, dtype=torch.fl
     i, j = np.asarray(i)[ok].astype(np.int64), np.asarray(j)[ok].astype(np.int64)
     g = torch.zeros((len(i), 4, nZ), dtype=dtype) if noise is None else torch.tensor(np.asarray(noise)[ok], dtype=dtype)
     x, xn = torch.tensor(np.asarray(obs, np.float64), dtype=dtype), torch.tensor(np.asarray(nxt, np.float64), dtype=dtype)
-    enc = lambda v: F.linear(F.leaky_relu(F.linear(v, W1, b1)), W2, b2)  # noqa: E731
+    enc = lambda v: F.linear(F.leaky_relu(F.linear(v, W1, b1), slope), W2, b2)  # noqa: E731
     oh = F.one_hot(torch.tensor(np.asarray(act)[i].astype(np.int64)), nA).to(dtype)
     zs = []
     for q, e in enumerate((enc(x[i]), enc(xn[i]), enc(x[i]), enc(xn[j]))):
         y = F.softmax((e + g[:, q]) / tau, -1)
         zs.append((torch.zeros_like(y).scatter_(-1, y.max(-1, keepdim=True)[1], 1.0) - y) + y if hard else y)
-    cls = lambda a, b: F.log_softmax(F.linear(F.leaky_relu(F.linear(torch.cat([a, oh, b], 1), V1, c1)), V2, c2), 1)  # noqa: E731
+    cls = lambda a, b: F.log_softmax(F.linear(F.leaky_relu(F.linear(torch.cat([a, oh, b], 1), V1, c1), slope), V2, c2), 1)  # noqa: E731
     n = len(i)
     loss = (F.nll_loss(cls(zs[0], zs[1]), torch.ones(n, dtype=torch.long)) + F.nll_loss(cls(zs[2], zs[3]), torch.zeros(n, dtype=torch.long))) / 2
     if hard:
