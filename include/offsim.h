@@ -297,6 +297,21 @@ int offsim_eval_mc_rows_policy(const offsim_table *t, offsim_rollouts *ro, const
                                int32_t reject_mode, double gamma, const double *gamma_pow, int64_t n_gamma_pow, int64_t max_episodes,
                                const offsim_evalmc_out *out, int32_t *out_obs_row, void *stream);
 
+/* offsim_eval_mc_rows_policy_pop: offsim_eval_mc_rows_policy for a population of L policies on the same S seeds in ONE launch (ranking
+ * learners on a log: every policy sees the same queues and the same draws, so differences between policies are paired).
+ *   p_next [L,N,nA], p_init [L,N0,nA]   the per-row tables of offsim_eval_mc_rows_policy, stacked, contiguous.
+ *   ro->R = L * S, policy-major: rollout r evaluates policy r / S on seed index r % S.  ro->rng, cursor, init_cursor and cur_slot are
+ *   [R] rows as always (the caller's S rows replicated L times) and are advanced per rollout.
+ *   ro->perm / ro->init_perm hold S orders, not R: rollout r reads row r % S (perm_stride = 0: one shared order; NULL: table order, as
+ *   always).  The kernel only reads the orders, so all policies of a seed share one copy.
+ * Everything else -- both stream providers, the f64 and f32 modes, the reject modes, the outputs [R] with ep_* / trace_* and out_obs_row,
+ * the status codes -- is offsim_eval_mc_rows_policy's, and rollout l * S + j equals, in every output and in the state it leaves, that
+ * entry point run alone with policy l from seed j's state and order.  L in 1..65535, S >= 1, ro->R = L * S, tables not NULL where N > 0 /
+ * N0 > 0 (otherwise OFFSIM_EINVAL).  Argument validation happens before any HIP call; ro->R = 0 launches nothing. */
+int offsim_eval_mc_rows_policy_pop(const offsim_table *t, offsim_rollouts *ro, const void *p_next, const void *p_init, int32_t L, int32_t S,
+                                   int32_t prob_mode, int32_t reject_mode, double gamma, const double *gamma_pow, int64_t n_gamma_pow,
+                                   int64_t max_episodes, const offsim_evalmc_out *out, int32_t *out_obs_row, void *stream);
+
 /* PSRS_Exo.step (offsim4rl/evaluators/psrs.py:99-117): endogenous state s and exogenous state x have their own queue
  * families; every candidate pops the head of both, the accept/reject test reads the s-row, the accepted s-row gives
  * (r, s', done) and the accepted x-row gives x'.  ts / rs: table grouped by s and its rollout state (rng, cursors,
@@ -487,6 +502,16 @@ typedef struct offsim_mlp_layer {
 int offsim_policy_mlp(const void *x, int32_t x_dtype, int64_t n_x, int32_t dO, const int32_t *rows, int64_t M,
                       const offsim_mlp_layer *layers_host, int32_t n_layers, int32_t activation, float slope, float *out_probs,
                       void *stream);
+
+/* offsim_policy_mlp_pop: offsim_policy_mlp for L stacked networks of one architecture in ONE launch.  Stacking as
+ * offsim_vector_collect_ppo_pop's: every layer's W is [L, out, in] and b is [L, out] (or NULL), contiguous; layers_host describes learner
+ * 0, learner l's tensors are at W + l * out * in and b + l * out.  x, rows and M are shared by all learners; out_probs is [L, M, nA].
+ * The grid is (ceil(M / 32), L): a workgroup serves one learner, and learner l's [M, nA] equals offsim_policy_mlp with its tensors bit
+ * for bit (NaN rows included).  Limits as offsim_policy_mlp's; L in 1..65535 (otherwise OFFSIM_EINVAL).
+ * Argument validation happens before any HIP call; M = 0 launches nothing. */
+int offsim_policy_mlp_pop(const void *x, int32_t x_dtype, int64_t n_x, int32_t dO, const int32_t *rows, int64_t M,
+                          const offsim_mlp_layer *layers_host, int32_t n_layers, int32_t activation, float slope, int32_t L,
+                          float *out_probs, void *stream);
 
 /* ---- a learner's data collection (VectorPSRS.collect) ------------------------------------------------------------------------
  * The loop a neural learner runs against the log (examples/cartpole/psrs_from_expert_heuristic.py:59-80, with the network fixed for

@@ -253,7 +253,10 @@ SIGNATURES = {
     "offsim_encode_mlp": (C.c_int, [_vp, _i32, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
     "offsim_eval_mc_rows_policy": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), _vp, _vp, _i32, _i32, C.c_double, _vp, _i64, _i64,
                                              C.POINTER(EvalMCOut), _vp, _vp]),
+    "offsim_eval_mc_rows_policy_pop": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), _vp, _vp, _i32, _i32, _i32, _i32, C.c_double, _vp, _i64,
+                                                 _i64, C.POINTER(EvalMCOut), _vp, _vp]),
     "offsim_policy_mlp": (C.c_int, [_vp, _i32, _i64, _i32, _vp, _i64, C.POINTER(MLPLayer), _i32, _i32, C.c_float, _vp, _vp]),
+    "offsim_policy_mlp_pop": (C.c_int, [_vp, _i32, _i64, _i32, _vp, _i64, C.POINTER(MLPLayer), _i32, _i32, C.c_float, _i32, _vp, _vp]),
     "offsim_vector_collect": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), C.POINTER(CollectPolicy), _i32, _i32, _i64, _i32,
                                         C.POINTER(CollectState), C.POINTER(CollectOut), _vp]),
     "offsim_value_mlp": (C.c_int, [_vp, _i32, _i64, _i32, _vp, _i64, C.POINTER(MLPLayer), _i32, _i32, C.c_float, _vp, _vp]),

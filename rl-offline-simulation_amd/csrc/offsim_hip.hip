@@ -918,17 +918,29 @@ __device__ __forceinline__ uint32_t mt_bounded(volatile uint32_t *mt, uint32_t &
 // accepted grouped row g, rp.p_init[k] right after the reset that popped initial row k (a policy over observations asked at next_obs of
 // the accepted row, psrs.py:49-51, or at obs of the popped initial row, :32-37).  No pi block in LDS; rp.obs_row gets which row the
 // environment's observation comes from when the loop stops.
+//
+// POP = true (with ROWP): a population of L policies on the same S seeds (offsim_eval_mc_rows_policy_pop).  ro.R = L * S, policy-major:
+// rollout r = l * S + j walks queue order j (ro.perm / ro.init_perm hold S orders, only read) with tables rp.p_next + l * N * nA and
+// rp.p_init + l * N0 * nA; its stream, cursors, current state and outputs are row r's.  A workgroup holds consecutive r: seeds of one
+// policy (policies of one seed, which read the same order, measured no faster: DESIGN section 17).  The POP instances take their own
+// argument struct, so the kernel arguments of every other instance are what they were.
 struct RowPolicyArgs {
     const void *p_next, *p_init;
     int32_t *obs_row;
 };
+struct RowPolicyPopArgs : RowPolicyArgs {
+    int32_t S;
+};
+template <bool POP>
+using RowArgs = std::conditional_t<POP, RowPolicyPopArgs, RowPolicyArgs>;
 
-template <typename PL, typename PROB, bool TD, bool ROWP = false>
+template <typename PL, typename PROB, bool TD, bool ROWP = false, bool POP = false>
 __global__ void __launch_bounds__(256, 4) k_eval_mc(offsim_table t, offsim_rollouts ro, const PROB *__restrict__ pi,
                                                  int reject_mode, double gamma, const double *__restrict__ gamma_pow,
                                                  int64_t n_gamma_pow, int64_t max_episodes, offsim_evalmc_out out, offsim_td td,
-                                                 RowPolicyArgs rp) {
+                                                 RowArgs<POP> rp) {
     static_assert(!(TD && ROWP), "the learner drivers index their tables by state");
+    static_assert(!POP || ROWP, "a population is a population of row policies");
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const int waves = blockDim.x / WAVE;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE), lane = threadIdx.x & (WAVE - 1);  // uniform -> SGPR
@@ -949,6 +961,11 @@ __global__ void __launch_bounds__(256, 4) k_eval_mc(offsim_table t, offsim_rollo
     __syncthreads();
     const int r = blockIdx.x * waves + wave;
     if (r >= ro.R) return;
+    int pol = 0, ord = r;  // POP: the policy and the queue order of rollout r
+    if constexpr (POP) {
+        pol = r / rp.S;
+        ord = r - pol * rp.S;
+    }
     uint32_t *cur_glb = ro.cursor + (int64_t)r * n_slots;
     for (int s = lane; s < n_slots; s += WAVE) cur_lds[s] = cur_glb[s];
     uint32_t mt_pos = 624u;
@@ -966,8 +983,8 @@ __global__ void __launch_bounds__(256, 4) k_eval_mc(offsim_table t, offsim_rollo
     wave_rng_init(rng, tables + wave * (WAVE + 1), base, inc, ro.rng_kind);
     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): table and cursors visible to the whole wave
 
-    const uint32_t *perm_row = ro.perm ? ro.perm + (int64_t)r * ro.perm_stride : nullptr;
-    const uint32_t *init_row = ro.init_perm ? ro.init_perm + (int64_t)r * ro.init_stride : nullptr;
+    const uint32_t *perm_row = ro.perm ? ro.perm + (int64_t)(POP ? ord : r) * ro.perm_stride : nullptr;
+    const uint32_t *init_row = ro.init_perm ? ro.init_perm + (int64_t)(POP ? ord : r) * ro.init_stride : nullptr;
     uint32_t ic = ro.init_cursor[r];
     int slot = ro.cur_slot[r];
     int64_t ep = 0, n_len = 0, steps = 0, cand = 0;
@@ -976,8 +993,8 @@ __global__ void __launch_bounds__(256, 4) k_eval_mc(offsim_table t, offsim_rollo
     int status = OFFSIM_ST_OK;
     bool terminate = false;
     // ROWP: the row whose probabilities the next step uses (grouped row of the last accepted step, or -1: the initial row k_init)
-    const PROB *__restrict__ p_next = (const PROB *)rp.p_next;
-    const PROB *__restrict__ p_init = (const PROB *)rp.p_init;
+    const PROB *__restrict__ p_next = (const PROB *)rp.p_next + (POP ? (int64_t)pol * t.N * nA : 0);
+    const PROB *__restrict__ p_init = (const PROB *)rp.p_init + (POP ? (int64_t)pol * t.N0 * nA : 0);
     int32_t g_prev = -1;
     uint32_t k_init = 0;
     bool no_init = false;
@@ -1169,10 +1186,10 @@ static int check_evalmc_out(const char *who, const offsim_evalmc_out *out, const
     return OFFSIM_OK;
 }
 // ... and the launch: 4 rollouts per workgroup, halved until the LDS carve fits 64 KiB; up to 160 KiB with one rollout.
-template <typename PL, typename PROB, bool TD, bool ROWP>
+template <typename PL, typename PROB, bool TD, bool ROWP, bool POP = false>
 static int evalmc_launch(const char *who, const offsim_table *t, offsim_rollouts *ro, const void *pi, int32_t reject_mode, double gamma,
                          const double *gamma_pow, int64_t n_gamma_pow, int64_t max_episodes, const offsim_evalmc_out *out, const offsim_td &td,
-                         const RowPolicyArgs &rp, void *stream) {
+                         const RowArgs<POP> &rp, void *stream) {
     const size_t pb = ROWP ? 0 : sizeof(PROB);  // (ROWP: no pi block)
     int waves = 4;
     while (waves > 1 && evalmc_lds_bytes(waves, t->n_slots, t->nA, pb, TD) > 64 * 1024) waves >>= 1;
@@ -1180,8 +1197,8 @@ static int evalmc_launch(const char *who, const offsim_table *t, offsim_rollouts
     if (lds > 160 * 1024)
         return fail(OFFSIM_EUNSUPPORTED, TD ? "%s: Q table, cursors and policy exceed 160 KiB of LDS" : ROWP ? "%s: per-state cursors exceed 160 KiB of LDS"
                                                                                                               : "%s: per-state cursors and policy exceed 160 KiB of LDS", who);
-    if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_eval_mc<PL, PROB, TD, ROWP>), (int)lds));
-    hipLaunchKernelGGL((k_eval_mc<PL, PROB, TD, ROWP>), dim3((ro->R + waves - 1) / waves), dim3(waves * WAVE), lds, (hipStream_t)stream, *t, *ro,
+    if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_eval_mc<PL, PROB, TD, ROWP, POP>), (int)lds));
+    hipLaunchKernelGGL((k_eval_mc<PL, PROB, TD, ROWP, POP>), dim3((ro->R + waves - 1) / waves), dim3(waves * WAVE), lds, (hipStream_t)stream, *t, *ro,
                        (const PROB *)pi, reject_mode, gamma, gamma_pow, n_gamma_pow, max_episodes, *out, td, rp);
     LAUNCH_CHECK();
     return OFFSIM_OK;
@@ -1469,6 +1486,29 @@ extern "C" int offsim_eval_mc_rows_policy(const offsim_table *t, offsim_rollouts
     return with_plog_prob(t, prob_mode, [&](auto pl, auto prob) -> int {
         return evalmc_launch<decltype(pl), decltype(prob), false, true>("eval_mc_rows_policy", t, ro, nullptr, reject_mode, gamma, gamma_pow, n_gamma_pow,
                                                                         max_episodes, out, offsim_td{}, rp, stream);
+    });
+}
+
+// ---- offsim_eval_mc_rows_policy for L policies on the same S seeds in one launch (k_eval_mc<..., ROWP, POP>): the queue orders are the
+// seeds', shared by all policies and only read.
+extern "C" int offsim_eval_mc_rows_policy_pop(const offsim_table *t, offsim_rollouts *ro, const void *p_next, const void *p_init, int32_t L,
+                                              int32_t S, int32_t prob_mode, int32_t reject_mode, double gamma, const double *gamma_pow,
+                                              int64_t n_gamma_pow, int64_t max_episodes, const offsim_evalmc_out *out, int32_t *out_obs_row,
+                                              void *stream) {
+    static const char *who = "eval_mc_rows_policy_pop";
+    int rc = check_table(t);
+    if (rc) return rc;
+    if (!ro || ro->R < 0 || !out) return fail(OFFSIM_EINVAL, "%s: bad argument", who);
+    if (L < 1 || L > 65535 || S < 1) return fail(OFFSIM_EINVAL, "%s: L must be 1..65535 and S >= 1", who);
+    if (ro->R != 0 && (int64_t)ro->R != (int64_t)L * S) return fail(OFFSIM_EINVAL, "%s: ro->R must be L * S", who);
+    if ((t->N > 0 && !p_next) || (t->N0 > 0 && !p_init)) return fail(OFFSIM_EINVAL, "%s: p_next / p_init is NULL", who);
+    if (t->N0 > 0 && (!t->init_slot || !t->init_orig)) return fail(OFFSIM_EINVAL, "%s: table has no init rows", who);
+    if ((rc = check_evalmc_out(who, out, gamma_pow, n_gamma_pow)) || (rc = check_prob_mode(who, t, prob_mode))) return rc;
+    if (ro->R == 0) return OFFSIM_OK;
+    const RowPolicyPopArgs rp{{p_next, p_init, out_obs_row}, S};
+    return with_plog_prob(t, prob_mode, [&](auto pl, auto prob) -> int {
+        return evalmc_launch<decltype(pl), decltype(prob), false, true, true>(who, t, ro, nullptr, reject_mode, gamma, gamma_pow, n_gamma_pow, max_episodes,
+                                                                              out, offsim_td{}, rp, stream);
     });
 }
 
@@ -2233,7 +2273,8 @@ extern "C" int offsim_encode_mlp(const void *x, int32_t x_dtype, int64_t N, int3
 // the forward of offsim_policy_mlp (value false: softmax over the last layer's units) and offsim_value_mlp (value true: the last layer has
 // one unit, written as it is); `who` names the entry point in the error messages
 static int mlp_forward(const void *x, int32_t x_dtype, int64_t n_x, int32_t dO, const int32_t *rows, int64_t M, const offsim_mlp_layer *layers_host,
-                       int32_t n_layers, int32_t activation, float slope, float *out, void *stream, bool value, const char *who) {
+                       int32_t n_layers, int32_t activation, float slope, float *out, void *stream, bool value, const char *who, int32_t n_pop = 0) {
+    // n_pop: 0 = one network; L = a stacked population (offsim_policy_mlp_pop), the learner is the grid's y
     if (M < 0 || n_x < 0) return fail(OFFSIM_EINVAL, "%s: bad argument", who);
     PmlpNet N;
     int rc = pmlp_describe(who, layers_host, n_layers, dO, activation, slope, x_dtype, value ? 1 : PMLP_OUT_ACTIONS, N);
@@ -2257,15 +2298,17 @@ static int mlp_forward(const void *x, int32_t x_dtype, int64_t n_x, int32_t dO, 
     if (nb > 0x7fffffffull) return fail(OFFSIM_EINVAL, "%s: too many rows", who);
     hipStream_t st = (hipStream_t)stream;
     const float sl = slope;
-#define LAUNCH_PMLP(XT, V)                                                                                                              \
+#define LAUNCH_PMLP(XT, V, P)                                                                                                           \
     do {                                                                                                                                \
-        if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_policy_mlp<XT, V>), (int)lds));                                                  \
-        hipLaunchKernelGGL((k_policy_mlp<XT, V>), dim3((unsigned)nb), dim3(256), lds, st, (const XT *)x, n_x, dO, rows, M, L, activation, sl, out); \
+        if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_policy_mlp<XT, V, P>), (int)lds));                                               \
+        hipLaunchKernelGGL((k_policy_mlp<XT, V, P>), dim3((unsigned)nb, P ? n_pop : 1), dim3(256), lds, st, (const XT *)x, n_x, dO, rows, M, L, activation, sl, out); \
     } while (0)
-    if (x_dtype == OFFSIM_F32 && !value) LAUNCH_PMLP(float, false);
-    else if (!value) LAUNCH_PMLP(__half, false);
-    else if (x_dtype == OFFSIM_F32) LAUNCH_PMLP(float, true);
-    else LAUNCH_PMLP(__half, true);
+    if (n_pop && x_dtype == OFFSIM_F32) LAUNCH_PMLP(float, false, true);
+    else if (n_pop) LAUNCH_PMLP(__half, false, true);
+    else if (x_dtype == OFFSIM_F32 && !value) LAUNCH_PMLP(float, false, false);
+    else if (!value) LAUNCH_PMLP(__half, false, false);
+    else if (x_dtype == OFFSIM_F32) LAUNCH_PMLP(float, true, false);
+    else LAUNCH_PMLP(__half, true, false);
 #undef LAUNCH_PMLP
     LAUNCH_CHECK();
     return OFFSIM_OK;
@@ -2275,6 +2318,13 @@ extern "C" int offsim_policy_mlp(const void *x, int32_t x_dtype, int64_t n_x, in
                                  const offsim_mlp_layer *layers_host, int32_t n_layers, int32_t activation, float slope, float *out_probs,
                                  void *stream) {
     return mlp_forward(x, x_dtype, n_x, dO, rows, M, layers_host, n_layers, activation, slope, out_probs, stream, false, "policy_mlp");
+}
+
+extern "C" int offsim_policy_mlp_pop(const void *x, int32_t x_dtype, int64_t n_x, int32_t dO, const int32_t *rows, int64_t M,
+                                     const offsim_mlp_layer *layers_host, int32_t n_layers, int32_t activation, float slope, int32_t L,
+                                     float *out_probs, void *stream) {
+    if (L < 1 || L > 65535) return fail(OFFSIM_EINVAL, "%s: L must be 1..65535", "policy_mlp_pop");
+    return mlp_forward(x, x_dtype, n_x, dO, rows, M, layers_host, n_layers, activation, slope, out_probs, stream, false, "policy_mlp_pop", L);
 }
 
 extern "C" int offsim_value_mlp(const void *x, int32_t x_dtype, int64_t n_x, int32_t dO, const int32_t *rows, int64_t M,

@@ -146,7 +146,9 @@ __device__ __forceinline__ void pmlp_stage(float *dst, const NET &N, const int *
 
 // VALUE: the critic of the same shape (offsim_value_mlp, spinup's MLPCritic: v = squeeze(v_net(obs), -1)): the last layer has one unit and
 // no softmax follows, probs is then out[M].
-template <typename XT, bool VALUE>
+// POP: a stacked population (offsim_policy_mlp_pop: W [L][out][in], b [L][out], L's descriptor is learner 0's), the learner is blockIdx.y:
+// the same tile loop on that learner's tensors, written to probs [L][M][nA].
+template <typename XT, bool VALUE, bool POP = false>
 __global__ void __launch_bounds__(256) k_policy_mlp(const XT *__restrict__ x, int64_t n_x, int dO, const int32_t *__restrict__ rows, int64_t M,
                                                     PmlpLayers L, int act, float slope, float *__restrict__ probs) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -164,8 +166,8 @@ __global__ void __launch_bounds__(256) k_policy_mlp(const XT *__restrict__ x, in
     for (int l = 0; l < L.n; l++) {
         const int in = L.in[l], out = L.out[l], ldw = in + 1;
         const int jc_max = L.w_floats / ldw;
-        const float *__restrict__ W = L.W[l];
-        const float *__restrict__ b = L.b[l];
+        const float *__restrict__ W = L.W[l] + (POP ? (size_t)blockIdx.y * in * out : 0);
+        const float *__restrict__ b = POP && L.b[l] ? L.b[l] + (size_t)blockIdx.y * out : L.b[l];
         const bool last = l == L.n - 1;
         for (int j0 = 0; j0 < out; j0 += jc_max) {
             const int jc = out - j0 < jc_max ? out - j0 : jc_max;
@@ -191,6 +193,7 @@ __global__ void __launch_bounds__(256) k_policy_mlp(const XT *__restrict__ x, in
     }
     // softmax of the logits (torch.distributions.Categorical(logits=...).probs)
     const int nA = L.out[L.n - 1];
+    if (POP) probs += (int64_t)blockIdx.y * M * nA;
     for (int m = threadIdx.x; m < tm; m += blockDim.x) pmlp_softmax(cur + m * ld, nA, probs + (m0 + m) * nA);
 }
 

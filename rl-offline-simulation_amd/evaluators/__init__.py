@@ -4,7 +4,8 @@ from .trivial_baselines import FollowObservationOnly, FollowActionOnly, ServeRan
 from .queue_evaluator import QueueEvaluator, BatchedQueueEvaluator  # noqa: F401
 from .psrs_exo import PSRS_Exo  # noqa: F401
 from .vector_env import VectorPSRS  # noqa: F401
-from .obs_policy import MLPPolicy, RowPolicy, CallablePolicy, MLPValue, RowValue  # noqa: F401
+from .obs_policy import MLPPolicy, RowPolicy, CallablePolicy, MLPValue, RowValue, PolicyPopulation  # noqa: F401
+from .batched import evalmc_rollouts_population  # noqa: F401
 from .ppo_buffer import PPOBatch, ppo_advantages  # noqa: F401
 from .ppo_learner import PPOLearner, PPOUpdateInfo, ppo_grad  # noqa: F401
 from .ppo_population import PPOPopulation, ppo_grad_population  # noqa: F401

@@ -12,6 +12,7 @@ drivers (PSRS, evalMC_psrs, qlearn_psrs, expSARSA_psrs) are in psrs.py, on top o
 import ctypes as C
 import os
 import time
+import warnings
 
 import numpy as np
 import torch
@@ -666,6 +667,53 @@ class BatchedPSRS:
         o["_kernel"] = "k_eval_mc_rows_policy"
         return o
 
+    # -- the same for L policies on this environment's R seeds, in one launch --
+    def eval_mc_rows_policy_population(self, p_next, p_init, gamma, n_episodes=None, ep_cap=0, trace_cap=0, n_gamma_pow=4096):
+        """p_next [L,N,nA], p_init [L,N0,nA]: the tables of eval_mc_rows_policy for L policies, stacked (PolicyPopulation.row_tables).
+        Every policy is evaluated on every one of this environment's R rollouts (its seeds): L * R rollouts in one launch that share
+        the R queue orders (include/offsim.h, offsim_eval_mc_rows_policy_pop).  Returns the dict of eval_mc_rows_policy with [L, R]
+        leading dimensions; entry [l, j] is what eval_mc_rows_policy gives rollout j with policy l.
+        An evaluation is a query: it runs on copies of the sampler state, so this environment's own cursors, rejection streams and
+        current slots are left as they were, and a following call (of this or any other method) starts from the same state."""
+        self._quiesce()
+        self._orders_for_generic()
+        t, dev, S = self.table, self.table.device, self.R
+        if p_next.dim() != 3 or p_init.dim() != 3 or p_next.shape[0] != p_init.shape[0] or p_next.shape[0] < 1:
+            raise ValueError(f"eval_mc_rows_policy_population: p_next [L,N,nA] and p_init [L,N0,nA] expected, got {tuple(p_next.shape)} and {tuple(p_init.shape)}")
+        n_pol = int(p_next.shape[0])
+        R = n_pol * S
+        mode = _prob_mode(t, p_next.dtype if p_next.dtype == p_init.dtype else torch.float64)
+        dt = torch.float32 if mode == L.PROB_F32 else torch.float64
+        pn = p_next.to(device=dev, dtype=dt).reshape(n_pol, t.N, t.nA).contiguous()
+        p0 = p_init.to(device=dev, dtype=dt).reshape(n_pol, t.N0, t.nA).contiguous()
+        if n_episodes is None:
+            n_episodes = 1 << 62
+        st = self.state
+        rng, cursor = st.rng.repeat(n_pol, 1), st.cursor.repeat(n_pol, 1)
+        init_cursor, cur_slot = st.init_cursor.repeat(n_pol), st.cur_slot.repeat(n_pol)
+        ro = L.Rollouts(R=R, rng=L.ptr(rng), cursor=L.ptr(cursor), init_cursor=L.ptr(init_cursor), cur_slot=L.ptr(cur_slot), perm=L.ptr(st.perm),
+                        perm_stride=st.perm_stride, init_perm=L.ptr(st.init_perm), init_stride=st.init_stride, rng_kind=st.rng_kind)
+        o = {k: torch.empty(R, dtype=dt_, device=dev) for k, dt_ in (("sum_g", torch.float64), ("n_ep", torch.int64), ("steps", torch.int64),
+                                                                    ("cand", torch.int64), ("n_len", torch.int64), ("status", torch.int32))}
+        o["obs_row"] = torch.full((R,), -(1 << 31), dtype=torch.int32, device=dev)
+        if ep_cap:
+            o["ep_g"] = torch.zeros((R, ep_cap), dtype=torch.float64, device=dev)
+            o["ep_len"] = torch.zeros((R, ep_cap + 1), dtype=torch.int32, device=dev)
+        if trace_cap:
+            o["trace_row"] = torch.full((R, trace_cap), -1, dtype=torch.int32, device=dev)
+            o["trace_pop"] = torch.zeros((R, trace_cap), dtype=torch.int32, device=dev)
+        gp = _gamma_pow(gamma, n_gamma_pow, dev, cap=t.N + 2)
+        oc = L.EvalMCOut(sum_g=L.ptr(o["sum_g"]), n_ep=L.ptr(o["n_ep"]), steps=L.ptr(o["steps"]), cand=L.ptr(o["cand"]),
+                         n_len=L.ptr(o["n_len"]), status=L.ptr(o["status"]), ep_g=L.ptr(o.get("ep_g")), ep_len=L.ptr(o.get("ep_len")),
+                         ep_cap=ep_cap, trace_row=L.ptr(o.get("trace_row")), trace_pop=L.ptr(o.get("trace_pop")), trace_cap=trace_cap)
+        L.check(L.load().offsim_eval_mc_rows_policy_pop(C.byref(t.c), C.byref(ro), L.ptr(pn) if t.N else None, L.ptr(p0) if t.N0 else None, n_pol, S,
+                                                        mode, self.reject_mode, float(gamma), L.ptr(gp), gp.numel(), int(n_episodes), C.byref(oc),
+                                                        L.ptr(o["obs_row"]), L.stream_ptr()))
+        o = {k: v.reshape(n_pol, S, *v.shape[1:]) for k, v in o.items()}
+        o["_keepalive"] = (pn, p0, gp, rng, cursor, init_cursor, cur_slot)
+        o["_kernel"] = "k_eval_mc_rows_policy_pop"
+        return o
+
     # -- qlearn_psrs / expSARSA_psrs (psrs.py:119-239) with a Q-independent behaviour policy, all rollouts in one launch --
     def eval_td(self, pi_slots, gamma, mode, alpha, q_slots=None, n_episodes=None, ep_cap=0, trace_cap=0, n_gamma_pow=4096,
                 behaviour=L.BEHAVIOUR_FIXED, epsilon=0.0, alpha_ep=None, epsilon_ep=None, snap_cap=0, snap_stride=1, tie_mt=None):
@@ -837,4 +885,61 @@ def _evalmc_rollouts_rows_policy(table, seeds, pi, gamma, shuffle, shuffle_seed,
     res = {k: np.concatenate(v) for k, v in outs.items()}
     with np.errstate(invalid="ignore", divide="ignore"):
         res["value"] = res["sum_g"] / res["n_ep"]
+    return res
+
+
+def evalmc_rollouts_population(table, seeds, policies, gamma, shuffle=SHUFFLE_PER_ROLLOUT, shuffle_seed=None, tile=None, policy_tile=None,
+                               reject_mode=L.REJECT_DEFAULT, n_episodes=None, obs=None, next_obs=None):
+    """evalMC_psrs of L policies over observations on the same S sampler seeds (ranking learners on a log): every policy sees the same
+    queue orders and the same rejection draws, so the differences between policies are paired.  `policies`: a PolicyPopulation
+    (evaluators/obs_policy.py), or a list of policies over observations (MLPPolicy's of one architecture are stacked, anything else goes
+    through its own row tables); obs / next_obs [N, dO]: the log's observations in caller order.
+    One reset_sampler per tile of `tile` seeds (default: resident_rollouts(keyed=False) -- the queue orders are the seeds', shared by all
+    policies, so the tile does not shrink with L), and per seed tile one forward launch and one scan launch per tile of `policy_tile`
+    policies (default: as many as keep the [L, N + N0, nA] tables within a quarter of the free memory; with more than one policy tile the
+    tables are recomputed per seed tile).
+    Returns host arrays [L, S]: sum_g, n_ep, steps, cand, status and value = sum_g / n_ep (NaN where a seed completed no episode);
+    mean_value [L], the mean of value over the seeds that have one (NaN where none has); best, the arg-max of mean_value (-1 when every
+    mean is NaN)."""
+    from .obs_policy import MLPPolicy, PolicyPopulation
+    seeds = np.asarray(seeds, dtype=np.uint64)
+    S = len(seeds)
+    if not isinstance(policies, PolicyPopulation):
+        policies = list(policies)
+        policies = PolicyPopulation.from_policies(policies) if policies and all(isinstance(p, MLPPolicy) for p in policies) else PolicyPopulation.from_rows(policies)
+    n_pol = len(policies)
+    if (obs is None or next_obs is None) and policies.needs_obs():
+        raise ValueError("evalmc_rollouts_population: policies over observations need the log's obs= and next_obs=")
+    if policy_tile is None:
+        per_policy = max(1, (int(table.N) + int(table.N0)) * int(table.nA) * 8)
+        policy_tile = (torch.cuda.mem_get_info(table.device)[0] // 4) // per_policy
+    policy_tile = int(max(1, min(n_pol, policy_tile)))
+    tables = policies.row_tables(table, obs, next_obs) if policy_tile >= n_pol else None  # (one policy tile: computed once)
+    if tile is None:
+        tile = S if shuffle != SHUFFLE_PER_ROLLOUT else int(max(1, min(S, resident_rollouts(table, keyed=False)[0])))
+    keys = ("sum_g", "n_ep", "steps", "cand", "status")
+    outs = {k: [] for k in keys}
+    env = None
+    for b in range(0, S, tile):
+        sd = seeds[b:b + tile]
+        if env is None or env.R != len(sd):
+            env = BatchedPSRS(table, len(sd), reject_mode)
+        env.reset_sampler(sd, shuffle, shuffle_seed)
+        env._orders_for_generic()
+        cols = {k: [] for k in keys}
+        for lo in range(0, n_pol, policy_tile):
+            p_next, p_init = tables if tables is not None else policies.row_tables(table, obs, next_obs, lo, min(n_pol, lo + policy_tile))
+            o = env.eval_mc_rows_policy_population(p_next, p_init, gamma, n_episodes)
+            for k in keys:
+                cols[k].append(o[k].cpu().numpy())
+            L.check_async_faults()  # (the copies above synchronised the stream)
+        for k in keys:
+            outs[k].append(np.concatenate(cols[k], axis=0))
+    res = {k: np.concatenate(v, axis=1) if v else np.zeros((n_pol, 0)) for k, v in outs.items()}
+    with np.errstate(invalid="ignore", divide="ignore"):
+        res["value"] = res["sum_g"] / res["n_ep"]
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)  # (a policy without one completed episode: its mean is NaN, as its values are)
+        res["mean_value"] = np.nanmean(res["value"], axis=1)
+    res["best"] = -1 if np.isnan(res["mean_value"]).all() else int(np.nanargmax(res["mean_value"]))
     return res

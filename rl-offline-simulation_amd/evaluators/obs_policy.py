@@ -15,6 +15,9 @@ device (`row_tables`):
                    (its `rows` gather index is table.order for P_next and table.init_orig for P_init: no second gather pass)
   RowPolicy        per-row probabilities the caller already has, in caller order (gathered into the two tables on the device)
   CallablePolicy   any fn(obs_tensor) -> probs, run by torch on the device in chunks (plumbing: the scan is still the HIP kernel)
+
+PolicyPopulation is L such policies evaluated together on the same seeds: the pair stacked, [L, N, nA] and [L, N0, nA], for stacked MLPs
+by one launch of offsim_policy_mlp_pop, read by the population form of the scan (offsim_eval_mc_rows_policy_pop).
 """
 import ctypes as C
 
@@ -220,6 +223,138 @@ class RowPolicy(ObsPolicy):
     def row_tables(self, table, obs=None, next_obs=None):
         pn, p0 = self.caller_tables(table)
         return gather_rows(pn, table.order), gather_rows(p0, table.init_orig)
+
+
+class _StackedMLP:
+    """L MLPPolicy's of one architecture, stacked per layer (W [L, out, in], b [L, out]): the host copies, and per device the stacked
+    tensors with the offsim_mlp_layer array that describes learner 0 -- what PPOPopulation's own stack offers, for policies that come
+    from anywhere else."""
+
+    def __init__(self, policies):
+        for p in policies:
+            if not isinstance(p, MLPPolicy):
+                raise ValueError(f"PolicyPopulation.from_policies: every policy must be an MLPPolicy, got {type(p).__name__}")
+        first = policies[0]
+        self.n, self.policies = len(policies), list(policies)
+        self.activation, self.slope, self.dO, self.nA = first.activation, first.slope, first.dO, first.nA
+        shape = [(tuple(W.shape), b is not None) for W, b in first.weights]
+        for p in policies:
+            if[(tuple(W.shape), b is not None) for W, b in p.weights] != shape or (p.activation, p.slope) != (self.activation, self.slope):
+                raise ValueError("PolicyPopulation.from_policies: all policies share one architecture (layer shapes, biases, activation, slope)")
+        self.host = [(torch.stack([p.weights[i][0] for p in policies]), torch.stack([p.weights[i][1] for p in policies]) if has_b else None)
+                     for i, (_, has_b) in enumerate(shape)]
+        self._dev = {}
+
+    def _device_weights(self, device):
+        key = str(device)
+        if key not in self._dev:
+            ws = [(W.to(device).contiguous(), None if b is None else b.to(device).contiguous()) for W, b in self.host]
+            self._dev[key] = (ws, _stacked_layers(ws, 0))
+        return self._dev[key]
+
+    def export(self, l):
+        return self.policies[l]
+
+
+def _stacked_layers(ws, lo):
+    """the offsim_mlp_layer array of learner `lo` of stacked tensors [(W [L, out, in], b [L, out] or None)]"""
+    arr = (L.MLPLayer * len(ws))()
+    for i, (W, b) in enumerate(ws):
+        arr[i].W, arr[i].b = L.ptr(W[lo:]), None if b is None else L.ptr(b[lo:])
+        setattr(arr[i], "in", int(W.shape[2]))
+        arr[i].out = int(W.shape[1])
+    return arr
+
+
+class PolicyPopulation:
+    """L policies over observations, evaluated together on the same seeds (BatchedPSRS.eval_mc_rows_policy_population,
+    evalmc_rollouts_population): `row_tables` gives their per-row tables stacked, P_next [L, N, nA] and P_init [L, N0, nA].
+
+      from_policies([MLPPolicy, ...])   policies of one architecture; their weights are stacked once per device and every forward is ONE
+                                        launch for all of them (offsim_policy_mlp_pop)
+      from_ppo(PPOPopulation)           the population's own stacked actor weights, as they are: no copy, so an evaluation after
+                                        PPOPopulation.update sees the new weights
+      from_rows([RowPolicy | CallablePolicy | any ObsPolicy, ...])   each policy's own row_tables, stacked
+    """
+
+    def __init__(self, stack=None, rows=None):
+        if (stack is None) == (rows is None):
+            raise ValueError("PolicyPopulation: use from_policies, from_ppo or from_rows")
+        self._stack, self._rows = stack, rows
+
+    @classmethod
+    def from_policies(cls, policies):
+        policies = list(policies)
+        if not policies:
+            raise ValueError("PolicyPopulation.from_policies: no policies")
+        return cls(stack=_StackedMLP(policies))
+
+    @classmethod
+    def from_ppo(cls, population):
+        if not hasattr(population, "_pi") or not hasattr(population._pi, "_device_weights"):
+            raise TypeError(f"PolicyPopulation.from_ppo: needs a PPOPopulation, got {type(population).__name__}")
+        return cls(stack=population._pi)
+
+    @classmethod
+    def from_rows(cls, policies):
+        policies = list(policies)
+        if not policies:
+            raise ValueError("PolicyPopulation.from_rows: no policies")
+        for p in policies:
+            if not isinstance(p, ObsPolicy):
+                raise ValueError(f"PolicyPopulation.from_rows: every policy must be a policy over observations, got {type(p).__name__}")
+        return cls(rows=policies)
+
+    def __len__(self):
+        return self._stack.n if self._stack is not None else len(self._rows)
+
+    def policy(self, l):
+        """policy l on its own (from_ppo: a copy of learner l's actor with its current weights)"""
+        if not 0 <= l < len(self):
+            raise IndexError(f"PolicyPopulation: policy {l} of {len(self)}")
+        return self._stack.export(l) if self._stack is not None else self._rows[l]
+
+    def needs_obs(self):
+        """whether row_tables reads the log's observations (everything but a population of RowPolicy's)"""
+        return self._stack is not None or not all(hasattr(p, "p_next") for p in self._rows)
+
+    def forward(self, x, rows=None, lo=0, hi=None):
+        """probs [hi - lo, M, nA] of the stacked networks lo .. hi - 1 (default: all) in one launch: x [n, dO] f32 / f16 device tensor,
+        rows (optional) [M] int32 gather index into x.  Every [M, nA] equals that policy's MLPPolicy.forward bit for bit."""
+        st = self._stack
+        if st is None:
+            raise TypeError("PolicyPopulation.forward: a population of row tables has no network")
+        hi = st.n if hi is None else hi
+        if not 0 <= lo < hi <= st.n:
+            raise IndexError(f"PolicyPopulation.forward: policies {lo}..{hi} of {st.n}")
+        if x.dim() != 2 or x.shape[1] != st.dO:
+            raise ValueError(f"PolicyPopulation: observations of width {st.dO} expected, got shape {tuple(x.shape)}")
+        if x.dtype not in (torch.float32, torch.float16):
+            x = x.to(torch.float32)
+        x = x.contiguous()
+        if rows is not None:
+            rows = rows.to(device=x.device, dtype=torch.int32).contiguous()
+        M = int(x.shape[0]) if rows is None else int(rows.numel())
+        out = torch.empty((hi - lo, M, st.nA), dtype=torch.float32, device=x.device)
+        ws, arr = st._device_weights(x.device)
+        if lo:
+            arr = _stacked_layers(ws, lo)
+        L.check(L.load().offsim_policy_mlp_pop(L.ptr(x) if x.numel() else None, L.F32 if x.dtype == torch.float32 else L.F16, int(x.shape[0]), st.dO,
+                                               L.ptr(rows) if rows is not None and M else None, M, arr, len(ws), _ACT[st.activation], st.slope,
+                                               hi - lo, L.ptr(out) if M else None, L.stream_ptr()))
+        return out
+
+    def row_tables(self, table, obs=None, next_obs=None, lo=0, hi=None):
+        """(P_next [hi - lo, N, nA] in grouped order, P_init [hi - lo, N0, nA] in init_orig order) of policies lo .. hi - 1 (default: all)
+        on the table's device."""
+        hi = len(self) if hi is None else hi
+        if self._stack is not None:
+            xn, x0 = obs_tensor(next_obs, table.device), obs_tensor(obs, table.device)
+            return self.forward(xn, table.order, lo, hi), self.forward(x0, table.init_orig, lo, hi)
+        pairs = [p.row_tables(table, obs, next_obs) for p in self._rows[lo:hi]]
+        dt = torch.float32 if all(p.dtype == torch.float32 for pr in pairs for p in pr) else torch.float64
+        return (torch.stack([pn.to(dt).reshape(table.N, table.nA) for pn, _ in pairs]),
+                torch.stack([p0.to(dt).reshape(table.N0, table.nA) for _, p0 in pairs]))
 
 
 class MLPValue(_MLPNet):

@@ -160,6 +160,15 @@ class PPOPopulation:
             raise ValueError("PPOPopulation.adam_state: the population has not been on a device yet")
         return (self._pi.m, self._pi.v, self._pi.t), (self._v.m, self._v.v, self._v.t)
 
+    # ---- ranking the learners on a log ----
+    def evaluate(self, table, seeds, gamma, obs, next_obs, **kw):
+        """evalMC_psrs of every learner's actor, with its current weights, on the same sampler seeds: evalmc_rollouts_population (batched.py)
+        over PolicyPopulation.from_ppo(self) -- the stacked device weights as they are, no copy.  Returns its dict: [L, S] host arrays,
+        mean_value [L] and best."""
+        from .batched import evalmc_rollouts_population
+        from .obs_policy import PolicyPopulation
+        return evalmc_rollouts_population(table, seeds, PolicyPopulation.from_ppo(self), gamma, obs=obs, next_obs=next_obs, **kw)
+
     # ---- one learner, exported ----
     def actor(self, l):
         """learner l's actor as an MLPPolicy of its current weights (a copy)"""
