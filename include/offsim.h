@@ -695,6 +695,42 @@ int offsim_ppo_advantages_pop(const float *rew, const float *value, const uint8_
                               int64_t T, int32_t L, int64_t E, double gamma, double lam, int32_t bootstrap, float *adv, float *ret,
                               float *adv_norm, double *stats, double *work, void *stream);
 
+/* offsim_ppo_epoch_log: what the reference's agent hands to its EpochLogger during one epoch, and spinup's statistics of it, over the
+ * step-major [T, E] records of that epoch as offsim_vector_collect_ppo leaves them (offsim4rl/agents/ppo.py:103-160, :225-235; E
+ * environments = E MPI processes).  valid / terminated / truncated: [T, E] bytes, non-zero = set.  open_ret [E] f64 and open_len [E] i32
+ * are the caller's carried state -- self.ep_ret / self.ep_len of every environment -- read and updated in place, so an episode that an
+ * epoch cuts goes on in the next call (zero them to begin).  Per environment, over its valid steps in order:
+ *   open_ret += (double)rew, open_len += 1;
+ *   at a step with terminated or truncated an episode ends: its return is open_ret, its length open_len - 1 under
+ *     OFFSIM_EPLEN_REFERENCE (end_episode does not count its own transition, ppo.py:116-133; step does, :138-140) or open_len under
+ *     OFFSIM_EPLEN_STEPS (the number of its transitions); both counters go back to zero;
+ *   an environment with a valid step and no ended episode contributes the one entry (open_ret, open_len) -- _log_epoch_metrics' store
+ *     when EpRet is empty (ppo.py:226-227); open_len is here the transition count so far under either mode, and the counters go on;
+ *   an environment without a valid step contributes nothing;
+ *   VVals are value[t] of every valid step.
+ * stats [OFFSIM_PPO_LOG_STATS] f64: EpRet mean, std, min, max | EpLen mean | VVals mean, std, min, max | the number of entries, with
+ * mean = sum / n and std = sqrt(sum((x - mean)^2) / n) (mpi_statistics_scalar; two passes, f64); n = 0 gives NaN.  counts [2] i64:
+ * EpisodesInEpoch (ended episodes only) and the valid steps.  Optional (NULL to skip), the ENDED episodes of every environment in order:
+ * ep_ret [E, ep_cap] f64, ep_len [E, ep_cap] i32 (the first ep_cap of them), n_ep [E] i32 (their number, which may pass ep_cap); the
+ * open entry of an environment with n_ep = 0 and a valid step is its open_ret / open_len after the call.
+ * One launch; no atomics, every sum in a fixed order (a lane's environments in order, each in step order, then an LDS tree): the same
+ * bits every run.  T >= 1, E >= 1, ep_cap >= 0, a known mode, non-NULL records, state, stats and counts (otherwise OFFSIM_EINVAL);
+ * argument validation happens before any HIP call.  Asynchronous on `stream`, capturable. */
+#define OFFSIM_EPLEN_REFERENCE 0
+#define OFFSIM_EPLEN_STEPS 1
+#define OFFSIM_PPO_LOG_STATS 10
+int offsim_ppo_epoch_log(const float *rew, const float *value, const uint8_t *valid, const uint8_t *terminated, const uint8_t *truncated,
+                         int64_t T, int64_t E, int32_t eplen_mode, double *open_ret, int32_t *open_len, double *stats, int64_t *counts,
+                         double *ep_ret, int32_t *ep_len, int32_t *n_ep, int64_t ep_cap, void *stream);
+
+/* offsim_ppo_epoch_log_pop: offsim_ppo_epoch_log over the [T, L * E] records of a population (learner-major columns: environment r belongs
+ * to learner r / E), one workgroup per learner in the same single launch.  open_ret / open_len / n_ep [L * E], ep_ret / ep_len
+ * [L * E, ep_cap], stats [L, OFFSIM_PPO_LOG_STATS], counts [L, 2].  Learner l's outputs are, bit for bit, those of offsim_ppo_epoch_log on
+ * its own E columns; a learner without a valid step gets NaN statistics and zero counts.  L in 1..65535. */
+int offsim_ppo_epoch_log_pop(const float *rew, const float *value, const uint8_t *valid, const uint8_t *terminated, const uint8_t *truncated,
+                             int64_t T, int32_t L, int64_t E, int32_t eplen_mode, double *open_ret, int32_t *open_len, double *stats,
+                             int64_t *counts, double *ep_ret, int32_t *ep_len, int32_t *n_ep, int64_t ep_cap, void *stream);
+
 /* ---- the PPO update (PPOLearner.update, ppo_grad) --------------------------------------------------------------------------------
  * PPOAgentRevealed.adapt (offsim4rl/agents/ppo.py:162-223) over M records -- a PPO buffer as offsim_vector_collect_ppo and
  * offsim_ppo_advantages leave it, [T*E] step-major, or any flat batch -- for one network at a time (kind):

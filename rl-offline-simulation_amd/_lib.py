@@ -92,6 +92,8 @@ class CollectOut(C.Structure):
 
 VALUE_MLP, VALUE_ROWS = 0, 1
 PPO_BOOT_REFERENCE, PPO_BOOT_SPINUP = 0, 1
+EPLEN_REFERENCE, EPLEN_STEPS = 0, 1
+PPO_LOG_STATS = 10
 
 
 def ppo_work_doubles(E):
@@ -270,7 +272,9 @@ SIGNATURES = {
     "offsim_vector_collect_ppo_pop": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), C.POINTER(CollectPolicy), C.POINTER(CollectValue), _i32, _i32,
                                                 _i32, _i32, _i64, _i32, C.POINTER(CollectState), C.POINTER(CollectOut), C.POINTER(CollectPPOOut), _vp]),
     "offsim_ppo_advantages_pop": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, C.c_double, C.c_double, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "offsim_ppo_update_work_doubles_pop": (_i64, [C.POINTER(PPONet), _i32, _i64]),
+    "offsim_ppo_epoch_log": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "offsim_ppo_epoch_log_pop": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "offsim_ppo_update_work_doubles_pop":(_i64, [C.POINTER(PPONet), _i32, _i64]),
     "offsim_ppo_grad_pop": (C.c_int, [C.POINTER(PPONet), _i32, C.POINTER(PPOBatchC), _i32, _i32, C.POINTER(C.c_double), _vp, _vp, _vp, _vp]),
     "offsim_ppo_update_pop": (C.c_int, [C.POINTER(PPONet), _i32, C.POINTER(PPOBatchC), _i32, _i32, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32,
                                         C.POINTER(PPOAdamPop), _vp, _vp, _vp, _vp]),

@@ -2338,6 +2338,9 @@ extern "C" int offsim_value_mlp(const void *x, int32_t x_dtype, int64_t n_x, int
 // ---- the PPO buffer: GAE-lambda, rewards-to-go and spinup's normalisation over [T, E] records (csrc/ppo_buffer.hpp) ----
 #include "ppo_buffer.hpp"
 
+// ---- the epoch log of the reference's PPO agent: episode returns / lengths with a carry, VVals, their statistics (csrc/ppo_log.hpp) ----
+#include "ppo_log.hpp"
+
 // ---- the PPO update: fused forward / loss / backward, reduce + Adam, early stop on the device (csrc/ppo_update.hpp) ----
 #include "ppo_update.hpp"
 

@@ -145,6 +145,17 @@ class PPOLearner:
         return PPOUpdateInfo(LossPi=ps[0], LossV=vs[0], KL=ps[2], Entropy=ps[3], ClipFrac=ps[4], DeltaLossPi=ps[1] - ps[0],
                              DeltaLossV=vs[1] - vs[0], StopIter=ps[5].to(torch.int64))
 
+    def fit(self, env, epochs, T, tracker=None, **collect_kwargs):
+        """The training loop of the reference's example (examples/cartpole/psrs_from_expert_heuristic.py) inside the VectorPSRS `env`:
+        per epoch env.collect_ppo(actor, critic, T, **collect_kwargs), ppo_epoch_log of the batch, update(batch) -- nothing more, all
+        of it enqueued, nothing read back between epochs.  tracker: the EpisodeTracker that carries the open episodes (a fresh one if
+        None; pass your own to go on from an earlier fit).  Returns a PPOTrainLog of [epochs] device tensors.  An epoch in which the
+        log ran dry shows in StepsServed and as NaN rows; fit does not stop or synchronise for it."""
+        from .ppo_log import EpisodeTracker, _fit
+        if tracker is None:
+            tracker = EpisodeTracker(env.num_envs, env.table.device)
+        return _fit(lambda: env.collect_ppo(self.actor, self.critic, T, **collect_kwargs), self.update, tracker, epochs, T, env.num_envs, True, 1)
+
     def adam_state(self, device=None):
         """((m, v, t) of the actor, (m, v, t) of the critic): the device tensors of the optimiser states."""
         key = str(device) if device is not None else next(iter(self._opt))

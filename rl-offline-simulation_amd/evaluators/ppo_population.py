@@ -154,6 +154,17 @@ class PPOPopulation:
         return PPOUpdateInfo(LossPi=ps[:, 0], LossV=vs[:, 0], KL=ps[:, 2], Entropy=ps[:, 3], ClipFrac=ps[:, 4], DeltaLossPi=ps[:, 1] - ps[:, 0],
                              DeltaLossV=vs[:, 1] - vs[:, 0], StopIter=ps[:, 5].to(torch.int64))
 
+    def fit(self, env, epochs, T, tracker=None, **collect_kwargs):
+        """PPOLearner.fit for every learner at once: per epoch env.collect_ppo_population(self, T, **collect_kwargs), ppo_epoch_log over
+        the L learners, update(batch); everything enqueued, nothing read back between epochs.  env: a VectorPSRS of L * E environments,
+        learner-major; tracker: the EpisodeTracker over them (a fresh one if None).  Returns a PPOTrainLog of [epochs, L] device tensors:
+        column l is, bit for bit, PPOLearner.fit of learner l on its own E environments."""
+        from .ppo_log import EpisodeTracker, _fit
+        if tracker is None:
+            tracker = EpisodeTracker(env.num_envs, env.table.device)
+        return _fit(lambda: env.collect_ppo_population(self, T, **collect_kwargs), self.update, tracker, epochs, T, env.num_envs // self.L, False,
+                    self.L)
+
     def adam_state(self):
         """((m [L, P], v [L, P], t [L]) of the actors, the same of the critics): the device tensors of the optimiser states."""
         if self._pi.device is None:

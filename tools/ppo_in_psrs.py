@@ -8,10 +8,16 @@ logged dataset), vectorised: E environments play E spinup MPI processes of T loc
      the collect kernel reads; --update torch: torch autograd over PPOBatch.flat(), the new weights read back into the MLPPolicy /
      MLPValue with from_torch every epoch (the comparison route).
 
-Prints per epoch the mean return of the episodes that ended in it, the simulated steps per second of the collect, and the split of the
-epoch's time between collect and update.  Uses the synthetic CartPole log of synth.cartpole_log (a uniform-random logging policy).
+  3. the epoch log of the agent (EpRet, EpLen, EpisodesInEpoch, VVals; ppo.py:225-235) --
+     --log device (default): ppo_epoch_log, one launch on the records with the open episodes carried in an EpisodeTracker;
+     --log host: the loop over the T steps in Python (episode_returns below, T host reads per epoch; the comparison route).
 
-usage: python tools/ppo_in_psrs.py [--rows 1000000] [--envs 1024] [--steps 256] [--epochs 20] [--hid 64] [--l 2] [--update device|torch]"""
+Prints per epoch the mean return of the episodes that ended in it (under either --log), the simulated steps per second of the collect, and
+the split of the epoch's time between collect and update; with --log device also the reference's EpLen, EpisodesInEpoch and VVals.  Uses the
+synthetic CartPole log of synth.cartpole_log (a uniform-random logging policy).
+
+usage: python tools/ppo_in_psrs.py [--rows 1000000] [--envs 1024] [--steps 256] [--epochs 20] [--hid 64] [--l 2] [--update device|torch]
+                                   [--log device|host]"""
 import argparse
 import os
 import sys
@@ -24,7 +30,7 @@ from torch.optim import Adam
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from rl_offline_simulation_amd import OfflineDataset, ProbDistribution, spaces, synth  # noqa: E402
 from rl_offline_simulation_amd.encoders import CartpoleBoxEncoder  # noqa: E402
-from rl_offline_simulation_amd.evaluators import MLPPolicy, MLPValue, PPOLearner, VectorPSRS  # noqa: E402
+from rl_offline_simulation_amd.evaluators import EpisodeTracker, MLPPolicy, MLPValue, PPOLearner, VectorPSRS, ppo_epoch_log  # noqa: E402
 
 
 def net(sizes):
@@ -65,6 +71,7 @@ def main():
     ap.add_argument("--target-kl", type=float, default=0.01)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--update", choices=("device", "torch"), default="device")
+    ap.add_argument("--log", choices=("device", "host"), default="device", help="the epoch log: ppo_epoch_log, or the Python loop over the steps")
     a = ap.parse_args()
 
     e = synth.cartpole_log(a.rows, seed=a.seed)
@@ -76,7 +83,8 @@ def main():
     torch.manual_seed(a.seed)
     pi_net = net([4] + [a.hid] * a.l + [2]).cuda()
     v_net = net([4] + [a.hid] * a.l + [1]).cuda()
-    open_ret = torch.zeros(a.envs, device="cuda")
+    open_ret = torch.zeros(a.envs, device="cuda")  # (--log host)
+    tracker = EpisodeTracker(a.envs, "cuda")  # (--log device)
     actor, critic = MLPPolicy.from_torch(pi_net), MLPValue.from_torch(v_net)
     if a.update == "device":  # (pi_net / v_net only supply the initial weights; the learner steps the device copy the kernel reads)
         learner = PPOLearner(actor, critic, pi_lr=a.pi_lr, vf_lr=a.vf_lr, clip_ratio=a.clip_ratio, train_pi_iters=a.train_pi_iters,
@@ -123,11 +131,18 @@ def main():
                 v_opt.step()
         torch.cuda.synchronize()
         t2 = time.perf_counter()
-        rets = episode_returns(b, open_ret)
+        extra = ""
+        if a.log == "host":
+            rets = episode_returns(b, open_ret)
+        else:  # one launch; the lists are read back here only because this script prints the mean over ENDED episodes under either --log
+            log, eps = ppo_epoch_log(b, tracker, episodes=True)
+            rets = eps.ep_ret[torch.arange(eps.ep_ret.shape[1], device="cuda")[None, :] < eps.n_ep[:, None]]
+            extra = (f"  EpRet {float(log.EpRet):.2f} +- {float(log.StdEpRet):.2f} [{float(log.MinEpRet):.1f}, {float(log.MaxEpRet):.1f}] over "
+                     f"{int(log.Entries)} entries  EpLen {float(log.EpLen):.1f}  EpisodesInEpoch {int(log.EpisodesInEpoch)}  VVals {float(log.VVals):.3f}")
         served = int(b.valid.sum())
         ep = f"{float(rets.mean()):8.2f} over {rets.numel():6d} episodes" if rets.numel() else "      -- (no episode ended)"
         print(f"epoch {epoch:3d}: return {ep}  {served / (t1 - t0):.3e} simulated steps/s  collect {1e3 * (t1 - t0):7.2f} ms  "
-              f"update {1e3 * (t2 - t1):7.2f} ms (StopIter {stop})", flush=True)
+              f"update {1e3 * (t2 - t1):7.2f} ms (StopIter {stop}){extra}", flush=True)
 
 
 if __name__ == "__main__":
