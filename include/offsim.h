@@ -371,6 +371,52 @@ int offsim_eval_td(const offsim_table *t, offsim_rollouts *ro, const double *pi,
                    const double *gamma_pow, int64_t n_gamma_pow, int64_t max_episodes, const offsim_evalmc_out *out,
                    const offsim_td *td, void *stream);
 
+/* offsim_eval_mc_exo: whole rollouts on PSRS_Exo (offsim4rl/evaluators/psrs.py:59-117) under the reference's three drivers -- evalMC_psrs
+ * (td = NULL), qlearn_psrs and expSARSA_psrs (td->mode; psrs.py:119-271) -- for all rollouts in ONE launch (csrc/eval_exo.hpp).
+ * ts / rs, tx / rx: the two queue families of offsim_step_exo (same log: ts->N == tx->N, ts->N0 == tx->N0; rs->R == rx->R).  Rollout r
+ * reads its own orders (rs->perm, rx->perm, rs->init_perm with their strides; NULL: table order) and owns its cursors of both families,
+ * rs->init_cursor[r] and rs / rx->cur_slot[r]; all of it is written back (rx->init_cursor[r] follows rs's), so a later call or a later
+ * offsim_step_exo continues where this one stopped.
+ *   reset   the next entry of the s-table's init order; s and x are that row's (psrs.py:91-97)
+ *   step    pops s_queues[s] and x_queues[x] together until a candidate is accepted (default reject rule, offsim_step_exo's p_log / prob
+ *           dispatch); either queue empty: OFFSIM_ST_EXHAUSTED, the state stays; a slot without rows or out of range in either family:
+ *           OFFSIM_ST_KEYERROR.  Reward, done and s' are the accepted s-row's, x' the x-row's popped with it; G += gamma_pow[t] * r.
+ * The policy and Q are indexed by the OBSERVATION o = o_combine_func(s, x) (psrs.py:255, :158, :214):
+ *   obs_of [ts->n_slots, tx->n_slots] i32   the row of pi / Q for that pair of slots, 0 .. n_obs-1 (several pairs may share a row); -1 (or
+ *                                           anything outside the range) where pi has no row: reaching such a pair stops the rollout
+ *                                           with OFFSIM_ST_KEYERROR (the reference raises IndexError at pi[S] / Q[S'])
+ *   pi [n_obs, nA]                          f32 for OFFSIM_PROB_F32 (f32 p_log), f64 otherwise
+ * reseed, the rejection stream:
+ *   OFFSIM_EXO_RESEED_EPISODE  the reference's protocol: PSRS_Exo.reset(seed) restarts the stream (psrs.py:92) and the drivers call
+ *                              env.reset(seed=episode), so episode e of this call draws from default_rng(episode0 + e) -- seeded at
+ *                              the reset, before the init queue is looked at.  PCG64 only: rs->rng_kind = OFFSIM_STREAM_PHILOX is
+ *                              refused with OFFSIM_EUNSUPPORTED.  On exit rs->rng[r] holds the state after the last draw.
+ *   OFFSIM_EXO_RESEED_NONE     the rollout's own stream rs->rng[r] (either provider) runs on across episodes and is advanced.
+ * out: offsim_eval_mc's, trace_row holding the accepted s-rows.  xout (optional, members optional):
+ *   trace_row_x [R, out->trace_cap] i32  caller rows of the x-rows popped with the accepted s-rows
+ *   last [R,3] i32                       where env.o comes from when the loop stops: caller row of the last accepted s-row, caller row of
+ *                                        the x-row popped with it, caller row of the initial row when no step was accepted since the
+ *                                        last reset; -1 where a field does not apply.  Left unwritten when no reset served a row.
+ * td (NULL: evalMC): OFFSIM_TD_QLEARN / OFFSIM_TD_EXPSARSA on td->q [R, n_obs, nA] f64 -- the update, td_err, alpha_ep, q_snap /
+ *   snap_stride / snap_cap and the left-to-right sum of Q[S'] @ pi[S'] are offsim_eval_td's with the slot replaced by obs_of[s, x];
+ *   OFFSIM_PROB_F64 only.  An accepted step whose next pair has no row stops the rollout with OFFSIM_ST_KEYERROR: the environment has
+ *   stepped (cursors, state, last), the step is not counted.  Behaviour policy: OFFSIM_BEHAVIOUR_FIXED only -- the epsilon-greedy and
+ *   soft-greedy behaviours on the learner's own Q and the tie stream (td->tie_mt) return OFFSIM_EUNSUPPORTED: deliberately not built.
+ * LDS per workgroup: jump tables, pi, obs_of, both seg_off arrays, per-rollout cursors of both families and per-rollout Q; 4 rollouts per
+ *   workgroup, then 2, then 1 while the carve exceeds 64 KiB, one rollout up to 160 KiB, beyond that OFFSIM_EUNSUPPORTED.
+ * Argument validation happens before any HIP call -- the two tables, rs / rx, n_obs / obs_of / pi, the prob mode, the reseed / provider
+ * pair, the TD mode and behaviour, the capacities, the LDS size --; rs->R = 0 launches nothing. */
+#define OFFSIM_EXO_RESEED_NONE 0
+#define OFFSIM_EXO_RESEED_EPISODE 1
+typedef struct offsim_exo_out {
+    int32_t *trace_row_x;
+    int32_t *last;
+} offsim_exo_out;
+int offsim_eval_mc_exo(const offsim_table *ts, const offsim_table *tx, offsim_rollouts *rs, offsim_rollouts *rx, const void *pi,
+                       const int32_t *obs_of, int32_t n_obs, int32_t prob_mode, int32_t reseed, uint64_t episode0, double gamma,
+                       const double *gamma_pow, int64_t n_gamma_pow, int64_t max_episodes, const offsim_evalmc_out *out,
+                       const offsim_exo_out *xout, const offsim_td *td /* NULL: evalMC */, void *stream);
+
 /* Fast path of evalMC_psrs for a fixed tabular policy (the headline scan).
  * offsim_compile_policy folds psrs.py:53-57 for policy pi [n_slots,nA] f64 into one 64-bit key per grouped row:
  *   key = T << 11 | done << 10 | z_next_slot,  T = floor(2^53 * pi[z][a]/p_log[a]/max_a'(pi[z][a']/p_log[a'])),

@@ -210,6 +210,13 @@ class StepMailbox(C.Structure):
 
 TD_QLEARN, TD_EXPSARSA = 1, 2
 BEHAVIOUR_FIXED, BEHAVIOUR_EPS_GREEDY, BEHAVIOUR_SOFT_GREEDY = 0, 1, 2
+EXO_RESEED_NONE, EXO_RESEED_EPISODE = 0, 1
+
+
+class ExoOut(C.Structure):
+    """struct offsim_exo_out"""
+    _fields_ = [("trace_row_x", _vp), ("last", _vp)]
+
 
 # name -> (restype, argtypes): exactly the entry points include/offsim.h declares
 SIGNATURES = {
@@ -233,6 +240,8 @@ SIGNATURES = {
                                   _vp, _vp, _vp, _vp, _vp]),
     "offsim_eval_td": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), _vp, _i32, C.c_double, _vp, _i64, _i64,
                                  C.POINTER(EvalMCOut), C.POINTER(TD), _vp]),
+    "offsim_eval_mc_exo": (C.c_int, [C.POINTER(Table), C.POINTER(Table), C.POINTER(Rollouts), C.POINTER(Rollouts), _vp, _vp, _i32, _i32, _i32,
+                                     C.c_uint64, C.c_double, _vp, _i64, _i64, C.POINTER(EvalMCOut), C.POINTER(ExoOut), C.POINTER(TD), _vp]),
     "offsim_compile_policy": (C.c_int, [C.POINTER(Table), _vp, _vp, _vp]),
     "offsim_eval_mc_keys_kernel": (C.c_char_p, [_i32, _i32]),
     "offsim_compile_digests": (C.c_int, [C.POINTER(Table), _vp, _i32, _vp, _vp]),

@@ -1762,6 +1762,9 @@ extern "C" int offsim_eval_td(const offsim_table *t, offsim_rollouts *ro, const 
     });
 }
 
+// ---- whole rollouts on PSRS_Exo: evalMC_psrs / qlearn_psrs / expSARSA_psrs over two queue families (csrc/eval_exo.hpp) ----
+#include "eval_exo.hpp"
+
 // ------------------------------------------------------------------------------------------------
 // Fast evalMC scan: compiled-policy keys + LDS candidate windows (scan_win.hpp)
 // ------------------------------------------------------------------------------------------------

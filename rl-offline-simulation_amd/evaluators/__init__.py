@@ -2,7 +2,7 @@ from .psrs import PSRS, BatchedPSRS, evalMC_psrs, evalmc_rollouts, qlearn_psrs, 
 from .per_state_rejection import PerStateRejectionSampling  # noqa: F401
 from .trivial_baselines import FollowObservationOnly, FollowActionOnly, ServeRandomTransitions  # noqa: F401
 from .queue_evaluator import QueueEvaluator, BatchedQueueEvaluator  # noqa: F401
-from .psrs_exo import PSRS_Exo  # noqa: F401
+from .psrs_exo import PSRS_Exo, BatchedPSRSExo, evalmc_rollouts_exo, tabulate_obs  # noqa: F401
 from .vector_env import VectorPSRS  # noqa: F401
 from .obs_policy import MLPPolicy, RowPolicy, CallablePolicy, MLPValue, RowValue, PolicyPopulation  # noqa: F401
 from .batched import evalmc_rollouts_population  # noqa: F401

@@ -3,6 +3,7 @@
   PSRS          the reference's single-environment class (psrs.py:5-57), as BatchedPSRS (batched.py) with R = 1
   evalMC_psrs   psrs.py:241-271; one kernel launch when given a device-backed env
   qlearn_psrs / expSARSA_psrs   psrs.py:119-239, whole on the device (offsim_eval_td)
+All three also take a PSRS_Exo (psrs_exo.py: two queue families, tables indexed by the observation), one launch of offsim_eval_mc_exo each.
 
 The batched engine itself -- BatchedPSRS, evalmc_rollouts, the stream layouts -- lives in batched.py and is re-exported here (callers
 and tests import it from either).  No CPU fallback.
@@ -14,6 +15,7 @@ import torch
 
 from .. import _lib as L
 from ..table import TransitionTable
+from . import psrs_exo as _exo
 from .batched import (BatchedPSRS, SHUFFLE_NONE, SHUFFLE_PER_ROLLOUT, SHUFFLE_SHARED, ROWS_MAX_ALL_REJECTED, ROWS_MAX_WINDOW_LOAD,  # noqa: F401
                       ROWS_TICK_STEPS, _gamma_pow, _prob_mode, evalmc_rollouts, resident_rollouts, rollout_resident_bytes, stream_format)
 
@@ -223,6 +225,8 @@ def evalMC_psrs(env, n_episodes, pi, gamma):
     from .obs_policy import ObsPolicy
     if isinstance(pi, ObsPolicy):
         return _evalmc_obs_policy(env, n_episodes, pi, gamma)
+    if isinstance(env, _exo.PSRS_Exo):  # two queue families, pi indexed by the observation o_combine_func(s, x): offsim_eval_mc_exo
+        return _exo.evalmc_exo(env, n_episodes, pi, gamma)
     _require_device_env(env, "evalMC_psrs")
     pi = np.asarray(pi)
     if pi.ndim != 2:
@@ -447,6 +451,14 @@ def qlearn_psrs(env, n_episodes, behavior_policy, gamma, alpha=0.1, epsilon=1.0,
     recognised by probing, see _behaviour_kind); alpha and epsilon may be callables of the episode (psrs.py:128-135); ties between
     maximal Q values are broken with NumPy's global stream exactly as the reference's _random_argmax does, and the stream is left
     where the reference would leave it; save_Q returns Q after every step (psrs.py:172-173)."""
+    if isinstance(env, _exo.PSRS_Exo):
+        kind, fixed = _behaviour_kind(behavior_policy, env.nA)
+        if kind != "fixed":
+            raise NotImplementedError(f"qlearn_psrs on a PSRS_Exo: the behaviour policy is {kind}, which acts on the learner's own Q row; the two-queue "
+                                      "kernel (offsim_eval_mc_exo) keeps the behaviour policy as a fixed table and has no tie stream, so only "
+                                      "Q-independent policies (uniformly_random_policy) run there")
+        n_rows = env.nS if Q_init is None else int(np.shape(Q_init)[0])
+        return _exo.td_exo(env, "qlearn_psrs", n_episodes, gamma, alpha, Q_init, save_Q, L.TD_QLEARN, np.tile(np.asarray(fixed, dtype=np.float64), (n_rows, 1)))
     _require_device_env(env, "qlearn_psrs")
     kind, fixed = _behaviour_kind(behavior_policy, env.nA)
     t = env.table
@@ -458,8 +470,11 @@ def qlearn_psrs(env, n_episodes, behavior_policy, gamma, alpha=0.1, epsilon=1.0,
 def expSARSA_psrs(env, n_episodes, pi, gamma, alpha=0.1, Q_init=None, save_Q=0):
     """psrs.py:187-239: expected SARSA under a fixed target / behaviour policy pi, one kernel launch; alpha may be a callable of the
     episode, save_Q returns Q after every step."""
-    _require_device_env(env, "expSARSA_psrs")
+    if not isinstance(env, _exo.PSRS_Exo):
+        _require_device_env(env, "expSARSA_psrs")
     pi = np.asarray(pi, dtype=np.float64)
     if pi.ndim != 2:
         raise ValueError("expSARSA_psrs: pi must be a [nS, nA] table")
+    if isinstance(env, _exo.PSRS_Exo):
+        return _exo.td_exo(env, "expSARSA_psrs", n_episodes, gamma, alpha, Q_init, save_Q, L.TD_EXPSARSA, pi)
     return _td_run(env, "expSARSA_psrs", n_episodes, gamma, alpha, Q_init, save_Q, L.TD_EXPSARSA, "fixed", pi, 0.0)
