@@ -371,6 +371,62 @@ int offsim_eval_td(const offsim_table *t, offsim_rollouts *ro, const double *pi,
                    const double *gamma_pow, int64_t n_gamma_pow, int64_t max_episodes, const offsim_evalmc_out *out,
                    const offsim_td *td, void *stream);
 
+/* offsim_eval_td_pop: offsim_eval_td for a population of L learners on the same S seeds in ONE launch (comparing the learning curves of a
+ * grid of step sizes, exploration rates and discounts over many sampler seeds: every learner of a seed sees the same queues and the same
+ * draws, so differences between learners are paired).
+ *   ro->R = L * S, learner-major: rollout r = l * S + j is learner l on seed j.  ro->rng, cursor, init_cursor and cur_slot are [R] rows as
+ *   always (the caller's S rows replicated L times) and are advanced and written back per rollout.
+ *   ro->perm / ro->init_perm hold S orders, not R: rollout r reads row j (perm_stride = 0: one shared order; NULL: table order) -- the
+ *   stride rule of offsim_eval_mc_rows_policy_pop.  The kernel only reads the orders.
+ * Per learner (device arrays, one entry per learner unless said otherwise):
+ *   alpha, epsilon, gamma [L] f64; gamma_pow [L, n_gamma_pow] f64, row l the discount table of gamma[l] (the rule of offsim_eval_mc's
+ *   gamma_pow, per learner: a row that is stationary before n_gamma_pow is padded with its last entry, which is exact);
+ *   behaviour [L] i32 OFFSIM_BEHAVIOUR_*, and behaviour_host, the same L values in HOST memory, which is what is validated;
+ *   alpha_ep / epsilon_ep [L, n_sched] f64 or NULL (the constants); pi [L, n_slots, nA] f64 with pi_stride = n_slots * nA, or one table
+ *   [n_slots, nA] shared by all learners with pi_stride = 0.
+ *   mode is one value per launch (OFFSIM_TD_QLEARN or OFFSIM_TD_EXPSARSA).
+ * Per rollout, [L * S, ...] in the layouts of offsim_td: q, td_err / td_cap, q_snap / snap_cap / snap_stride, tie_mt [L * S, 625] or NULL,
+ * beh_arg.  out: offsim_evalmc_out as it is, [L * S] rows.
+ * Rollout l * S + j equals, in every output bit and in the state it leaves, offsim_eval_td run alone with learner l's setting from seed j's
+ * state and order (the loop is the same code: k_eval_mc's TD instance under a population index, csrc/td_pop.hpp).  A workgroup holds
+ * rollouts of one learner (grid = L * ceil(S / waves)); the LDS carve, the 4 / 2 / 1 rollouts per workgroup and the refusal past 160 KiB
+ * (OFFSIM_EUNSUPPORTED) are offsim_eval_td's.  L in 1..65535, S >= 1, ro->R = L * S, a behaviour outside OFFSIM_BEHAVIOUR_*, NULL
+ * per-learner arrays, schedules without n_sched, a bad snapshot stride: OFFSIM_EINVAL.  Argument validation happens before any HIP call;
+ * ro->R = 0 launches nothing. */
+typedef struct offsim_td_pop {
+    int32_t mode;
+    const double *alpha;
+    const double *epsilon;
+    const double *gamma;
+    const double *gamma_pow;
+    int64_t n_gamma_pow;
+    const int32_t *behaviour;
+    const int32_t *behaviour_host;
+    const double *alpha_ep;
+    const double *epsilon_ep;
+    int64_t n_sched;
+    const double *pi;
+    int64_t pi_stride;
+    double *q;
+    double *td_err;
+    int64_t td_cap;
+    double *q_snap;
+    int64_t snap_cap;
+    int64_t snap_stride;
+    uint32_t *tie_mt;
+    int32_t *beh_arg;
+} offsim_td_pop;
+int offsim_eval_td_pop(const offsim_table *t, offsim_rollouts *ro, int32_t L, int32_t S, const offsim_td_pop *pop, int32_t reject_mode,
+                       int64_t max_episodes, const offsim_evalmc_out *out, void *stream);
+
+/* offsim_td_curves: the learning curves of a population on the device.  ep_g [L * S, ep_cap] f64 and n_ep [L * S] i64 are
+ * offsim_eval_td_pop's outputs (learner-major).  For learner l and episode e < ep_cap, over the seeds j with e < n_ep[l * S + j] (completed
+ * episodes only): n_out[l, e] their number (i64), mean_out[l, e] the mean return, var_out[l, e] the population variance (two passes: the
+ * mean first, then the mean squared deviation).  One thread per (l, e) sums in seed order j = 0 .. S - 1 in f64 without atomics, so the
+ * numbers equal a plain float loop in that order bit for bit and two calls give the same bits.  n = 0: NaN (0x7ff8000000000000) for both. */
+int offsim_td_curves(const double *ep_g, const int64_t *n_ep, int32_t L, int32_t S, int64_t ep_cap, int64_t *n_out, double *mean_out,
+                     double *var_out, void *stream);
+
 /* offsim_eval_mc_exo: whole rollouts on PSRS_Exo (offsim4rl/evaluators/psrs.py:59-117) under the reference's three drivers -- evalMC_psrs
  * (td = NULL), qlearn_psrs and expSARSA_psrs (td->mode; psrs.py:119-271) -- for all rollouts in ONE launch (csrc/eval_exo.hpp).
  * ts / rs, tx / rx: the two queue families of offsim_step_exo (same log: ts->N == tx->N, ts->N0 == tx->N0; rs->R == rx->R).  Rollout r

@@ -59,6 +59,14 @@ class TD(C.Structure):
                 ("tie_mt", _vp), ("beh_arg", _vp)]
 
 
+class TDPop(C.Structure):
+    """struct offsim_td_pop"""
+    _fields_ = [("mode", _i32), ("alpha", _vp), ("epsilon", _vp), ("gamma", _vp), ("gamma_pow", _vp), ("n_gamma_pow", _i64), ("behaviour", _vp),
+                ("behaviour_host", C.POINTER(_i32)), ("alpha_ep", _vp), ("epsilon_ep", _vp), ("n_sched", _i64), ("pi", _vp), ("pi_stride", _i64),
+                ("q", _vp), ("td_err", _vp), ("td_cap", _i64), ("q_snap", _vp), ("snap_cap", _i64), ("snap_stride", _i64), ("tie_mt", _vp),
+                ("beh_arg", _vp)]
+
+
 ACT_IDENTITY, ACT_TANH, ACT_RELU, ACT_LEAKY_RELU = 0, 1, 2, 3
 POLICY_MLP_MAX_LAYERS, POLICY_MLP_MAX_IN, POLICY_MLP_MAX_HIDDEN, POLICY_MLP_MAX_ACTIONS = 4, 128, 256, 16
 
@@ -240,6 +248,8 @@ SIGNATURES = {
                                   _vp, _vp, _vp, _vp, _vp]),
     "offsim_eval_td": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), _vp, _i32, C.c_double, _vp, _i64, _i64,
                                  C.POINTER(EvalMCOut), C.POINTER(TD), _vp]),
+    "offsim_eval_td_pop": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), _i32, _i32, C.POINTER(TDPop), _i32, _i64, C.POINTER(EvalMCOut), _vp]),
+    "offsim_td_curves": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp]),
     "offsim_eval_mc_exo": (C.c_int, [C.POINTER(Table), C.POINTER(Table), C.POINTER(Rollouts), C.POINTER(Rollouts), _vp, _vp, _i32, _i32, _i32,
                                      C.c_uint64, C.c_double, _vp, _i64, _i64, C.POINTER(EvalMCOut), C.POINTER(ExoOut), C.POINTER(TD), _vp]),
     "offsim_compile_policy": (C.c_int, [C.POINTER(Table), _vp, _vp, _vp]),

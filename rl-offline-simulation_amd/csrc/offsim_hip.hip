@@ -931,18 +931,35 @@ struct RowPolicyArgs {
 struct RowPolicyPopArgs : RowPolicyArgs {
     int32_t S;
 };
-template <bool POP>
-using RowArgs = std::conditional_t<POP, RowPolicyPopArgs, RowPolicyArgs>;
+// POP = true with TD: a population of L tabular learners on the same S seeds (offsim_eval_td_pop; arguments and launch shape in
+// csrc/td_pop.hpp).  The instance overwrites its per-launch hyper-parameters -- td.alpha / epsilon / behaviour / the schedule rows, gamma,
+// gamma_pow, pi -- with its workgroup's learner's before anything reads them; from there on it is the TD loop below, unchanged.
+#include "td_pop.hpp"
+template <bool TD, bool POP>
+using RowArgs = std::conditional_t<!POP, RowPolicyArgs, std::conditional_t<TD, TdPopArgs, RowPolicyPopArgs>>;
 
 template <typename PL, typename PROB, bool TD, bool ROWP = false, bool POP = false>
 __global__ void __launch_bounds__(256, 4) k_eval_mc(offsim_table t, offsim_rollouts ro, const PROB *__restrict__ pi,
                                                  int reject_mode, double gamma, const double *__restrict__ gamma_pow,
                                                  int64_t n_gamma_pow, int64_t max_episodes, offsim_evalmc_out out, offsim_td td,
-                                                 RowArgs<POP> rp) {
+                                                 RowArgs<TD, POP> rp) {
     static_assert(!(TD && ROWP), "the learner drivers index their tables by state");
-    static_assert(!POP || ROWP, "a population is a population of row policies");
+    static_assert(!POP || ROWP || TD, "a population is a population of row policies or of learners");
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const int waves = blockDim.x / WAVE;
+    int pop_l = 0, pop_nb = 1;  // TD + POP: this workgroup's learner, workgroups per learner
+    if constexpr (TD && POP) {
+        pop_nb = (rp.S + waves - 1) / waves;
+        pop_l = blockIdx.x / pop_nb;
+        td.alpha = rp.alpha[pop_l];
+        td.epsilon = rp.epsilon[pop_l];
+        td.behaviour = rp.behaviour[pop_l];
+        td.alpha_ep = rp.alpha_ep ? rp.alpha_ep + (int64_t)pop_l * td.n_sched : nullptr;
+        td.epsilon_ep = rp.epsilon_ep ? rp.epsilon_ep + (int64_t)pop_l * td.n_sched : nullptr;
+        gamma = rp.gamma[pop_l];
+        gamma_pow = rp.gamma_pow + (int64_t)pop_l * n_gamma_pow;
+        pi = (const PROB *)rp.pi + (int64_t)pop_l * rp.pi_stride;
+    }
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE), lane = threadIdx.x & (WAVE - 1);  // uniform -> SGPR
     const int n_slots = t.n_slots, nA = t.nA;
     // LDS carve: [jump tables][Q per wave (TD only)][pi][seg_off][cursors per wave]
@@ -959,12 +976,19 @@ __global__ void __launch_bounds__(256, 4) k_eval_mc(offsim_table t, offsim_rollo
         for (int i = threadIdx.x; i < n_slots * nA; i += blockDim.x) pi_lds[i] = pi[i];
     for (int i = threadIdx.x; i <= n_slots; i += blockDim.x) seg_lds[i] = t.seg_off[i];
     __syncthreads();
-    const int r = blockIdx.x * waves + wave;
-    if (r >= ro.R) return;
-    int pol = 0, ord = r;  // POP: the policy and the queue order of rollout r
-    if constexpr (POP) {
-        pol = r / rp.S;
-        ord = r - pol * rp.S;
+    int r = blockIdx.x * waves + wave;
+    int pol = 0, ord = r;  // POP: the policy (learner) and the queue order of rollout r
+    if constexpr (TD && POP) {
+        pol = pop_l;
+        ord = (blockIdx.x - pop_l * pop_nb) * waves + wave;
+        if (ord >= rp.S) return;
+        r = pol * rp.S + ord;
+    } else {
+        if (r >= ro.R) return;
+        if constexpr (POP) {
+            pol = r / rp.S;
+            ord = r - pol * rp.S;
+        }
     }
     uint32_t *cur_glb = ro.cursor + (int64_t)r * n_slots;
     for (int s = lane; s < n_slots; s += WAVE) cur_lds[s] = cur_glb[s];
@@ -993,8 +1017,8 @@ __global__ void __launch_bounds__(256, 4) k_eval_mc(offsim_table t, offsim_rollo
     int status = OFFSIM_ST_OK;
     bool terminate = false;
     // ROWP: the row whose probabilities the next step uses (grouped row of the last accepted step, or -1: the initial row k_init)
-    const PROB *__restrict__ p_next = (const PROB *)rp.p_next + (POP ? (int64_t)pol * t.N * nA : 0);
-    const PROB *__restrict__ p_init = (const PROB *)rp.p_init + (POP ? (int64_t)pol * t.N0 * nA : 0);
+    const PROB *__restrict__ p_next = (const PROB *)rp.p_next + (POP && ROWP ? (int64_t)pol * t.N * nA : 0);
+    const PROB *__restrict__ p_init = (const PROB *)rp.p_init + (POP && ROWP ? (int64_t)pol * t.N0 * nA : 0);
     int32_t g_prev = -1;
     uint32_t k_init = 0;
     bool no_init = false;
@@ -1189,7 +1213,7 @@ static int check_evalmc_out(const char *who, const offsim_evalmc_out *out, const
 template <typename PL, typename PROB, bool TD, bool ROWP, bool POP = false>
 static int evalmc_launch(const char *who, const offsim_table *t, offsim_rollouts *ro, const void *pi, int32_t reject_mode, double gamma,
                          const double *gamma_pow, int64_t n_gamma_pow, int64_t max_episodes, const offsim_evalmc_out *out, const offsim_td &td,
-                         const RowArgs<POP> &rp, void *stream) {
+                         const RowArgs<TD, POP> &rp, void *stream) {
     const size_t pb = ROWP ? 0 : sizeof(PROB);  // (ROWP: no pi block)
     int waves = 4;
     while (waves > 1 && evalmc_lds_bytes(waves, t->n_slots, t->nA, pb, TD) > 64 * 1024) waves >>= 1;
@@ -1198,7 +1222,9 @@ static int evalmc_launch(const char *who, const offsim_table *t, offsim_rollouts
         return fail(OFFSIM_EUNSUPPORTED, TD ? "%s: Q table, cursors and policy exceed 160 KiB of LDS" : ROWP ? "%s: per-state cursors exceed 160 KiB of LDS"
                                                                                                               : "%s: per-state cursors and policy exceed 160 KiB of LDS", who);
     if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_eval_mc<PL, PROB, TD, ROWP, POP>), (int)lds));
-    hipLaunchKernelGGL((k_eval_mc<PL, PROB, TD, ROWP, POP>), dim3((ro->R + waves - 1) / waves), dim3(waves * WAVE), lds, (hipStream_t)stream, *t, *ro,
+    unsigned grid = (unsigned)((ro->R + waves - 1) / waves);
+    if constexpr (TD && POP) grid = (unsigned)(ro->R / rp.S) * (unsigned)((rp.S + waves - 1) / waves);  // a workgroup holds rollouts of one learner
+    hipLaunchKernelGGL((k_eval_mc<PL, PROB, TD, ROWP, POP>), dim3(grid), dim3(waves * WAVE), lds, (hipStream_t)stream, *t, *ro,
                        (const PROB *)pi, reject_mode, gamma, gamma_pow, n_gamma_pow, max_episodes, *out, td, rp);
     LAUNCH_CHECK();
     return OFFSIM_OK;
@@ -1760,6 +1786,69 @@ extern "C" int offsim_eval_td(const offsim_table *t, offsim_rollouts *ro, const 
         return evalmc_launch<decltype(pl), double, true, false>("eval_td", t, ro, pi, reject_mode, gamma, gamma_pow, n_gamma_pow, max_episodes, out, *td,
                                                                 RowPolicyArgs{}, stream);
     });
+}
+
+// ---- offsim_eval_td for L learners on the same S seeds in one launch (k_eval_mc<.., TD, false, POP>, csrc/td_pop.hpp): every learner has its
+// own hyper-parameters, behaviour and target policy; the queue orders are the seeds', shared by all learners and only read.
+extern "C" int offsim_eval_td_pop(const offsim_table *t, offsim_rollouts *ro, int32_t L, int32_t S, const offsim_td_pop *pop, int32_t reject_mode,
+                                  int64_t max_episodes, const offsim_evalmc_out *out, void *stream) {
+    static const char *who = "eval_td_pop";
+    int rc = check_table(t);
+    if (rc) return rc;
+    if (!ro || ro->R < 0 || !pop || !out) return fail(OFFSIM_EINVAL, "%s: bad argument", who);
+    if (L < 1 || L > 65535 || S < 1) return fail(OFFSIM_EINVAL, "%s: L must be 1..65535 and S >= 1", who);
+    if (ro->R != 0 && (int64_t)ro->R != (int64_t)L * S) return fail(OFFSIM_EINVAL, "%s: ro->R must be L * S", who);
+    if ((rc = check_evalmc_out(who, out, pop->gamma_pow, pop->n_gamma_pow))) return rc;
+    if ((pop->mode != OFFSIM_TD_QLEARN && pop->mode != OFFSIM_TD_EXPSARSA) || !pop->q) return fail(OFFSIM_EINVAL, "%s: bad td mode or NULL q", who);
+    if (!pop->alpha || !pop->epsilon || !pop->gamma || !pop->behaviour || !pop->behaviour_host || !pop->pi || pop->pi_stride < 0 || pop->n_gamma_pow < 0)
+        return fail(OFFSIM_EINVAL, "%s: a per-learner array is NULL (alpha, epsilon, gamma, behaviour and its host copy, pi)", who);
+    for (int32_t l = 0; l < L; l++) {
+        const int32_t b = pop->behaviour_host[l];
+        if (b != OFFSIM_BEHAVIOUR_FIXED && b != OFFSIM_BEHAVIOUR_EPS_GREEDY && b != OFFSIM_BEHAVIOUR_SOFT_GREEDY) return fail(OFFSIM_EINVAL, "%s: bad behaviour", who);
+    }
+    if ((pop->alpha_ep || pop->epsilon_ep) && pop->n_sched <= 0) return fail(OFFSIM_EINVAL, "%s: schedules need n_sched > 0", who);
+    if (pop->q_snap && (pop->snap_stride <= 0 || pop->snap_cap < 0)) return fail(OFFSIM_EINVAL, "%s: bad snapshot stride / capacity", who);
+    if (ro->R == 0) return OFFSIM_OK;
+    offsim_td td{};  // per rollout: the members of offsim_td as they are; per learner: filled in by the kernel from rp
+    td.mode = pop->mode;
+    td.q = pop->q;
+    td.td_err = pop->td_err;
+    td.td_cap = pop->td_cap;
+    td.n_sched = pop->n_sched;
+    td.q_snap = pop->q_snap;
+    td.snap_cap = pop->snap_cap;
+    td.snap_stride = pop->snap_stride;
+    td.tie_mt = pop->tie_mt;
+    td.beh_arg = pop->beh_arg;
+    TdPopArgs rp{};
+    rp.S = S;
+    rp.alpha = pop->alpha;
+    rp.epsilon = pop->epsilon;
+    rp.gamma = pop->gamma;
+    rp.gamma_pow = pop->gamma_pow;
+    rp.behaviour = pop->behaviour;
+    rp.alpha_ep = pop->alpha_ep;
+    rp.epsilon_ep = pop->epsilon_ep;
+    rp.pi = pop->pi;
+    rp.pi_stride = pop->pi_stride;
+    return with_plog(t, [&](auto pl) -> int {
+        return evalmc_launch<decltype(pl), double, true, false, true>(who, t, ro, nullptr, reject_mode, 0.0, nullptr, pop->n_gamma_pow, max_episodes, out, td,
+                                                                      rp, stream);
+    });
+}
+
+// ---- the learning curves of a population: per learner and episode, count / mean / population variance of the returns over the seeds that
+// completed that episode (k_td_curves, csrc/td_pop.hpp)
+extern "C" int offsim_td_curves(const double *ep_g, const int64_t *n_ep, int32_t L, int32_t S, int64_t ep_cap, int64_t *n_out, double *mean_out,
+                                double *var_out, void *stream) {
+    if (L < 0 || S < 0 || ep_cap < 0) return fail(OFFSIM_EINVAL, "td_curves: negative size%s");
+    if ((int64_t)L * ep_cap > 0 && (!n_out || !mean_out || !var_out || ((int64_t)S > 0 && (!ep_g || !n_ep)))) return fail(OFFSIM_EINVAL, "td_curves: NULL argument%s");
+    const int64_t n = (int64_t)L * ep_cap;
+    if (n == 0) return OFFSIM_OK;
+    if ((n + 255) / 256 > 0x7fffffffll) return fail(OFFSIM_EUNSUPPORTED, "td_curves: more than 2^39 curve points%s");
+    hipLaunchKernelGGL(k_td_curves, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ep_g, n_ep, L, S, ep_cap, n_out, mean_out, var_out);
+    LAUNCH_CHECK();
+    return OFFSIM_OK;
 }
 
 // ---- whole rollouts on PSRS_Exo: evalMC_psrs / qlearn_psrs / expSARSA_psrs over two queue families (csrc/eval_exo.hpp) ----

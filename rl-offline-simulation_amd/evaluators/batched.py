@@ -766,6 +766,119 @@ class BatchedPSRS:
         o["_keepalive"] = (pi_d, gp, a_ep, e_ep)
         return o
 
+    # -- the same for L learners on this environment's R seeds, in one launch --
+    def eval_td_population(self, mode, alpha, gamma, behaviour=L.BEHAVIOUR_FIXED, epsilon=0.0, pi_slots=None, q_slots=None, alpha_ep=None,
+                           epsilon_ep=None, tie_mt=None, n_episodes=None, ep_cap=0, trace_cap=0, snap_cap=0, snap_stride=1, n_gamma_pow=4096):
+        """eval_td for L learners, each on every one of this environment's S = R rollouts (its seeds): L * S rollouts in one launch that
+        share the S queue orders (include/offsim.h, offsim_eval_td_pop).  alpha, gamma, behaviour (_lib.BEHAVIOUR_*) and epsilon are each
+        a scalar or [L]; pi_slots [n_slots,nA] or [L,n_slots,nA] (None: uniform); q_slots [n_slots,nA], [L,...], [L,S,...] or None
+        (zeros); alpha_ep / epsilon_ep [n_sched] or [L,n_sched]; tie_mt [L,S,625] or None.  L is the common length of the per-learner
+        arguments (1 when every one is shared); lengths that disagree raise ValueError.  mode is one value for the launch.
+        Returns eval_td's dict with [L, S, ...] leading dimensions; entry [l, j] is, bit for bit, what eval_td gives rollout j under
+        learner l's setting.  It is a query, like eval_mc_rows_policy_population: it runs on copies of the sampler state (every learner
+        of seed j sees the same queues and the same draws), and this environment's own cursors, rejection streams and current slots
+        are left as they were."""
+        self._quiesce()
+        self._orders_for_generic()
+        t, dev, S = self.table, self.table.device, self.R
+        f64 = lambda x: np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float64)  # noqa: E731
+        per = {"alpha": np.atleast_1d(f64(alpha)), "gamma": np.atleast_1d(f64(gamma)), "epsilon": np.atleast_1d(f64(epsilon)),
+               "behaviour": np.atleast_1d(np.asarray(behaviour, dtype=np.int64))}
+        if any(v.ndim != 1 for v in per.values()):
+            raise ValueError("eval_td_population: alpha, gamma, behaviour and epsilon are scalars or [L]")
+        lens = {k: len(v) for k, v in per.items() if len(v) != 1}
+        pi_t = None if pi_slots is None else torch.as_tensor(pi_slots if isinstance(pi_slots, torch.Tensor) else np.ascontiguousarray(pi_slots), dtype=torch.float64)
+        if pi_t is not None:
+            if pi_t.dim() not in (2, 3) or tuple(pi_t.shape[-2:]) != (t.n_slots, t.nA):
+                raise ValueError(f"eval_td_population: pi_slots [n_slots,nA] or [L,n_slots,nA] expected, got {tuple(pi_t.shape)}")
+            if pi_t.dim() == 3:
+                lens["pi_slots"] = int(pi_t.shape[0])
+        q_t = None if q_slots is None else torch.as_tensor(q_slots if isinstance(q_slots, torch.Tensor) else np.ascontiguousarray(q_slots), dtype=torch.float64)
+        if q_t is not None:
+            if q_t.dim() not in (2, 3, 4) or tuple(q_t.shape[-2:]) != (t.n_slots, t.nA) or (q_t.dim() == 4 and q_t.shape[1] != S):
+                raise ValueError(f"eval_td_population: q_slots [n_slots,nA], [L,n_slots,nA] or [L,S,n_slots,nA] expected, got {tuple(q_t.shape)}")
+            if q_t.dim() > 2:
+                lens["q_slots"] = int(q_t.shape[0])
+        sched = {}
+        for k, x in (("alpha_ep", alpha_ep), ("epsilon_ep", epsilon_ep)):
+            if x is not None:
+                sched[k] = np.atleast_1d(f64(x))
+                if sched[k].ndim not in (1, 2) or sched[k].shape[-1] < 1:
+                    raise ValueError(f"eval_td_population: {k} [n_sched] or [L,n_sched] expected")
+                if sched[k].ndim == 2:
+                    lens[k] = sched[k].shape[0]
+        mt = None
+        if tie_mt is not None:
+            mt = torch.as_tensor(np.ascontiguousarray(tie_mt).view(np.int32) if not isinstance(tie_mt, torch.Tensor) else tie_mt)
+            if mt.dim() != 3 or tuple(mt.shape[1:]) != (S, 625):
+                raise ValueError(f"eval_td_population: tie_mt [L,S,625] expected, got {tuple(mt.shape)}")
+            lens["tie_mt"] = int(mt.shape[0])
+        if len(set(lens.values())) > 1:
+            raise ValueError(f"eval_td_population: per-learner arguments of different lengths: {lens}")
+        n_l = next(iter(lens.values())) if lens else 1
+        if n_l < 1:
+            raise ValueError("eval_td_population: no learner")
+        R = n_l * S
+        beh_host = np.ascontiguousarray(np.broadcast_to(per["behaviour"], (n_l,)), dtype=np.int32)
+        dev_f64 = lambda a: torch.from_numpy(np.array(a, dtype=np.float64, order="C")).to(dev)  # noqa: E731  (a copy: broadcasts are read-only)
+        alpha_d, eps_d, gamma_d = (dev_f64(np.broadcast_to(per[k], (n_l,))) for k in ("alpha", "epsilon", "gamma"))
+        beh_d = torch.from_numpy(beh_host).to(dev)
+        n_sched = max([v.shape[-1] for v in sched.values()], default=0)
+        assert all(v.shape[-1] == n_sched for v in sched.values()), "alpha_ep and epsilon_ep cover the same episodes"
+        a_ep, e_ep = (dev_f64(np.broadcast_to(sched[k], (n_l, n_sched))) if k in sched else None for k in ("alpha_ep", "epsilon_ep"))
+        if pi_t is None:
+            pi_t = torch.full((t.n_slots, t.nA), 1.0 / t.nA, dtype=torch.float64)
+        pi_d = pi_t.to(dev).contiguous()
+        # the discount tables, one row per learner: each as eval_td builds it, the shorter ones (stationary) padded with their last entry
+        rows = [_gamma_pow(g, n_gamma_pow, dev, cap=t.N + 2) for g in np.broadcast_to(per["gamma"], (n_l,)).tolist()]
+        n_gp = max(r.numel() for r in rows)
+        gp = torch.stack([r if r.numel() == n_gp else torch.cat([r, r[-1:].expand(n_gp - r.numel())]) for r in rows]).contiguous()
+        if n_episodes is None:
+            n_episodes = 1 << 62
+        if q_t is None:
+            q = torch.zeros((R, t.n_slots, t.nA), dtype=torch.float64, device=dev)
+        else:
+            q_t = q_t.to(dev)
+            q = (q_t if q_t.dim() == 4 else q_t.reshape(-1, 1, t.n_slots, t.nA)).expand(n_l, S, t.n_slots, t.nA).reshape(R, t.n_slots, t.nA).contiguous().clone()
+        st = self.state
+        rng, cursor = st.rng.repeat(n_l, 1), st.cursor.repeat(n_l, 1)
+        init_cursor, cur_slot = st.init_cursor.repeat(n_l), st.cur_slot.repeat(n_l)
+        ro = L.Rollouts(R=R, rng=L.ptr(rng), cursor=L.ptr(cursor), init_cursor=L.ptr(init_cursor), cur_slot=L.ptr(cur_slot), perm=L.ptr(st.perm),
+                        perm_stride=st.perm_stride, init_perm=L.ptr(st.init_perm), init_stride=st.init_stride, rng_kind=st.rng_kind)
+        o = {k: torch.empty(R, dtype=dt, device=dev) for k, dt in (("sum_g", torch.float64), ("n_ep", torch.int64), ("steps", torch.int64),
+                                                                   ("cand", torch.int64), ("n_len", torch.int64), ("status", torch.int32))}
+        if ep_cap:
+            o["ep_g"] = torch.zeros((R, ep_cap), dtype=torch.float64, device=dev)
+            o["ep_len"] = torch.zeros((R, ep_cap + 1), dtype=torch.int32, device=dev)
+        if trace_cap:
+            o["trace_row"] = torch.full((R, trace_cap), -1, dtype=torch.int32, device=dev)
+            o["trace_pop"] = torch.zeros((R, trace_cap), dtype=torch.int32, device=dev)
+            o["td_err"] = torch.zeros((R, trace_cap), dtype=torch.float64, device=dev)
+            if (beh_host == L.BEHAVIOUR_EPS_GREEDY).any():
+                o["beh_arg"] = torch.zeros((R, trace_cap), dtype=torch.int32, device=dev)
+        if snap_cap:
+            o["q_snap"] = torch.zeros((R, snap_cap, t.n_slots, t.nA), dtype=torch.float64, device=dev)
+        if mt is not None:
+            mt = mt.to(device=dev, dtype=torch.int32).reshape(R, 625).contiguous().clone()
+            o["tie_mt"] = mt
+        oc = L.EvalMCOut(sum_g=L.ptr(o["sum_g"]), n_ep=L.ptr(o["n_ep"]), steps=L.ptr(o["steps"]), cand=L.ptr(o["cand"]),
+                         n_len=L.ptr(o["n_len"]), status=L.ptr(o["status"]), ep_g=L.ptr(o.get("ep_g")), ep_len=L.ptr(o.get("ep_len")),
+                         ep_cap=ep_cap, trace_row=L.ptr(o.get("trace_row")), trace_pop=L.ptr(o.get("trace_pop")), trace_cap=trace_cap)
+        pc = L.TDPop(mode=int(mode), alpha=L.ptr(alpha_d), epsilon=L.ptr(eps_d), gamma=L.ptr(gamma_d), gamma_pow=L.ptr(gp), n_gamma_pow=n_gp,
+                     behaviour=L.ptr(beh_d), behaviour_host=beh_host.ctypes.data_as(C.POINTER(C.c_int32)), alpha_ep=L.ptr(a_ep), epsilon_ep=L.ptr(e_ep),
+                     n_sched=n_sched, pi=L.ptr(pi_d), pi_stride=t.n_slots * t.nA if pi_d.dim() == 3 else 0, q=L.ptr(q), td_err=L.ptr(o.get("td_err")),
+                     td_cap=trace_cap, q_snap=L.ptr(o.get("q_snap")), snap_cap=snap_cap, snap_stride=max(int(snap_stride), 1), tie_mt=L.ptr(mt),
+                     beh_arg=L.ptr(o.get("beh_arg")))
+        L.check(L.load().offsim_eval_td_pop(C.byref(t.c), C.byref(ro), n_l, S, C.byref(pc), self.reject_mode, int(n_episodes), C.byref(oc),
+                                            L.stream_ptr()))
+        o["q"] = q
+        o = {k: v.reshape(n_l, S, *v.shape[1:]) for k, v in o.items()}
+        o["_keepalive"] = (pi_d, gp, alpha_d, eps_d, gamma_d, beh_d, a_ep, e_ep, rng, cursor, init_cursor, cur_slot)
+        o["_state"] = dict(rng=rng.reshape(n_l, S, 4), cursor=cursor.reshape(n_l, S, t.n_slots), init_cursor=init_cursor.reshape(n_l, S),
+                           cur_slot=cur_slot.reshape(n_l, S))  # where every learner's copy of the sampler stands afterwards
+        o["_kernel"] = "k_eval_td_pop"
+        return o
+
     def scan_variant(self):
         """Name of the kernel eval_mc's fast path launches for this table and batch size (measurement label)."""
         if self._streams is not None:

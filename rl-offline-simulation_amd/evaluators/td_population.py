@@ -1,0 +1,211 @@
+"""A population of tabular TD learners inside the simulator: a grid of step sizes, exploration rates and discounts per launch.
+
+qlearn_psrs / expSARSA_psrs (offsim4rl/evaluators/psrs.py:119-239) run one hyper-parameter setting on one sampler seed per call.  What
+they are used for is the comparison of learning curves -- every setting over many seeds -- so the learner is a grid dimension of the
+learner kernel here: BatchedPSRS.eval_td_population runs L learners on each of S seeds in one launch (offsim_eval_td_pop), all learners of
+a seed on the same queue orders and the same rejection draws (paired comparisons), and offsim_td_curves reduces the returns to one curve
+per learner on the device.  Learners never interact: learner l on seed j is, bit for bit, what eval_td gives that setting on that seed.
+
+  TDPopulation(mode, alpha, gamma, epsilon, behaviour, pi, Q_init)   the settings, each a scalar or one value per learner
+  TDPopulation.grid(mode, alpha=[..], epsilon=[..], gamma=[..])      their Cartesian product
+  population.run(table, seeds, ...)                                  -> TDPopulationResult of device tensors
+"""
+import itertools
+from dataclasses import dataclass, field
+from typing import Optional
+
+import numpy as np
+import torch
+
+from .. import _lib as L
+from .batched import SHUFFLE_PER_ROLLOUT, BatchedPSRS, resident_rollouts
+from .psrs import _schedule
+
+_MODE = {"qlearn": L.TD_QLEARN, "expsarsa": L.TD_EXPSARSA, L.TD_QLEARN: L.TD_QLEARN, L.TD_EXPSARSA: L.TD_EXPSARSA}
+_BEHAVIOUR = {"fixed": L.BEHAVIOUR_FIXED, "eps_greedy": L.BEHAVIOUR_EPS_GREEDY, "greedy": L.BEHAVIOUR_EPS_GREEDY, "soft_greedy": L.BEHAVIOUR_SOFT_GREEDY}
+
+
+def _is_seq(x):
+    return isinstance(x, (list, tuple, np.ndarray)) or (isinstance(x, torch.Tensor) and x.dim() > 0)
+
+
+def _per_learner(x):
+    """a scalar, a callable or a string -> [x]; a sequence -> its list"""
+    return list(x) if _is_seq(x) else [x]
+
+
+@dataclass
+class TDPopulationResult:
+    """What TDPopulation.run returns; every array is a tensor on the table's device.
+    Q [L,S,nS,nA] by caller state id; Gs [L,S,ep_cap] the returns in episode order (entry n_ep of a row: the episode the end of the log
+    cut short, as qlearn_psrs appends it); n_ep, steps, status [L,S]; curve_n / curve_mean / curve_var [L,ep_cap]: per learner and
+    episode, over the seeds that completed that episode, their number, the mean return and its population variance (NaN where no seed
+    did); td_err [L,S,trace_cap] when the run was asked for the trace."""
+    Q: torch.Tensor
+    Gs: torch.Tensor
+    n_ep: torch.Tensor
+    steps: torch.Tensor
+    status: torch.Tensor
+    curve_mean: torch.Tensor
+    curve_var: torch.Tensor
+    curve_n: torch.Tensor
+    learners: list = field(default_factory=list)
+    td_err: Optional[torch.Tensor] = None
+
+    def best(self, last=1):
+        """The learner with the highest mean of its last `last` curve points that every seed reached (curve_n == S); points fewer
+        seeds completed are ignored, a learner without such a point is never the best; -1 when no learner has one."""
+        S = int(self.Gs.shape[1])
+        n, mean = self.curve_n.cpu().numpy(), self.curve_mean.cpu().numpy()
+        score = np.full(n.shape[0], -np.inf)
+        for l in range(n.shape[0]):
+            full = np.nonzero(n[l] == S)[0][-max(int(last), 1):]
+            if len(full):
+                score[l] = float(np.mean(mean[l, full]))
+        return -1 if not np.isfinite(score).any() else int(np.argmax(score))
+
+
+class TDPopulation:
+    """L tabular TD learners.  mode: "qlearn" or "expsarsa" (one for the population).  alpha, gamma, epsilon, behaviour: a scalar or one
+    value per learner; alpha and epsilon may be callables of the episode (psrs.py:128-135), tabulated per run as the single-learner
+    drivers do.  behaviour: "fixed" (the tabular pi, e.g. uniformly random), "eps_greedy", "greedy" (epsilon 0) or "soft_greedy" on the
+    learner's own Q (offsim4rl/agents/tabular.py:7-32).  pi [nS,nA] or [L,nS,nA] by caller state id: the behaviour policy when fixed and
+    the target of expected SARSA (None: uniform).  Q_init [nS,nA] or [L,nS,nA] (None: zeros).  L is the common length of the per-learner
+    arguments; lengths that disagree raise ValueError."""
+
+    def __init__(self, mode, alpha, gamma, epsilon=1.0, behaviour="fixed", pi=None, Q_init=None):
+        if mode not in _MODE:
+            raise ValueError(f"TDPopulation: mode must be 'qlearn' or 'expsarsa', got {mode!r}")
+        self.mode = _MODE[mode]
+        given = {"alpha": alpha, "gamma": gamma, "epsilon": epsilon, "behaviour": behaviour}
+        per = {k: _per_learner(x) for k, x in given.items()}
+        self.pi = None if pi is None else np.asarray(pi, dtype=np.float64)
+        self.Q_init = None if Q_init is None else np.asarray(Q_init, dtype=np.float64)
+        lens = {k: len(per[k]) for k, x in given.items() if _is_seq(x)}
+        for k, x in (("pi", self.pi), ("Q_init", self.Q_init)):
+            if x is not None:
+                if x.ndim not in (2, 3):
+                    raise ValueError(f"TDPopulation: {k} must be [nS,nA] or [L,nS,nA], got {x.shape}")
+                if x.ndim == 3:
+                    lens[k] = x.shape[0]
+        if len(set(lens.values())) > 1:
+            raise ValueError(f"TDPopulation: per-learner arguments of different lengths: {lens}")
+        self.L = next(iter(lens.values())) if lens else 1
+        if self.L < 1:
+            raise ValueError("TDPopulation: no learner")
+        self.alpha, self.gamma, self.epsilon, self.behaviour = (v * self.L if len(v) == 1 else v for v in (per[k] for k in ("alpha", "gamma", "epsilon", "behaviour")))
+        for b in self.behaviour:
+            if b not in _BEHAVIOUR or not isinstance(b, str):
+                raise ValueError(f"TDPopulation: behaviour must be one of {sorted(k for k in _BEHAVIOUR if isinstance(k, str))}, got {b!r}")
+        self.gamma = [float(g) for g in self.gamma]
+
+    @classmethod
+    def grid(cls, mode, alpha, epsilon=(1.0,), gamma=(0.99,), behaviour="fixed", pi=None, Q_init=None):
+        """The Cartesian product of the listed values, alpha slowest and gamma fastest: learner i is (alpha, epsilon, gamma) =
+        list(itertools.product(alpha, epsilon, gamma))[i]; behaviour, pi and Q_init are shared."""
+        alpha, epsilon, gamma = (list(x) if _is_seq(x) else [x] for x in (alpha, epsilon, gamma))
+        cells = list(itertools.product(alpha, epsilon, gamma))
+        if not cells:
+            raise ValueError("TDPopulation.grid: an empty axis")
+        return cls(mode, [c[0] for c in cells], [c[2] for c in cells], [c[1] for c in cells], behaviour, pi, Q_init)
+
+    def __len__(self):
+        return self.L
+
+    @property
+    def learners(self):
+        """The settings, one dict per learner."""
+        return [dict(alpha=self.alpha[l], epsilon=self.epsilon[l], gamma=self.gamma[l], behaviour=self.behaviour[l]) for l in range(self.L)]
+
+    def tabulate(self, n_ep):
+        """The per-learner constants and schedules of a run of at most n_ep episodes: (alpha [L], epsilon [L], alpha_ep, epsilon_ep), the
+        last two [L, max(n_ep, 1)] or None when no learner has a callable.  A callable is evaluated per episode (_schedule of psrs.py)
+        and its constant is 0; a learner with a constant gets a constant row; "greedy" is epsilon 0 whatever epsilon says (_td_run)."""
+        eps = [0.0 if b == "greedy" else e for e, b in zip(self.epsilon, self.behaviour)]
+        a_const = np.array([0.0 if callable(a) else float(a) for a in self.alpha])
+        e_const = np.array([0.0 if callable(e) else float(e) for e in eps])
+        if not any(callable(x) for x in list(self.alpha) + eps):
+            return a_const, e_const, None, None
+        n = max(int(n_ep), 1)
+        a_tab = np.stack([_schedule(a, n) if callable(a) else np.full(n, float(a)) for a in self.alpha])
+        e_tab = np.stack([_schedule(e, n) if callable(e) else np.full(n, float(e)) for e in eps])
+        return a_const, e_const, a_tab, e_tab
+
+    def _n_rows(self, table):
+        for x in (self.Q_init, self.pi):
+            if x is not None:
+                return int(x.shape[-2])
+        return max(int(table.slot_z.max()) + 1 if table.N else 1, 1)
+
+    def _slots(self, table, x, nan=None):
+        """[nS,nA] or [L,nS,nA] by caller state id -> the same in slot order (TransitionTable.policy_slots per learner)"""
+        out = table.policy_slots(x) if x.ndim == 2 else np.stack([table.policy_slots(v) for v in x])
+        return out if nan is None else np.nan_to_num(out, nan=nan)
+
+    def run(self, table, seeds, n_episodes=None, shuffle=SHUFFLE_PER_ROLLOUT, tile=None, tie_mt=None, rejection="pcg64", shuffle_seed=None,
+            trace_cap=0, reject_mode=L.REJECT_DEFAULT):
+        """Every learner on every seed.  One reset_sampler per tile of `tile` seeds (default: resident_rollouts(keyed=False), as
+        evalmc_rollouts_population -- the queue orders are the seeds', shared by all learners, so the tile does not shrink with L), one
+        launch per tile, then offsim_td_curves over all seeds.  n_episodes: at most that many episodes per learner and seed (None: until
+        the log ends).  tie_mt [L,S,625]: NumPy MT19937 states for ties between maximal Q values (None: the first maximum).
+        trace_cap > 0 also returns the TD errors of the first trace_cap steps."""
+        seeds = np.asarray(seeds, dtype=np.uint64)
+        S, n_l, dev = len(seeds), self.L, table.device
+        if S < 1:
+            raise ValueError("TDPopulation.run: no seed")
+        n_ep = int(min(n_episodes if n_episodes is not None else table.N0 + 1, table.N0 + 1))
+        ep_cap = max(n_ep, 1)
+        a_const, e_const, a_tab, e_tab = self.tabulate(n_ep)
+        nS = self._n_rows(table)
+        Q0 = np.zeros((nS, table.nA)) if self.Q_init is None else self.Q_init
+        pi = np.full((nS, table.nA), 1.0 / table.nA) if self.pi is None else self.pi
+        if table.N and pi.shape[-2] <= int(table.slot_z.max()):
+            raise IndexError("pi has no row for some latent state")
+        pi_slots, q_slots = self._slots(table, pi), self._slots(table, Q0, nan=0.0)
+        beh = np.array([_BEHAVIOUR[b] for b in self.behaviour], dtype=np.int32)
+        if tie_mt is not None:
+            tie_mt = torch.as_tensor(np.ascontiguousarray(tie_mt).view(np.int32) if not isinstance(tie_mt, torch.Tensor) else tie_mt)
+            if tuple(tie_mt.shape) != (n_l, S, 625):
+                raise ValueError(f"TDPopulation.run: tie_mt [L,S,625] = {(n_l, S, 625)} expected, got {tuple(tie_mt.shape)}")
+        if tile is None:
+            tile = S if shuffle != SHUFFLE_PER_ROLLOUT else int(max(1, min(S, resident_rollouts(table, keyed=False)[0])))
+        keys = ["q", "ep_g", "n_ep", "steps", "status"] + (["td_err"] if trace_cap else [])
+        parts = {k: [] for k in keys}
+        env = None
+        for b in range(0, S, int(tile)):
+            sd = seeds[b:b + int(tile)]
+            if env is None or env.R != len(sd):
+                env = BatchedPSRS(table, len(sd), reject_mode)
+            env.reset_sampler(sd, shuffle, shuffle_seed, rejection=rejection)
+            o = env.eval_td_population(self.mode, a_const, self.gamma, beh, e_const, pi_slots=pi_slots, q_slots=q_slots, alpha_ep=a_tab,
+                                       epsilon_ep=e_tab, tie_mt=None if tie_mt is None else tie_mt[:, b:b + len(sd)], n_episodes=n_ep, ep_cap=ep_cap,
+                                       trace_cap=int(trace_cap))
+            for k in keys:
+                parts[k].append(o[k])
+            env.check_faults()
+        res = {k: v[0] if len(v) == 1 else torch.cat(v, dim=1).contiguous() for k, v in parts.items()}
+        curve_n = torch.empty((n_l, ep_cap), dtype=torch.int64, device=dev)
+        curve_mean, curve_var = (torch.empty((n_l, ep_cap), dtype=torch.float64, device=dev) for _ in range(2))
+        L.check(L.load().offsim_td_curves(L.ptr(res["ep_g"]), L.ptr(res["n_ep"]), n_l, S, ep_cap, L.ptr(curve_n), L.ptr(curve_mean), L.ptr(curve_var),
+                                          L.stream_ptr()))
+        return TDPopulationResult(Q=self._q_by_state(table, res["q"], Q0), Gs=res["ep_g"], n_ep=res["n_ep"], steps=res["steps"], status=res["status"],
+                                  curve_mean=curve_mean, curve_var=curve_var, curve_n=curve_n, learners=self.learners, td_err=res.get("td_err"))
+
+    @staticmethod
+    def _q_by_state(table, q_slots, Q0):
+        """q_slots [L,S,n_slots,nA] back into copies of Q0 [nS,nA] or [L,nS,nA] on the device, by the rule of psrs._slots_to_q: slot s goes
+        to row slot_z[s] with NumPy's negative-index wrap, the later slot winning a shared row; rows without a slot keep Q0's values."""
+        n_l, S = q_slots.shape[:2]
+        nS = Q0.shape[-2]
+        q0 = torch.from_numpy(np.ascontiguousarray(Q0, dtype=np.float64)).to(q_slots.device)
+        out = (q0[:, None] if q0.dim() == 3 else q0[None, None]).expand(n_l, S, nS, q_slots.shape[-1]).contiguous().clone()
+        last = {}
+        for s in range(table.n_slots):
+            z = table.z_of(s)
+            if -nS <= z < nS:
+                last[z % nS] = s
+        if last:
+            rows = torch.tensor(list(last.keys()), dtype=torch.int64, device=q_slots.device)
+            slots = torch.tensor(list(last.values()), dtype=torch.int64, device=q_slots.device)
+            out[:, :, rows] = q_slots[:, :, slots]
+        return out
