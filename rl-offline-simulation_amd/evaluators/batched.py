@@ -4,6 +4,7 @@
                     119-271 for every rollout), candidate streams and their layouts, the resident step server
   evalmc_rollouts   the batched driver behind the headline metric (thousands of seeds per launch, tiled to the free HBM)
   resident_rollouts / rollout_resident_bytes   the one tile-size rule (shared with bench.py)
+The output dicts, state copies and the seed-tile loop that the launches and drivers share are in rollout_io.py.
 
 Every decision (queue order, accept / reject, state walk, discounted return) is computed on the GPU through the C ABI of
 include/offsim.h; the host only moves arguments and payload.  No CPU fallback.  The reference's single-environment class and its
@@ -19,40 +20,12 @@ import torch
 
 from .. import _lib as L
 from ..table import RolloutState, TransitionTable, seed_streams, seeds_tensor, shuffle_queues
+from .rollout_io import (HOST_KEYS, _gamma_pow, _prob_mode, collect_host, episode_bound, host_result, population_result,  # noqa: F401
+                         population_state, rollout_outputs, seed_tiles, td_outputs, tie_stream)
 
 SHUFFLE_PER_ROLLOUT = "per_rollout"  # reset_sampler(seed_r) for every rollout r: the reference's meaning
 SHUFFLE_SHARED = "shared"            # one queue order (shuffle_seed) shared by all rollouts, per-rollout rejection streams
 SHUFFLE_NONE = "table_order"         # queues in buffer order (no shuffle); per-rollout rejection streams
-
-
-_GP_CACHE = {}
-_GP_CACHE_BYTES = 256 << 20
-
-
-def _gamma_pow(gamma, n, device, cap=None):
-    """gamma**t exactly as the host computes it for the reference (Python float ** int == libm pow, psrs.py:262), for every
-    t an episode can reach: at least `n` entries, then on until the factor is stationary (0, inf or 1: the device clamps t to
-    the last entry in that case, csrc/discount.hpp) or `cap` entries (an episode has at most N steps) are there.  Built in
-    blocks of 65536 with Python's own `float ** int` (NumPy's array pow is vectorised differently and differs in the last bit for
-    some t), so a gamma below 1 stops after the block its factor underflows in; the cache is bounded by bytes (_GP_CACHE_BYTES)."""
-    g = float(gamma)
-    cap = max(int(n), 2) if cap is None else max(int(cap), int(n), 2)
-    key = (g, int(n), cap, str(device))
-    if key not in _GP_CACHE:
-        stationary = lambda v: len(v) >= 2 and v[-1] == v[-2] and (v[-1] in (0.0, 1.0) or np.isinf(v[-1]))
-        blocks, total = [], 0
-        while total < max(int(n), 2) or (total < cap and not stationary(blocks[-1])):
-            m = min(65536, (max(int(n), 2) if total < max(int(n), 2) else cap) - total)
-            blocks.append(np.array([g ** t for t in range(total, total + m)], dtype=np.float64))  # (Python's own pow: NumPy's array pow is not bit-identical)
-            total += m
-        vals = np.concatenate(blocks)
-        keep = len(vals)
-        while keep > max(int(n), 2) and vals[keep - 1] == vals[keep - 2] == vals[keep - 3] and (vals[keep - 1] in (0.0, 1.0) or np.isinf(vals[keep - 1])):
-            keep -= 1  # (extended in blocks: keep exactly two stationary entries)
-        if sum(v.numel() * 8 for v in _GP_CACHE.values()) + keep * 8 > _GP_CACHE_BYTES:
-            _GP_CACHE.clear()
-        _GP_CACHE[key] = torch.from_numpy(vals[:keep].copy()).to(device)
-    return _GP_CACHE[key]
 
 
 def stream_format(table):
@@ -71,12 +44,9 @@ def stream_format(table):
 
 ROWS_TICK_STEPS = 16  # steps between two top-up rounds of the row-packed scan (csrc/scan_rows.hpp: ROWS_TICK)
 ROWS_MAX_WINDOW_LOAD = 1.2  # candidates a tick takes out of the busiest 8-entry window, above which the window kernel is the faster scan
+WS_BUDGET_FRAC = 0.92  # share of the free HBM the chunked shuffle's workspace may take ...
+WS_KEEP_FREE = 2 << 30  # ... and the bytes it always leaves: what the rest of the job (policy keys, rebuilt permutations, outputs) allocates later
 ROWS_MAX_ALL_REJECTED = 0.03  # probability that a full 8-entry window holds no accept, from which the 32-entry window kernel (<= 64 states) is the faster scan
-
-
-def _prob_mode(table, p_dtype):
-    f32 = (p_dtype in (np.float32, torch.float32, np.dtype(np.float32))) and table.p_log.dtype == torch.float32
-    return L.PROB_F32 if f32 else L.PROB_F64
 
 
 class BatchedPSRS:
@@ -86,6 +56,8 @@ class BatchedPSRS:
     inter-wavefront waits and raise a device-wide fault word instead of hanging (include/offsim.h: offsim_async_faults): whoever
     drives this class directly calls `check_faults()` once the results have been copied back (the host-facing drivers of this
     module -- PSRS, evalMC_psrs, qlearn_psrs, expSARSA_psrs, evalmc_rollouts, VectorPSRS(strict=True) -- do)."""
+
+    ws_budget_frac, ws_keep_free = WS_BUDGET_FRAC, WS_KEEP_FREE  # budget of _shuffle_workspace; an instance may set its own
 
     def __init__(self, table: TransitionTable, R: int, reject_mode=L.REJECT_DEFAULT):
         self.table, self.R = table, int(R)
@@ -203,7 +175,7 @@ class BatchedPSRS:
             self._ws = None  # (released first: what it held counts as free)
             torch.cuda.empty_cache()
             free = torch.cuda.mem_get_info(t.device)[0]
-            budget = min(int(free * getattr(self, "ws_budget_frac", 0.92)), free - int(getattr(self, "ws_keep_free", 2 << 30)))
+            budget = min(int(free * self.ws_budget_frac), free - int(self.ws_keep_free))
             n = min(want, max(0, (budget - head) // max(one - head, 1)))
             if n < 1 and have_bytes:  # nothing bigger fits: what there was is put back
                 n = max(0, (have_bytes - head) // max(one - head, 1))
@@ -579,26 +551,9 @@ class BatchedPSRS:
             pi_slots = torch.from_numpy(np.ascontiguousarray(pi_slots))
         mode = _prob_mode(t, pi_slots.dtype)
         pi_d = pi_slots.to(device=dev, dtype=torch.float32 if mode == L.PROB_F32 else torch.float64).reshape(t.n_slots, t.nA).contiguous()
-        if n_episodes is None:
-            n_episodes = 1 << 62
-        o = out or {}
-        for k, dt in (("sum_g", torch.float64), ("n_ep", torch.int64), ("steps", torch.int64), ("cand", torch.int64),
-                      ("n_len", torch.int64), ("status", torch.int32)):
-            if k not in o:
-                o[k] = torch.empty(R, dtype=dt, device=dev)
-        if ep_cap:
-            o["ep_g"] = torch.zeros((R, ep_cap), dtype=torch.float64, device=dev)
-            o["ep_len"] = torch.zeros((R, ep_cap + 1), dtype=torch.int32, device=dev)
-        if trace_cap:
-            o["trace_row"] = torch.full((R, trace_cap), -1, dtype=torch.int32, device=dev)
-            o["trace_pop"] = torch.zeros((R, trace_cap), dtype=torch.int32, device=dev)
-        if dbg:
-            o["dbg"] = torch.zeros((R, 4), dtype=torch.int64, device=dev)
+        n_episodes = episode_bound(n_episodes)
+        o, oc = rollout_outputs(R, dev, ep_cap, trace_cap, out=out, dbg=dbg)
         gp = _gamma_pow(gamma, n_gamma_pow, dev, cap=t.N + 2)
-        oc = L.EvalMCOut(dbg=L.ptr(o.get("dbg")), sum_g=L.ptr(o["sum_g"]), n_ep=L.ptr(o["n_ep"]), steps=L.ptr(o["steps"]), cand=L.ptr(o["cand"]),
-                         n_len=L.ptr(o["n_len"]), status=L.ptr(o["status"]), ep_g=L.ptr(o.get("ep_g")),
-                         ep_len=L.ptr(o.get("ep_len")), ep_cap=ep_cap, trace_row=L.ptr(o.get("trace_row")),
-                         trace_pop=L.ptr(o.get("trace_pop")), trace_cap=trace_cap)
         can_fast = mode == L.PROB_F64 and self.reject_mode == L.REJECT_DEFAULT and t.n_slots <= 256  # (either stream provider)
         if fast is None:
             fast = can_fast
@@ -645,21 +600,10 @@ class BatchedPSRS:
         dt = torch.float32 if mode == L.PROB_F32 else torch.float64
         pn = p_next.to(device=dev, dtype=dt).reshape(t.N, t.nA).contiguous()
         p0 = p_init.to(device=dev, dtype=dt).reshape(t.N0, t.nA).contiguous()
-        if n_episodes is None:
-            n_episodes = 1 << 62
-        o = {k: torch.empty(R, dtype=dt_, device=dev) for k, dt_ in (("sum_g", torch.float64), ("n_ep", torch.int64), ("steps", torch.int64),
-                                                                    ("cand", torch.int64), ("n_len", torch.int64), ("status", torch.int32))}
+        n_episodes = episode_bound(n_episodes)
+        o, oc = rollout_outputs(R, dev, ep_cap, trace_cap)
         o["obs_row"] = torch.full((R,), -(1 << 31), dtype=torch.int32, device=dev)
-        if ep_cap:
-            o["ep_g"] = torch.zeros((R, ep_cap), dtype=torch.float64, device=dev)
-            o["ep_len"] = torch.zeros((R, ep_cap + 1), dtype=torch.int32, device=dev)
-        if trace_cap:
-            o["trace_row"] = torch.full((R, trace_cap), -1, dtype=torch.int32, device=dev)
-            o["trace_pop"] = torch.zeros((R, trace_cap), dtype=torch.int32, device=dev)
         gp = _gamma_pow(gamma, n_gamma_pow, dev, cap=t.N + 2)
-        oc = L.EvalMCOut(sum_g=L.ptr(o["sum_g"]), n_ep=L.ptr(o["n_ep"]), steps=L.ptr(o["steps"]), cand=L.ptr(o["cand"]),
-                         n_len=L.ptr(o["n_len"]), status=L.ptr(o["status"]), ep_g=L.ptr(o.get("ep_g")), ep_len=L.ptr(o.get("ep_len")),
-                         ep_cap=ep_cap, trace_row=L.ptr(o.get("trace_row")), trace_pop=L.ptr(o.get("trace_pop")), trace_cap=trace_cap)
         L.check(L.load().offsim_eval_mc_rows_policy(C.byref(t.c), C.byref(self.state.c), L.ptr(pn) if t.N else None, L.ptr(p0) if t.N0 else None,
                                                     mode, self.reject_mode, float(gamma), L.ptr(gp), gp.numel(), int(n_episodes), C.byref(oc),
                                                     L.ptr(o["obs_row"]), L.stream_ptr()))
@@ -686,33 +630,15 @@ class BatchedPSRS:
         dt = torch.float32 if mode == L.PROB_F32 else torch.float64
         pn = p_next.to(device=dev, dtype=dt).reshape(n_pol, t.N, t.nA).contiguous()
         p0 = p_init.to(device=dev, dtype=dt).reshape(n_pol, t.N0, t.nA).contiguous()
-        if n_episodes is None:
-            n_episodes = 1 << 62
-        st = self.state
-        rng, cursor = st.rng.repeat(n_pol, 1), st.cursor.repeat(n_pol, 1)
-        init_cursor, cur_slot = st.init_cursor.repeat(n_pol), st.cur_slot.repeat(n_pol)
-        ro = L.Rollouts(R=R, rng=L.ptr(rng), cursor=L.ptr(cursor), init_cursor=L.ptr(init_cursor), cur_slot=L.ptr(cur_slot), perm=L.ptr(st.perm),
-                        perm_stride=st.perm_stride, init_perm=L.ptr(st.init_perm), init_stride=st.init_stride, rng_kind=st.rng_kind)
-        o = {k: torch.empty(R, dtype=dt_, device=dev) for k, dt_ in (("sum_g", torch.float64), ("n_ep", torch.int64), ("steps", torch.int64),
-                                                                    ("cand", torch.int64), ("n_len", torch.int64), ("status", torch.int32))}
+        n_episodes = episode_bound(n_episodes)
+        ro, copies = population_state(self.state, n_pol)
+        o, oc = rollout_outputs(R, dev, ep_cap, trace_cap)
         o["obs_row"] = torch.full((R,), -(1 << 31), dtype=torch.int32, device=dev)
-        if ep_cap:
-            o["ep_g"] = torch.zeros((R, ep_cap), dtype=torch.float64, device=dev)
-            o["ep_len"] = torch.zeros((R, ep_cap + 1), dtype=torch.int32, device=dev)
-        if trace_cap:
-            o["trace_row"] = torch.full((R, trace_cap), -1, dtype=torch.int32, device=dev)
-            o["trace_pop"] = torch.zeros((R, trace_cap), dtype=torch.int32, device=dev)
         gp = _gamma_pow(gamma, n_gamma_pow, dev, cap=t.N + 2)
-        oc = L.EvalMCOut(sum_g=L.ptr(o["sum_g"]), n_ep=L.ptr(o["n_ep"]), steps=L.ptr(o["steps"]), cand=L.ptr(o["cand"]),
-                         n_len=L.ptr(o["n_len"]), status=L.ptr(o["status"]), ep_g=L.ptr(o.get("ep_g")), ep_len=L.ptr(o.get("ep_len")),
-                         ep_cap=ep_cap, trace_row=L.ptr(o.get("trace_row")), trace_pop=L.ptr(o.get("trace_pop")), trace_cap=trace_cap)
         L.check(L.load().offsim_eval_mc_rows_policy_pop(C.byref(t.c), C.byref(ro), L.ptr(pn) if t.N else None, L.ptr(p0) if t.N0 else None, n_pol, S,
                                                         mode, self.reject_mode, float(gamma), L.ptr(gp), gp.numel(), int(n_episodes), C.byref(oc),
                                                         L.ptr(o["obs_row"]), L.stream_ptr()))
-        o = {k: v.reshape(n_pol, S, *v.shape[1:]) for k, v in o.items()}
-        o["_keepalive"] = (pn, p0, gp, rng, cursor, init_cursor, cur_slot)
-        o["_kernel"] = "k_eval_mc_rows_policy_pop"
-        return o
+        return population_result(o, n_pol, S, copies, (pn, p0, gp), "k_eval_mc_rows_policy_pop")
 
     # -- qlearn_psrs / expSARSA_psrs (psrs.py:119-239) with a Q-independent behaviour policy, all rollouts in one launch --
     def eval_td(self, pi_slots, gamma, mode, alpha, q_slots=None, n_episodes=None, ep_cap=0, trace_cap=0, n_gamma_pow=4096,
@@ -727,36 +653,19 @@ class BatchedPSRS:
         self._orders_for_generic()
         t, dev, R = self.table, self.table.device, self.R
         pi_d = torch.as_tensor(np.ascontiguousarray(pi_slots), dtype=torch.float64).to(dev).reshape(t.n_slots, t.nA).contiguous()
-        if n_episodes is None:
-            n_episodes = 1 << 62
+        n_episodes = episode_bound(n_episodes)
         q = torch.zeros((R, t.n_slots, t.nA), dtype=torch.float64, device=dev) if q_slots is None else \
             torch.as_tensor(q_slots, dtype=torch.float64).to(dev).reshape(R, t.n_slots, t.nA).contiguous().clone()
-        o = {k: torch.empty(R, dtype=dt, device=dev) for k, dt in (("sum_g", torch.float64), ("n_ep", torch.int64), ("steps", torch.int64),
-                                                                   ("cand", torch.int64), ("n_len", torch.int64), ("status", torch.int32))}
-        if ep_cap:
-            o["ep_g"] = torch.zeros((R, ep_cap), dtype=torch.float64, device=dev)
-            o["ep_len"] = torch.zeros((R, ep_cap + 1), dtype=torch.int32, device=dev)
-        if trace_cap:
-            o["trace_row"] = torch.full((R, trace_cap), -1, dtype=torch.int32, device=dev)
-            o["trace_pop"] = torch.zeros((R, trace_cap), dtype=torch.int32, device=dev)
-            o["td_err"] = torch.zeros((R, trace_cap), dtype=torch.float64, device=dev)
-            if behaviour == L.BEHAVIOUR_EPS_GREEDY:
-                o["beh_arg"] = torch.zeros((R, trace_cap), dtype=torch.int32, device=dev)
+        o, oc = rollout_outputs(R, dev, ep_cap, trace_cap)
+        td_outputs(o, q, trace_cap, snap_cap, beh_arg=behaviour == L.BEHAVIOUR_EPS_GREEDY)
         a_ep = None if alpha_ep is None else torch.as_tensor(np.ascontiguousarray(alpha_ep, dtype=np.float64)).to(dev)
         e_ep = None if epsilon_ep is None else torch.as_tensor(np.ascontiguousarray(epsilon_ep, dtype=np.float64)).to(dev)
         n_sched = max(a_ep.numel() if a_ep is not None else 0, e_ep.numel() if e_ep is not None else 0)
         assert all(x is None or x.numel() == n_sched for x in (a_ep, e_ep)), "alpha_ep and epsilon_ep cover the same episodes"
-        if snap_cap:
-            o["q_snap"] = torch.zeros((R, snap_cap, t.n_slots, t.nA), dtype=torch.float64, device=dev)
         mt = None
         if tie_mt is not None:
-            mt = torch.as_tensor(np.ascontiguousarray(tie_mt).view(np.int32) if not isinstance(tie_mt, torch.Tensor) else tie_mt)
-            mt = mt.to(device=dev, dtype=torch.int32).reshape(R, 625).contiguous()
-            o["tie_mt"] = mt
+            mt = o["tie_mt"] = tie_stream(tie_mt, dev).reshape(R, 625).contiguous()
         gp = _gamma_pow(gamma, n_gamma_pow, dev, cap=t.N + 2)
-        oc = L.EvalMCOut(sum_g=L.ptr(o["sum_g"]), n_ep=L.ptr(o["n_ep"]), steps=L.ptr(o["steps"]), cand=L.ptr(o["cand"]),
-                         n_len=L.ptr(o["n_len"]), status=L.ptr(o["status"]), ep_g=L.ptr(o.get("ep_g")), ep_len=L.ptr(o.get("ep_len")),
-                         ep_cap=ep_cap, trace_row=L.ptr(o.get("trace_row")), trace_pop=L.ptr(o.get("trace_pop")), trace_cap=trace_cap)
         tdc = L.TD(mode=mode, alpha=float(alpha), q=L.ptr(q), td_err=L.ptr(o.get("td_err")), td_cap=trace_cap, behaviour=int(behaviour),
                    epsilon=float(epsilon), alpha_ep=L.ptr(a_ep), epsilon_ep=L.ptr(e_ep), n_sched=n_sched, q_snap=L.ptr(o.get("q_snap")),
                    snap_cap=snap_cap, snap_stride=max(int(snap_stride), 1), tie_mt=L.ptr(mt), beh_arg=L.ptr(o.get("beh_arg")))
@@ -809,7 +718,7 @@ class BatchedPSRS:
                     lens[k] = sched[k].shape[0]
         mt = None
         if tie_mt is not None:
-            mt = torch.as_tensor(np.ascontiguousarray(tie_mt).view(np.int32) if not isinstance(tie_mt, torch.Tensor) else tie_mt)
+            mt = tie_stream(tie_mt)
             if mt.dim() != 3 or tuple(mt.shape[1:]) != (S, 625):
                 raise ValueError(f"eval_td_population: tie_mt [L,S,625] expected, got {tuple(mt.shape)}")
             lens["tie_mt"] = int(mt.shape[0])
@@ -833,37 +742,17 @@ class BatchedPSRS:
         rows = [_gamma_pow(g, n_gamma_pow, dev, cap=t.N + 2) for g in np.broadcast_to(per["gamma"], (n_l,)).tolist()]
         n_gp = max(r.numel() for r in rows)
         gp = torch.stack([r if r.numel() == n_gp else torch.cat([r, r[-1:].expand(n_gp - r.numel())]) for r in rows]).contiguous()
-        if n_episodes is None:
-            n_episodes = 1 << 62
+        n_episodes = episode_bound(n_episodes)
         if q_t is None:
             q = torch.zeros((R, t.n_slots, t.nA), dtype=torch.float64, device=dev)
         else:
             q_t = q_t.to(dev)
             q = (q_t if q_t.dim() == 4 else q_t.reshape(-1, 1, t.n_slots, t.nA)).expand(n_l, S, t.n_slots, t.nA).reshape(R, t.n_slots, t.nA).contiguous().clone()
-        st = self.state
-        rng, cursor = st.rng.repeat(n_l, 1), st.cursor.repeat(n_l, 1)
-        init_cursor, cur_slot = st.init_cursor.repeat(n_l), st.cur_slot.repeat(n_l)
-        ro = L.Rollouts(R=R, rng=L.ptr(rng), cursor=L.ptr(cursor), init_cursor=L.ptr(init_cursor), cur_slot=L.ptr(cur_slot), perm=L.ptr(st.perm),
-                        perm_stride=st.perm_stride, init_perm=L.ptr(st.init_perm), init_stride=st.init_stride, rng_kind=st.rng_kind)
-        o = {k: torch.empty(R, dtype=dt, device=dev) for k, dt in (("sum_g", torch.float64), ("n_ep", torch.int64), ("steps", torch.int64),
-                                                                   ("cand", torch.int64), ("n_len", torch.int64), ("status", torch.int32))}
-        if ep_cap:
-            o["ep_g"] = torch.zeros((R, ep_cap), dtype=torch.float64, device=dev)
-            o["ep_len"] = torch.zeros((R, ep_cap + 1), dtype=torch.int32, device=dev)
-        if trace_cap:
-            o["trace_row"] = torch.full((R, trace_cap), -1, dtype=torch.int32, device=dev)
-            o["trace_pop"] = torch.zeros((R, trace_cap), dtype=torch.int32, device=dev)
-            o["td_err"] = torch.zeros((R, trace_cap), dtype=torch.float64, device=dev)
-            if (beh_host == L.BEHAVIOUR_EPS_GREEDY).any():
-                o["beh_arg"] = torch.zeros((R, trace_cap), dtype=torch.int32, device=dev)
-        if snap_cap:
-            o["q_snap"] = torch.zeros((R, snap_cap, t.n_slots, t.nA), dtype=torch.float64, device=dev)
-        if mt is not None:
-            mt = mt.to(device=dev, dtype=torch.int32).reshape(R, 625).contiguous().clone()
-            o["tie_mt"] = mt
-        oc = L.EvalMCOut(sum_g=L.ptr(o["sum_g"]), n_ep=L.ptr(o["n_ep"]), steps=L.ptr(o["steps"]), cand=L.ptr(o["cand"]),
-                         n_len=L.ptr(o["n_len"]), status=L.ptr(o["status"]), ep_g=L.ptr(o.get("ep_g")), ep_len=L.ptr(o.get("ep_len")),
-                         ep_cap=ep_cap, trace_row=L.ptr(o.get("trace_row")), trace_pop=L.ptr(o.get("trace_pop")), trace_cap=trace_cap)
+        ro, copies = population_state(self.state, n_l)
+        o, oc = rollout_outputs(R, dev, ep_cap, trace_cap)
+        td_outputs(o, q, trace_cap, snap_cap, beh_arg=(beh_host == L.BEHAVIOUR_EPS_GREEDY).any())
+        if mt is not None:  # (a copy: the caller's states stay where they were)
+            mt = o["tie_mt"] = mt.to(dev).reshape(R, 625).contiguous().clone()
         pc = L.TDPop(mode=int(mode), alpha=L.ptr(alpha_d), epsilon=L.ptr(eps_d), gamma=L.ptr(gamma_d), gamma_pow=L.ptr(gp), n_gamma_pow=n_gp,
                      behaviour=L.ptr(beh_d), behaviour_host=beh_host.ctypes.data_as(C.POINTER(C.c_int32)), alpha_ep=L.ptr(a_ep), epsilon_ep=L.ptr(e_ep),
                      n_sched=n_sched, pi=L.ptr(pi_d), pi_stride=t.n_slots * t.nA if pi_d.dim() == 3 else 0, q=L.ptr(q), td_err=L.ptr(o.get("td_err")),
@@ -872,12 +761,7 @@ class BatchedPSRS:
         L.check(L.load().offsim_eval_td_pop(C.byref(t.c), C.byref(ro), n_l, S, C.byref(pc), self.reject_mode, int(n_episodes), C.byref(oc),
                                             L.stream_ptr()))
         o["q"] = q
-        o = {k: v.reshape(n_l, S, *v.shape[1:]) for k, v in o.items()}
-        o["_keepalive"] = (pi_d, gp, alpha_d, eps_d, gamma_d, beh_d, a_ep, e_ep, rng, cursor, init_cursor, cur_slot)
-        o["_state"] = dict(rng=rng.reshape(n_l, S, 4), cursor=cursor.reshape(n_l, S, t.n_slots), init_cursor=init_cursor.reshape(n_l, S),
-                           cur_slot=cur_slot.reshape(n_l, S))  # where every learner's copy of the sampler stands afterwards
-        o["_kernel"] = "k_eval_td_pop"
-        return o
+        return population_result(o, n_l, S, copies, (pi_d, gp, alpha_d, eps_d, gamma_d, beh_d, a_ep, e_ep), "k_eval_td_pop", state=True)
 
     def scan_variant(self):
         """Name of the kernel eval_mc's fast path launches for this table and batch size (measurement label)."""
@@ -902,7 +786,7 @@ def _workspace_reservation(table, free_b):
     one = int(lib.offsim_shuffle_workspace_bytes(C.byref(table.c), 1))
     if one <= 0 or max(table.max_seg, table.N0) <= 65536 or os.environ.get("OFFSIM_SHUFFLE_CHUNKED", "1") == "0":
         return 0, False
-    budget = max(0, min(int(free_b * 0.92), free_b - (2 << 30)))
+    budget = max(0, min(int(free_b * WS_BUDGET_FRAC), free_b - WS_KEEP_FREE))
     full = int(lib.offsim_shuffle_workspace_bytes(C.byref(table.c), 1024))
     # A format-C table allocates the workspace FIRST (its format depends on it) and gets what the rule gives; any other table allocates
     # its stream buffers first and the workspace adapts to what is left (fewer workgroups' pools): a tenth of the free memory is kept
@@ -940,7 +824,13 @@ def resident_rollouts(table, keyed=True, free_bytes=None):
     if fmt == L.STREAMS_C and (table.N0 > (1 << 23) or not fits):
         fmt = L.STREAMS_B
     per = max(rollout_resident_bytes(table, keyed=keyed, fmt=fmt), 1)
-    return int(max(0, free_b - (2 << 30) - ws_b) // per), per, int(free_b), int(total_b)
+    return int(max(0, free_b - WS_KEEP_FREE - ws_b) // per), per, int(free_b), int(total_b)
+
+
+def default_tile(table, S, shuffle, keyed, resident=resident_rollouts):
+    """Seeds per tile when a driver is given none: all S at once unless every rollout has queue orders of its own (SHUFFLE_PER_ROLLOUT);
+    then as many as `resident` (resident_rollouts) says the free memory holds, `keyed` as the driver's reset writes them, at least 1."""
+    return S if shuffle != SHUFFLE_PER_ROLLOUT else int(max(1, min(S, resident(table, keyed=keyed)[0])))
 
 
 def evalmc_rollouts(table, seeds, pi, gamma, shuffle=SHUFFLE_PER_ROLLOUT, shuffle_seed=None, tile=None,
@@ -957,23 +847,13 @@ def evalmc_rollouts(table, seeds, pi, gamma, shuffle=SHUFFLE_PER_ROLLOUT, shuffl
     if isinstance(pi, ObsPolicy):
         return _evalmc_rollouts_rows_policy(table, seeds, pi, gamma, shuffle, shuffle_seed, tile, reject_mode, n_episodes, obs, next_obs)
     if tile is None:
-        tile = R if shuffle != SHUFFLE_PER_ROLLOUT else int(max(1, min(R, resident_rollouts(table, keyed=True)[0])))
+        tile = default_tile(table, R, shuffle, keyed=True)
     pi_slots = table.policy_slots(pi)
-    outs = {k: [] for k in ("sum_g", "n_ep", "steps", "cand", "status")}
-    env = None
-    for b in range(0, R, tile):
-        sd = seeds[b:b + tile]
-        if env is None or env.R != len(sd):
-            env = BatchedPSRS(table, len(sd), reject_mode)
+    outs = {k: [] for k in HOST_KEYS}
+    for _, sd, env in seed_tiles(seeds, tile, lambda n: BatchedPSRS(table, n, reject_mode)):
         env.reset_sampler(sd, shuffle, shuffle_seed, policy=pi_slots)
-        o = env.eval_mc(pi_slots, gamma, n_episodes)
-        for k in outs:
-            outs[k].append(o[k].cpu().numpy())
-        L.check_async_faults()  # (the copies above synchronised the stream)
-    res = {k: np.concatenate(v) for k, v in outs.items()}
-    with np.errstate(invalid="ignore", divide="ignore"):
-        res["value"] = res["sum_g"] / res["n_ep"]
-    return res
+        collect_host(outs, env.eval_mc(pi_slots, gamma, n_episodes))
+    return host_result(outs)
 
 
 def _evalmc_rollouts_rows_policy(table, seeds, pi, gamma, shuffle, shuffle_seed, tile, reject_mode, n_episodes, obs, next_obs):
@@ -982,23 +862,13 @@ def _evalmc_rollouts_rows_policy(table, seeds, pi, gamma, shuffle, shuffle_seed,
         raise ValueError("evalmc_rollouts: a policy over observations needs the log's obs= and next_obs=")
     p_next, p_init = pi.row_tables(table, obs, next_obs)
     if tile is None:
-        tile = R if shuffle != SHUFFLE_PER_ROLLOUT else int(max(1, min(R, resident_rollouts(table, keyed=False)[0])))
-    outs = {k: [] for k in ("sum_g", "n_ep", "steps", "cand", "status")}
-    env = None
-    for b in range(0, R, tile):
-        sd = seeds[b:b + tile]
-        if env is None or env.R != len(sd):
-            env = BatchedPSRS(table, len(sd), reject_mode)
+        tile = default_tile(table, R, shuffle, keyed=False)
+    outs = {k: [] for k in HOST_KEYS}
+    for _, sd, env in seed_tiles(seeds, tile, lambda n: BatchedPSRS(table, n, reject_mode)):
         env.reset_sampler(sd, shuffle, shuffle_seed)
         env._orders_for_generic()
-        o = env.eval_mc_rows_policy(p_next, p_init, gamma, n_episodes)
-        for k in outs:
-            outs[k].append(o[k].cpu().numpy())
-        L.check_async_faults()  # (the copies above synchronised the stream)
-    res = {k: np.concatenate(v) for k, v in outs.items()}
-    with np.errstate(invalid="ignore", divide="ignore"):
-        res["value"] = res["sum_g"] / res["n_ep"]
-    return res
+        collect_host(outs, env.eval_mc_rows_policy(p_next, p_init, gamma, n_episodes))
+    return host_result(outs)
 
 
 def evalmc_rollouts_population(table, seeds, policies, gamma, shuffle=SHUFFLE_PER_ROLLOUT, shuffle_seed=None, tile=None, policy_tile=None,
@@ -1029,28 +899,18 @@ def evalmc_rollouts_population(table, seeds, policies, gamma, shuffle=SHUFFLE_PE
     policy_tile = int(max(1, min(n_pol, policy_tile)))
     tables = policies.row_tables(table, obs, next_obs) if policy_tile >= n_pol else None  # (one policy tile: computed once)
     if tile is None:
-        tile = S if shuffle != SHUFFLE_PER_ROLLOUT else int(max(1, min(S, resident_rollouts(table, keyed=False)[0])))
-    keys = ("sum_g", "n_ep", "steps", "cand", "status")
-    outs = {k: [] for k in keys}
-    env = None
-    for b in range(0, S, tile):
-        sd = seeds[b:b + tile]
-        if env is None or env.R != len(sd):
-            env = BatchedPSRS(table, len(sd), reject_mode)
+        tile = default_tile(table, S, shuffle, keyed=False)
+    outs = {k: [] for k in HOST_KEYS}
+    for _, sd, env in seed_tiles(seeds, tile, lambda n: BatchedPSRS(table, n, reject_mode)):
         env.reset_sampler(sd, shuffle, shuffle_seed)
         env._orders_for_generic()
-        cols = {k: [] for k in keys}
+        cols = {k: [] for k in HOST_KEYS}
         for lo in range(0, n_pol, policy_tile):
             p_next, p_init = tables if tables is not None else policies.row_tables(table, obs, next_obs, lo, min(n_pol, lo + policy_tile))
-            o = env.eval_mc_rows_policy_population(p_next, p_init, gamma, n_episodes)
-            for k in keys:
-                cols[k].append(o[k].cpu().numpy())
-            L.check_async_faults()  # (the copies above synchronised the stream)
-        for k in keys:
+            collect_host(cols, env.eval_mc_rows_policy_population(p_next, p_init, gamma, n_episodes))
+        for k in HOST_KEYS:
             outs[k].append(np.concatenate(cols[k], axis=0))
-    res = {k: np.concatenate(v, axis=1) if v else np.zeros((n_pol, 0)) for k, v in outs.items()}
-    with np.errstate(invalid="ignore", divide="ignore"):
-        res["value"] = res["sum_g"] / res["n_ep"]
+    res = host_result(outs, axis=1, empty=(n_pol, 0))
     with warnings.catch_warnings():
         warnings.simplefilter("ignore", RuntimeWarning)  # (a policy without one completed episode: its mean is NaN, as its values are)
         res["mean_value"] = np.nanmean(res["value"], axis=1)

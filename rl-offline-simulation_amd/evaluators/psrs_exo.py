@@ -18,6 +18,7 @@ import torch
 
 from .. import _lib as L
 from ..table import RolloutState, TransitionTable, seed_streams, seeds_tensor, shuffle_queues
+from .rollout_io import HOST_KEYS, _gamma_pow, _prob_mode, collect_host, episode_bound, host_result, rollout_outputs, seed_tiles, td_outputs
 
 
 def tabulate_obs(s_values, x_values, o_combine_func, n_rows):
@@ -87,7 +88,6 @@ class BatchedPSRSExo:
         return tuple(o)
 
     def _run(self, pi_obs, obs_of, gamma, n_episodes, reseed, episode0, ep_cap, trace_cap, n_gamma_pow, td):
-        from .batched import _gamma_pow, _prob_mode
         ts, tx, dev, R = self.ts, self.tx, self.ts.device, self.R
         if reseed not in _RESEED:
             raise ValueError(f"reseed must be 'episode' or 'none', got {reseed!r}")
@@ -98,37 +98,24 @@ class BatchedPSRSExo:
         pi_d = pi_obs.to(device=dev, dtype=torch.float32 if mode == L.PROB_F32 else torch.float64).reshape(n_obs, ts.nA).contiguous()
         ob = torch.as_tensor(np.ascontiguousarray(obs_of, dtype=np.int32) if not isinstance(obs_of, torch.Tensor) else obs_of)
         ob = ob.to(device=dev, dtype=torch.int32).reshape(ts.n_slots, tx.n_slots).contiguous()
-        if n_episodes is None:
-            n_episodes = 1 << 62
-        o = {k: torch.empty(R, dtype=dt, device=dev) for k, dt in (("sum_g", torch.float64), ("n_ep", torch.int64), ("steps", torch.int64),
-                                                                   ("cand", torch.int64), ("n_len", torch.int64), ("status", torch.int32))}
+        n_episodes = episode_bound(n_episodes)
+        o, oc = rollout_outputs(R, dev, ep_cap, trace_cap)
         o["last"] = torch.full((R, 3), -1, dtype=torch.int32, device=dev)
-        if ep_cap:
-            o["ep_g"] = torch.zeros((R, ep_cap), dtype=torch.float64, device=dev)
-            o["ep_len"] = torch.zeros((R, ep_cap + 1), dtype=torch.int32, device=dev)
         if trace_cap:
-            o["trace_row"] = torch.full((R, trace_cap), -1, dtype=torch.int32, device=dev)
             o["trace_row_x"] = torch.full((R, trace_cap), -1, dtype=torch.int32, device=dev)
-            o["trace_pop"] = torch.zeros((R, trace_cap), dtype=torch.int32, device=dev)
         tdc, keep = None, ()
         if td is not None:
             q = td["q_obs"]
             q = torch.zeros((R, n_obs, ts.nA), dtype=torch.float64, device=dev) if q is None else \
                 torch.as_tensor(q, dtype=torch.float64).to(dev).reshape(R, n_obs, ts.nA).contiguous().clone()
-            if trace_cap:
-                o["td_err"] = torch.zeros((R, trace_cap), dtype=torch.float64, device=dev)
+            td_outputs(o, q, trace_cap, td["snap_cap"])
             a_ep = None if td["alpha_ep"] is None else torch.as_tensor(np.ascontiguousarray(td["alpha_ep"], dtype=np.float64)).to(dev)
-            if td["snap_cap"]:
-                o["q_snap"] = torch.zeros((R, td["snap_cap"], n_obs, ts.nA), dtype=torch.float64, device=dev)
             tdc = L.TD(mode=td["mode"], alpha=float(td["alpha"]), q=L.ptr(q), td_err=L.ptr(o.get("td_err")), td_cap=trace_cap,
                        behaviour=int(td["behaviour"]), epsilon=0.0, alpha_ep=L.ptr(a_ep), epsilon_ep=None, n_sched=0 if a_ep is None else a_ep.numel(),
                        q_snap=L.ptr(o.get("q_snap")), snap_cap=td["snap_cap"], snap_stride=max(int(td["snap_stride"]), 1), tie_mt=None, beh_arg=None)
             o["q"] = q
             keep = (a_ep,)
         gp = _gamma_pow(gamma, n_gamma_pow, dev, cap=ts.N + 2)
-        oc = L.EvalMCOut(sum_g=L.ptr(o["sum_g"]), n_ep=L.ptr(o["n_ep"]), steps=L.ptr(o["steps"]), cand=L.ptr(o["cand"]), n_len=L.ptr(o["n_len"]),
-                         status=L.ptr(o["status"]), ep_g=L.ptr(o.get("ep_g")), ep_len=L.ptr(o.get("ep_len")), ep_cap=ep_cap,
-                         trace_row=L.ptr(o.get("trace_row")), trace_pop=L.ptr(o.get("trace_pop")), trace_cap=trace_cap)
         xo = L.ExoOut(trace_row_x=L.ptr(o.get("trace_row_x")), last=L.ptr(o["last"]))
         L.check(L.load().offsim_eval_mc_exo(C.byref(ts.c), C.byref(tx.c), C.byref(self.rs.c), C.byref(self.rx.c), L.ptr(pi_d), L.ptr(ob), n_obs, mode,
                                             _RESEED[reseed], int(episode0), float(gamma), L.ptr(gp), gp.numel(), int(n_episodes), C.byref(oc),
@@ -167,23 +154,12 @@ def evalmc_rollouts_exo(env_or_tables, seeds, pi, gamma, obs_of=None, reseed="ep
         ts, tx = env_or_tables
         if obs_of is None:
             raise ValueError("evalmc_rollouts_exo: a pair of tables needs obs_of")
-    R = len(seeds)
-    tile = R if tile is None else int(tile)
-    outs = {k: [] for k in ("sum_g", "n_ep", "steps", "cand", "status")}
-    env = None
-    for b in range(0, R, max(tile, 1)):
-        sd = seeds[b:b + tile]
-        if env is None or env.R != len(sd):
-            env = BatchedPSRSExo(ts, tx, len(sd))
+    tile = len(seeds) if tile is None else int(tile)
+    outs = {k: [] for k in HOST_KEYS}
+    for _, sd, env in seed_tiles(seeds, max(tile, 1), lambda n: BatchedPSRSExo(ts, tx, n)):
         env.reset_sampler(sd)
-        o = env.eval_mc(pi, obs_of, gamma, n_episodes, reseed=reseed)
-        for k in outs:
-            outs[k].append(o[k].cpu().numpy())
-        L.check_async_faults()  # (the copies above synchronised the stream)
-    res = {k: (np.concatenate(v) if v else np.zeros(0)) for k, v in outs.items()}
-    with np.errstate(invalid="ignore", divide="ignore"):
-        res["value"] = res["sum_g"] / res["n_ep"]
-    return res
+        collect_host(outs, env.eval_mc(pi, obs_of, gamma, n_episodes, reseed=reseed))
+    return host_result(outs, empty=0)
 
 
 class PSRS_Exo:

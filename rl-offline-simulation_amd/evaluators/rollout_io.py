@@ -1,0 +1,154 @@
+"""Host-side plumbing shared by every launch of the rollout kernels (k_eval_mc and its kin) and by the seed-tile drivers above them.
+
+  rollout_outputs     the output dict of a launch and its struct offsim_evalmc_out (the one place that states dtypes, fills, shapes)
+  td_outputs          the learner kernels' extras: td_err, beh_arg, q_snap
+  tie_stream          a caller's MT19937 states as the int32 tensor the kernels read
+  population_state / population_result   a population launch's copies of the sampler state, and its dict as [n, S, ...]
+  seed_tiles / collect_host / host_result   the loop over tiles of sampler seeds and the host arrays it returns
+  episode_bound, _gamma_pow, _prob_mode     the episode limit, the discount table and the probability mode of a launch
+
+A leaf: it imports _lib, torch and NumPy only, so batched.py, psrs_exo.py and td_population.py all import it at module top.
+"""
+import numpy as np
+import torch
+
+from .. import _lib as L
+
+_GP_CACHE = {}
+_GP_CACHE_BYTES = 256 << 20
+
+
+def _gamma_pow(gamma, n, device, cap=None):
+    """gamma**t exactly as the host computes it for the reference (Python float ** int == libm pow, psrs.py:262), for every
+    t an episode can reach: at least `n` entries, then on until the factor is stationary (0, inf or 1: the device clamps t to
+    the last entry in that case, csrc/discount.hpp) or `cap` entries (an episode has at most N steps) are there.  Built in
+    blocks of 65536 with Python's own `float ** int` (NumPy's array pow is vectorised differently and differs in the last bit for
+    some t), so a gamma below 1 stops after the block its factor underflows in; the cache is bounded by bytes (_GP_CACHE_BYTES)."""
+    g = float(gamma)
+    cap = max(int(n), 2) if cap is None else max(int(cap), int(n), 2)
+    key = (g, int(n), cap, str(device))
+    if key not in _GP_CACHE:
+        stationary = lambda v: len(v) >= 2 and v[-1] == v[-2] and (v[-1] in (0.0, 1.0) or np.isinf(v[-1]))
+        blocks, total = [], 0
+        while total < max(int(n), 2) or (total < cap and not stationary(blocks[-1])):
+            m = min(65536, (max(int(n), 2) if total < max(int(n), 2) else cap) - total)
+            blocks.append(np.array([g ** t for t in range(total, total + m)], dtype=np.float64))  # (Python's own pow: NumPy's array pow is not bit-identical)
+            total += m
+        vals = np.concatenate(blocks)
+        keep = len(vals)
+        while keep > max(int(n), 2) and vals[keep - 1] == vals[keep - 2] == vals[keep - 3] and (vals[keep - 1] in (0.0, 1.0) or np.isinf(vals[keep - 1])):
+            keep -= 1  # (extended in blocks: keep exactly two stationary entries)
+        if sum(v.numel() * 8 for v in _GP_CACHE.values()) + keep * 8 > _GP_CACHE_BYTES:
+            _GP_CACHE.clear()
+        _GP_CACHE[key] = torch.from_numpy(vals[:keep].copy()).to(device)
+    return _GP_CACHE[key]
+
+
+def _prob_mode(table, p_dtype):
+    f32 = (p_dtype in (np.float32, torch.float32, np.dtype(np.float32))) and table.p_log.dtype == torch.float32
+    return L.PROB_F32 if f32 else L.PROB_F64
+
+
+def episode_bound(n_episodes):
+    """The kernels' episode limit: None (until the log ends) is a bound no log reaches."""
+    return 1 << 62 if n_episodes is None else int(n_episodes)
+
+
+_REQUIRED = (("sum_g", torch.float64), ("n_ep", torch.int64), ("steps", torch.int64), ("cand", torch.int64), ("n_len", torch.int64),
+             ("status", torch.int32))
+
+
+def rollout_outputs(R, device, ep_cap=0, trace_cap=0, out=None, dbg=False):
+    """(dict of output tensors, struct offsim_evalmc_out pointing at them) of a launch of R rollouts.  The six required outputs [R]
+    are left uninitialised (the kernel writes every entry) and taken from `out` where the caller supplies them; ep_g [R, ep_cap] and
+    ep_len [R, ep_cap + 1] (zeros), trace_row (-1) and trace_pop (zeros) [R, trace_cap], and dbg [R, 4] exist only when asked for
+    and are always allocated afresh; an absent one is a NULL pointer in the struct."""
+    o = out or {}
+    for k, dt in _REQUIRED:
+        if k not in o:
+            o[k] = torch.empty(R, dtype=dt, device=device)
+    if ep_cap:
+        o["ep_g"] = torch.zeros((R, ep_cap), dtype=torch.float64, device=device)
+        o["ep_len"] = torch.zeros((R, ep_cap + 1), dtype=torch.int32, device=device)
+    if trace_cap:
+        o["trace_row"] = torch.full((R, trace_cap), -1, dtype=torch.int32, device=device)
+        o["trace_pop"] = torch.zeros((R, trace_cap), dtype=torch.int32, device=device)
+    if dbg:
+        o["dbg"] = torch.zeros((R, 4), dtype=torch.int64, device=device)
+    oc = L.EvalMCOut(sum_g=L.ptr(o["sum_g"]), n_ep=L.ptr(o["n_ep"]), steps=L.ptr(o["steps"]), cand=L.ptr(o["cand"]), n_len=L.ptr(o["n_len"]),
+                     status=L.ptr(o["status"]), ep_g=L.ptr(o.get("ep_g")), ep_len=L.ptr(o.get("ep_len")), ep_cap=ep_cap,
+                     trace_row=L.ptr(o.get("trace_row")), trace_pop=L.ptr(o.get("trace_pop")), trace_cap=trace_cap, dbg=L.ptr(o.get("dbg")))
+    return o, oc
+
+
+def td_outputs(o, q, trace_cap, snap_cap, beh_arg=False):
+    """The extras of a learner launch on the Q tables q [R, rows, nA], added to `o`: td_err [R, trace_cap] f64 and, for a launch with an
+    epsilon-greedy behaviour (`beh_arg`), beh_arg [R, trace_cap] int32 when trace_cap > 0; q_snap [R, snap_cap, rows, nA] f64 when
+    snap_cap > 0.  All zeros."""
+    R, dev = q.shape[0], q.device
+    if trace_cap:
+        o["td_err"] = torch.zeros((R, trace_cap), dtype=torch.float64, device=dev)
+        if beh_arg:
+            o["beh_arg"] = torch.zeros((R, trace_cap), dtype=torch.int32, device=dev)
+    if snap_cap:
+        o["q_snap"] = torch.zeros((R, snap_cap, *q.shape[1:]), dtype=torch.float64, device=dev)
+
+
+def tie_stream(tie_mt, device=None):
+    """NumPy MT19937 states [..., 625] (int32 / uint32 words, array or tensor) as an int32 tensor on `device` (None: where it is).  A
+    tensor that already is one comes back as itself, so a launch advances the caller's states in place."""
+    mt = torch.as_tensor(np.ascontiguousarray(tie_mt).view(np.int32) if not isinstance(tie_mt, torch.Tensor) else tie_mt)
+    return mt.to(device=device, dtype=torch.int32)
+
+
+def population_state(st, n_pop):
+    """Copies of the sampler state `st` (a RolloutState of S rollouts) for n_pop members that each run all S rollouts: (struct
+    offsim_rollouts of n_pop * S rollouts, dict of the repeated rng / cursor / init_cursor / cur_slot).  Member l's rollout j is row
+    l * S + j.  The queue orders (perm, init_perm and their strides) are st's own, shared by all members; st itself is not touched."""
+    cp = dict(rng=st.rng.repeat(n_pop, 1), cursor=st.cursor.repeat(n_pop, 1), init_cursor=st.init_cursor.repeat(n_pop),
+              cur_slot=st.cur_slot.repeat(n_pop))
+    ro = L.Rollouts(R=n_pop * st.rng.shape[0], perm=L.ptr(st.perm), perm_stride=st.perm_stride, init_perm=L.ptr(st.init_perm), init_stride=st.init_stride,
+                    rng_kind=st.rng_kind, **{k: L.ptr(v) for k, v in cp.items()})
+    return ro, cp
+
+
+def population_result(o, n_pop, S, copies, keep, kernel, state=False):
+    """What a population launch returns: every tensor of `o` [n_pop * S, ...] as [n_pop, S, ...], `keep` and the state copies kept
+    alive, the kernel's name, and with `state` the copies themselves as o["_state"]: where every member's sampler stands afterwards."""
+    split = lambda d: {k: v.reshape(n_pop, S, *v.shape[1:]) for k, v in d.items()}  # noqa: E731
+    o = split(o)
+    o["_keepalive"] = tuple(keep) + tuple(copies.values())
+    if state:
+        o["_state"] = split(copies)
+    o["_kernel"] = kernel
+    return o
+
+
+def seed_tiles(seeds, tile, make_env):
+    """The seed-tile loop of the drivers: yields (offset, the tile's seeds, environment) for tiles of `tile` seeds; make_env(n) builds
+    an environment of n rollouts and is called only when the tile length changes (the last, shorter tile)."""
+    env = n_env = None
+    for b in range(0, len(seeds), tile):
+        sd = seeds[b:b + tile]
+        if len(sd) != n_env:
+            env, n_env = make_env(len(sd)), len(sd)
+        yield b, sd, env
+
+
+HOST_KEYS = ("sum_g", "n_ep", "steps", "cand", "status")
+
+
+def collect_host(parts, o):
+    """Append the launch's outputs named in `parts` as host arrays, then look at the fault word (the copies synchronised the stream)."""
+    for k in parts:
+        parts[k].append(o[k].cpu().numpy())
+    L.check_async_faults()
+
+
+def host_result(parts, axis=0, empty=None):
+    """The drivers' dictionary: every list of `parts` concatenated along `axis` (a driver that accepts no seeds at all gives `empty`, the
+    shape of its empty arrays) and value = sum_g / n_ep, NaN where a seed completed no episode."""
+    res = {k: np.concatenate(v, axis=axis) if v or empty is None else np.zeros(empty) for k, v in parts.items()}
+    with np.errstate(invalid="ignore", divide="ignore"):
+        res["value"] = res["sum_g"] / res["n_ep"]
+    return res

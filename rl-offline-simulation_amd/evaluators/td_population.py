@@ -18,8 +18,9 @@ import numpy as np
 import torch
 
 from .. import _lib as L
-from .batched import SHUFFLE_PER_ROLLOUT, BatchedPSRS, resident_rollouts
+from .batched import SHUFFLE_PER_ROLLOUT, BatchedPSRS, default_tile
 from .psrs import _schedule
+from .rollout_io import seed_tiles, tie_stream
 
 _MODE = {"qlearn": L.TD_QLEARN, "expsarsa": L.TD_EXPSARSA, L.TD_QLEARN: L.TD_QLEARN, L.TD_EXPSARSA: L.TD_EXPSARSA}
 _BEHAVIOUR = {"fixed": L.BEHAVIOUR_FIXED, "eps_greedy": L.BEHAVIOUR_EPS_GREEDY, "greedy": L.BEHAVIOUR_EPS_GREEDY, "soft_greedy": L.BEHAVIOUR_SOFT_GREEDY}
@@ -164,18 +165,14 @@ class TDPopulation:
         pi_slots, q_slots = self._slots(table, pi), self._slots(table, Q0, nan=0.0)
         beh = np.array([_BEHAVIOUR[b] for b in self.behaviour], dtype=np.int32)
         if tie_mt is not None:
-            tie_mt = torch.as_tensor(np.ascontiguousarray(tie_mt).view(np.int32) if not isinstance(tie_mt, torch.Tensor) else tie_mt)
+            tie_mt = tie_stream(tie_mt)
             if tuple(tie_mt.shape) != (n_l, S, 625):
                 raise ValueError(f"TDPopulation.run: tie_mt [L,S,625] = {(n_l, S, 625)} expected, got {tuple(tie_mt.shape)}")
         if tile is None:
-            tile = S if shuffle != SHUFFLE_PER_ROLLOUT else int(max(1, min(S, resident_rollouts(table, keyed=False)[0])))
+            tile = default_tile(table, S, shuffle, keyed=False)
         keys = ["q", "ep_g", "n_ep", "steps", "status"] + (["td_err"] if trace_cap else [])
         parts = {k: [] for k in keys}
-        env = None
-        for b in range(0, S, int(tile)):
-            sd = seeds[b:b + int(tile)]
-            if env is None or env.R != len(sd):
-                env = BatchedPSRS(table, len(sd), reject_mode)
+        for b, sd, env in seed_tiles(seeds, int(tile), lambda n: BatchedPSRS(table, n, reject_mode)):
             env.reset_sampler(sd, shuffle, shuffle_seed, rejection=rejection)
             o = env.eval_td_population(self.mode, a_const, self.gamma, beh, e_const, pi_slots=pi_slots, q_slots=q_slots, alpha_ep=a_tab,
                                        epsilon_ep=e_tab, tie_mt=None if tie_mt is None else tie_mt[:, b:b + len(sd)], n_episodes=n_ep, ep_cap=ep_cap,
