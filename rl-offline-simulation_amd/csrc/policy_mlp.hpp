@@ -76,7 +76,7 @@ struct PmlpLayers {
 __device__ __forceinline__ float pmlp_act(float v, int act, float slope) {
     switch (act) {
         case OFFSIM_ACT_TANH: return tanhf(v);
-        case OFFSIM_ACT_RELU: return v > 0.0f ? v : 0.0f;
+        case OFFSIM_ACT_RELU: return !(v <= 0.0f) ? v : 0.0f;  // torch: NaN stays NaN (the NaN row of an index outside x, include/offsim.h)
         case OFFSIM_ACT_LEAKY_RELU: return v > 0.0f ? v : v * slope;  // torch: x if x > 0 else slope * x
         default: return v;
     }
