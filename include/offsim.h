@@ -457,7 +457,7 @@ int offsim_td_curves(const double *ep_g, const int64_t *n_ep, int32_t L, int32_t
  *   snap_stride / snap_cap and the left-to-right sum of Q[S'] @ pi[S'] are offsim_eval_td's with the slot replaced by obs_of[s, x];
  *   OFFSIM_PROB_F64 only.  An accepted step whose next pair has no row stops the rollout with OFFSIM_ST_KEYERROR: the environment has
  *   stepped (cursors, state, last), the step is not counted.  Behaviour policy: OFFSIM_BEHAVIOUR_FIXED only -- the epsilon-greedy and
- *   soft-greedy behaviours on the learner's own Q and the tie stream (td->tie_mt) return OFFSIM_EUNSUPPORTED: deliberately not built.
+ *   soft-greedy behaviours on the learner's own Q and the tie stream (td->tie_mt) return OFFSIM_EUNSUPPORTED here: they are offsim_eval_td_exo_pop's (below).
  * LDS per workgroup: jump tables, pi, obs_of, both seg_off arrays, per-rollout cursors of both families and per-rollout Q; 4 rollouts per
  *   workgroup, then 2, then 1 while the carve exceeds 64 KiB, one rollout up to 160 KiB, beyond that OFFSIM_EUNSUPPORTED.
  * Argument validation happens before any HIP call -- the two tables, rs / rx, n_obs / obs_of / pi, the prob mode, the reseed / provider
@@ -472,6 +472,37 @@ int offsim_eval_mc_exo(const offsim_table *ts, const offsim_table *tx, offsim_ro
                        const int32_t *obs_of, int32_t n_obs, int32_t prob_mode, int32_t reseed, uint64_t episode0, double gamma,
                        const double *gamma_pow, int64_t n_gamma_pow, int64_t max_episodes, const offsim_evalmc_out *out,
                        const offsim_exo_out *xout, const offsim_td *td /* NULL: evalMC */, void *stream);
+
+/* offsim_eval_td_exo_pop: the learner drivers of offsim_eval_mc_exo for a population of L learners on the same S seeds in ONE launch, every
+ * learner with any behaviour policy of the reference on its OWN Q (agents/tabular.py:7-32): what offsim_eval_td_pop is to offsim_eval_td,
+ * on PSRS_Exo.  L = 1 is the single learner with an epsilon-greedy / greedy / soft-greedy behaviour, which offsim_eval_mc_exo refuses.
+ *   ts / tx, obs_of [ts->n_slots, tx->n_slots], n_obs, xout: offsim_eval_mc_exo's.
+ *   rs->R = rx->R = L * S, learner-major: rollout r = l * S + j is learner l on seed j.  rs->rng, both cursor arrays, both init_cursor and
+ *   both cur_slot are [R] rows (the caller's S rows replicated L times), advanced and written back per rollout.  rs->perm / rs->init_perm
+ *   and rx->perm hold S orders, not R: rollout r reads row j (stride 0: one shared order; NULL: table order).  The kernel only reads them.
+ *   pop: struct offsim_td_pop as offsim_eval_td_pop takes it, with n_obs in the place of n_slots: q [L * S, n_obs, nA],
+ *   pi [L, n_obs, nA] with pi_stride = n_obs * nA or one table with pi_stride = 0, q_snap [L * S, snap_cap, n_obs, nA]; alpha, epsilon,
+ *   gamma, behaviour (+ behaviour_host), gamma_pow [L, n_gamma_pow], alpha_ep / epsilon_ep [L, n_sched], td_err / beh_arg [L * S, td_cap],
+ *   tie_mt [L * S, 625] or NULL (first maximum) unchanged.
+ * Behaviour (per learner): OFFSIM_BEHAVIOUR_FIXED rejects against pi[o]; OFFSIM_BEHAVIOUR_EPS_GREEDY / _SOFT_GREEDY rebuild the
+ *   distribution from the learner's Q row of the current OBSERVATION o = obs_of[s, x] before every step (psrs.py:158) -- the rules, the
+ *   schedules and the tie stream are offsim_eval_td's, word for word (one definition on the device).  The distribution is formed before
+ *   the step: a step that then finds a queue missing or empty has drawn its tie.
+ * reseed: OFFSIM_EXO_RESEED_EPISODE (episode e of every rollout draws from default_rng(episode0 + e), the reference's protocol; PCG64 only,
+ *   OFFSIM_STREAM_PHILOX is refused with OFFSIM_EUNSUPPORTED) or OFFSIM_EXO_RESEED_NONE (each seed's own stream rs->rng, either provider;
+ *   the L learners of seed j start from the same stream state, so comparisons between learners are paired).
+ * Identity: with OFFSIM_BEHAVIOUR_FIXED, rollout l * S + j equals, in every output bit and in the state it leaves, offsim_eval_mc_exo's
+ *   learner driver run alone with learner l's setting from seed j's state and orders (the loop is the same code: k_eval_mc_exo's TD
+ *   instance under a population index, csrc/td_pop_exo.hpp).
+ * LDS per workgroup: offsim_eval_mc_exo's learner carve plus, per rollout, nA f64 for the behaviour distribution and 624 u32 for the tie
+ *   stream; 4 / 2 / 1 rollouts per workgroup against 64 KiB, one rollout up to 160 KiB, beyond that OFFSIM_EUNSUPPORTED.  A workgroup holds
+ *   rollouts of one learner: grid = L * ceil(S / rollouts per workgroup).
+ * Argument validation happens before any HIP call -- everything offsim_eval_mc_exo checks about the two tables, rs / rx, obs_of / n_obs, the
+ * reseed / provider pair and the outputs; everything offsim_eval_td_pop checks about L (1..65535), S >= 1, R = L * S, the per-learner arrays,
+ * behaviour_host, the schedules and the snapshot stride; negative capacities; the LDS size --; rs->R = 0 launches nothing. */
+int offsim_eval_td_exo_pop(const offsim_table *ts, const offsim_table *tx, offsim_rollouts *rs, offsim_rollouts *rx, int32_t L, int32_t S,
+                           const offsim_td_pop *pop, const int32_t *obs_of, int32_t n_obs, int32_t reseed, uint64_t episode0,
+                           int64_t max_episodes, const offsim_evalmc_out *out, const offsim_exo_out *xout, void *stream);
 
 /* Fast path of evalMC_psrs for a fixed tabular policy (the headline scan).
  * offsim_compile_policy folds psrs.py:53-57 for policy pi [n_slots,nA] f64 into one 64-bit key per grouped row:

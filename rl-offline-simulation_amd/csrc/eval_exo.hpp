@@ -16,8 +16,9 @@
 //                              PCG64 only.
 //   OFFSIM_EXO_RESEED_NONE     the rollout's own stream (rs.rng, either provider) runs on across episodes.
 //
-// Not here, deliberately: the epsilon-greedy / soft-greedy behaviour policies of k_eval_mc and their tie stream (the learner acts on its
-// own Q row) -- offsim_eval_mc_exo returns OFFSIM_EUNSUPPORTED for them -- and the reject modes other than the default rule.
+// The epsilon-greedy / soft-greedy behaviour policies of k_eval_mc and their tie stream (the learner acts on its own Q row) are the POP
+// instances' (offsim_eval_td_exo_pop, a population of L >= 1 learners; below): offsim_eval_mc_exo keeps returning OFFSIM_EUNSUPPORTED for
+// them.  Not here, deliberately: the reject modes other than the default rule.
 //
 // Included by offsim_hip.hip behind offsim_eval_td: check_table, check_prob_mode, check_evalmc_out, with_plog_prob, rejects_f64 / _f32,
 // WaveRng, wave_rng_init and allow_big_lds are that file's.
@@ -30,12 +31,38 @@ struct ExoArgs {
     offsim_exo_out xout;
 };
 
-template <typename PL, typename PROB, bool TD>
+// POP = true (with TD): a population of L tabular learners on the same S seeds, every one acting on its own Q (offsim_eval_td_exo_pop;
+// arguments and index rules in csrc/td_pop_exo.hpp).  The instance overwrites its per-launch hyper-parameters -- td.alpha / epsilon /
+// behaviour / the schedule rows, gamma, gamma_pow, pi -- with its workgroup's learner's before anything reads them, and before every step
+// rebuilds the behaviour distribution from the Q row of the current observation (td_behaviour, the block k_eval_mc calls) in beh_lds,
+// which the step then rejects against.  LDS: the carve above, then -- behind the x-cursors, so that every offset above stays --
+//   [beh_lds per wave: waves * nA f64, 8-byte aligned][tie stream per wave: waves * 624 u32]
+// The POP instances take their own argument struct, so the kernel arguments of every other instance are what they were.
+#include "td_pop_exo.hpp"
+template <bool POP>
+using ExoKernelArgs = std::conditional_t<POP, TdPopExoArgs, ExoArgs>;
+
+template <typename PL, typename PROB, bool TD, bool POP = false>
 __global__ void __launch_bounds__(256, 4) k_eval_mc_exo(offsim_table ts, offsim_table tx, offsim_rollouts rs, offsim_rollouts rx,
-                                                     const PROB *__restrict__ pi, ExoArgs xa, double gamma, const double *__restrict__ gamma_pow,
-                                                     int64_t n_gamma_pow, int64_t max_episodes, offsim_evalmc_out out, offsim_td td) {
+                                                     const PROB *__restrict__ pi, ExoKernelArgs<POP> xa, double gamma,
+                                                     const double *__restrict__ gamma_pow, int64_t n_gamma_pow, int64_t max_episodes,
+                                                     offsim_evalmc_out out, offsim_td td) {
+    static_assert(!POP || (TD && sizeof(PROB) == 8), "a population is a population of learners (f64 pi)");
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const int waves = blockDim.x / WAVE;
+    int pop_l = 0, pop_nb = 1;  // POP: this workgroup's learner, workgroups per learner
+    if constexpr (POP) {
+        pop_nb = (xa.S + waves - 1) / waves;
+        pop_l = blockIdx.x / pop_nb;
+        td.alpha = xa.alpha[pop_l];
+        td.epsilon = xa.epsilon[pop_l];
+        td.behaviour = xa.behaviour[pop_l];
+        td.alpha_ep = xa.alpha_ep ? xa.alpha_ep + (int64_t)pop_l * td.n_sched : nullptr;
+        td.epsilon_ep = xa.epsilon_ep ? xa.epsilon_ep + (int64_t)pop_l * td.n_sched : nullptr;
+        gamma = xa.gamma[pop_l];
+        gamma_pow = xa.gamma_pow + (int64_t)pop_l * n_gamma_pow;
+        pi = (const PROB *)xa.pi + (int64_t)pop_l * xa.pi_stride;
+    }
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE), lane = threadIdx.x & (WAVE - 1);  // uniform -> SGPR
     const int ns = ts.n_slots, nx = tx.n_slots, nA = ts.nA, n_obs = xa.n_obs;
     Jump *tables = (Jump *)lds_raw;
@@ -46,18 +73,37 @@ __global__ void __launch_bounds__(256, 4) k_eval_mc_exo(offsim_table ts, offsim_
     uint32_t *seg_x = seg_s + (ns + 1);
     uint32_t *cur_s = seg_x + (nx + 1) + (size_t)wave * ns;
     uint32_t *cur_x = seg_x + (nx + 1) + (size_t)waves * ns + (size_t)wave * nx;
+    // POP: this rollout's action distribution at its current observation, and its copy of the tie-breaking MT19937 stream (624 words; the
+    // position is kept in a register)
+    double *beh_all = (double *)(((uintptr_t)(seg_x + (nx + 1) + (size_t)waves * (ns + nx)) + 7) & ~(uintptr_t)7);
+    double *beh_lds = beh_all + (size_t)wave * nA;
+    volatile uint32_t *mt_lds = (volatile uint32_t *)(beh_all + (size_t)waves * nA) + (size_t)wave * 624;
     for (int i = threadIdx.x; i < n_obs * nA; i += blockDim.x) pi_lds[i] = pi[i];
     for (int i = threadIdx.x; i < ns * nx; i += blockDim.x) obs_lds[i] = xa.obs_of[i];
     for (int i = threadIdx.x; i <= ns; i += blockDim.x) seg_s[i] = ts.seg_off[i];
     for (int i = threadIdx.x; i <= nx; i += blockDim.x) seg_x[i] = tx.seg_off[i];
     __syncthreads();
-    const int r = blockIdx.x * waves + wave;
-    if (r >= rs.R) return;
+    int r = blockIdx.x * waves + wave;
+    int ord = r;  // POP: the queue orders rollout r walks
+    if constexpr (POP) {
+        ord = __builtin_amdgcn_readfirstlane((blockIdx.x - pop_l * pop_nb) * waves + wave);
+        if (ord >= xa.S) return;
+        r = pop_l * xa.S + ord;
+    } else {
+        if (r >= rs.R) return;
+    }
     uint32_t *cur_s_glb = rs.cursor + (int64_t)r * ns, *cur_x_glb = rx.cursor + (int64_t)r * nx;
     for (int i = lane; i < ns; i += WAVE) cur_s[i] = cur_s_glb[i];
     for (int i = lane; i < nx; i += WAVE) cur_x[i] = cur_x_glb[i];
     if (TD)
         for (int i = lane; i < n_obs * nA; i += WAVE) q_lds[i] = td.q[(int64_t)r * n_obs * nA + i];
+    uint32_t mt_pos = 624u;
+    if constexpr (POP) {
+        if (td.tie_mt) {
+            for (int i = lane; i < 624; i += WAVE) mt_lds[i] = td.tie_mt[(int64_t)r * 625 + i];
+            mt_pos = td.tie_mt[(int64_t)r * 625 + 624];
+        }
+    }
 
     const bool per_episode = xa.reseed == OFFSIM_EXO_RESEED_EPISODE;
     const int kind = per_episode ? OFFSIM_STREAM_PCG64 : rs.rng_kind;
@@ -68,9 +114,9 @@ __global__ void __launch_bounds__(256, 4) k_eval_mc_exo(offsim_table ts, offsim_
     wave_rng_init(rng, table, base, inc, kind);  // (per episode: filled again at every reset)
     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): table, cursors and Q visible to the whole wave
 
-    const uint32_t *perm_s = rs.perm ? rs.perm + (int64_t)r * rs.perm_stride : nullptr;
-    const uint32_t *perm_x = rx.perm ? rx.perm + (int64_t)r * rx.perm_stride : nullptr;
-    const uint32_t *init_row = rs.init_perm ? rs.init_perm + (int64_t)r * rs.init_stride : nullptr;
+    const uint32_t *perm_s = rs.perm ? rs.perm + (int64_t)(POP ? ord : r) * rs.perm_stride : nullptr;
+    const uint32_t *perm_x = rx.perm ? rx.perm + (int64_t)(POP ? ord : r) * rx.perm_stride : nullptr;
+    const uint32_t *init_row = rs.init_perm ? rs.init_perm + (int64_t)(POP ? ord : r) * rs.init_stride : nullptr;
     const PL *plog = (const PL *)ts.p_log;
     uint32_t ic = rs.init_cursor[r];
     int ss = __builtin_amdgcn_readfirstlane(rs.cur_slot[r]), xs = __builtin_amdgcn_readfirstlane(rx.cur_slot[r]);
@@ -118,12 +164,24 @@ __global__ void __launch_bounds__(256, 4) k_eval_mc_exo(offsim_table ts, offsim_
             const int o_cur = __builtin_amdgcn_readfirstlane(obs_lds[ss * nx + xs]);
             const uint32_t beg_s = seg_s[ss], len_s = seg_s[ss + 1] - beg_s;
             const uint32_t beg_x = seg_x[xs], len_x = seg_x[xs + 1] - beg_x;
-            if ((unsigned)o_cur >= (unsigned)n_obs || len_s == 0 || len_x == 0) {  // pi has no row (IndexError) / a queue is missing (KeyError)
+            if ((unsigned)o_cur >= (unsigned)n_obs || (!POP && (len_s == 0 || len_x == 0))) {  // pi has no row (IndexError) / a queue is missing (KeyError)
                 status = OFFSIM_ST_KEYERROR;
                 terminate = true;
                 break;
             }
             const PROB *pn = pi_lds + (size_t)o_cur * nA;
+            if constexpr (POP) {
+                // p = behavior_policy(Q[[S], :], ...) (psrs.py:158) comes BEFORE env.step: a step that finds a queue missing has drawn its tie
+                if (td.behaviour != OFFSIM_BEHAVIOUR_FIXED) {
+                    td_behaviour(td, q_lds + (size_t)o_cur * nA, nA, beh_lds, mt_lds, mt_pos, lane, r, ep, steps);
+                    pn = (const PROB *)beh_lds;
+                }
+                if (len_s == 0 || len_x == 0) {
+                    status = OFFSIM_ST_KEYERROR;
+                    terminate = true;
+                    break;
+                }
+            }
             uint32_t cs = (uint32_t)__builtin_amdgcn_readfirstlane((int)cur_s[ss]), cx = (uint32_t)__builtin_amdgcn_readfirstlane((int)cur_x[xs]);
             uint32_t popped = 0;
             int gsf = -1, gxf = -1;
@@ -237,6 +295,12 @@ __global__ void __launch_bounds__(256, 4) k_eval_mc_exo(offsim_table ts, offsim_
     for (int i = lane; i < nx; i += WAVE) cur_x_glb[i] = cur_x[i];
     if (TD)
         for (int i = lane; i < n_obs * nA; i += WAVE) td.q[(int64_t)r * n_obs * nA + i] = q_lds[i];
+    if constexpr (POP) {
+        if (td.tie_mt) {
+            for (int i = lane; i < 624; i += WAVE) td.tie_mt[(int64_t)r * 625 + i] = mt_lds[i];
+            if (lane == 0) td.tie_mt[(int64_t)r * 625 + 624] = mt_pos;
+        }
+    }
     if (lane == 0) {
         rs.init_cursor[r] = ic;
         rx.init_cursor[r] = ic;  // (both families pop the same initial row: a later PSRS_Exo.reset finds them in step)
@@ -267,32 +331,58 @@ __global__ void __launch_bounds__(256, 4) k_eval_mc_exo(offsim_table ts, offsim_
     }
 }
 
-static size_t exo_lds_bytes(int waves, int64_t ns, int64_t nx, int64_t n_obs, int64_t nA, size_t prob_bytes, bool td) {
+// (pop: 8 bytes for the alignment of beh_lds, as evalmc_lds_bytes counts them)
+static size_t exo_lds_bytes(int waves, int64_t ns, int64_t nx, int64_t n_obs, int64_t nA, size_t prob_bytes, bool td, bool pop = false) {
     return (size_t)waves * (WAVE + 1) * sizeof(Jump) + (td ? (size_t)waves * n_obs * nA * 8 : 0) + (size_t)(n_obs * nA) * prob_bytes +
-           (size_t)(ns * nx) * 4 + (size_t)(ns + 1) * 4 + (size_t)(nx + 1) * 4 + (size_t)waves * (ns + nx) * 4;
+           (size_t)(ns * nx) * 4 + (size_t)(ns + 1) * 4 + (size_t)(nx + 1) * 4 + (size_t)waves * (ns + nx) * 4 +
+           (pop ? 8 + (size_t)waves * nA * 8 + (size_t)waves * 624 * 4 : 0);
 }
 
 // the launch shape of evalmc_launch: 4 rollouts per workgroup, halved until the carve fits 64 KiB; up to 160 KiB with one rollout
-static int exo_launch_shape(const offsim_table *ts, const offsim_table *tx, int32_t n_obs, size_t pb, bool td, int *waves_out, size_t *lds_out) {
+static int exo_launch_shape(const offsim_table *ts, const offsim_table *tx, int32_t n_obs, size_t pb, bool td, int *waves_out, size_t *lds_out,
+                            bool pop = false, const char *who = "eval_mc_exo") {
     if ((int64_t)ts->n_slots * tx->n_slots > 40960 || (int64_t)n_obs * ts->nA > 40960)  // (beyond 160 KiB whatever else: also keeps the sums below in range)
-        return fail(OFFSIM_EUNSUPPORTED, "eval_mc_exo: obs_of, policy, Q table and cursors exceed 160 KiB of LDS%s");
+        return fail(OFFSIM_EUNSUPPORTED, "%s: obs_of, policy, Q table and cursors exceed 160 KiB of LDS", who);
     int waves = 4;
-    while (waves > 1 && exo_lds_bytes(waves, ts->n_slots, tx->n_slots, n_obs, ts->nA, pb, td) > 64 * 1024) waves >>= 1;
-    const size_t lds = exo_lds_bytes(waves, ts->n_slots, tx->n_slots, n_obs, ts->nA, pb, td);
-    if (lds > 160 * 1024) return fail(OFFSIM_EUNSUPPORTED, "eval_mc_exo: obs_of, policy, Q table and cursors exceed 160 KiB of LDS%s");
+    while (waves > 1 && exo_lds_bytes(waves, ts->n_slots, tx->n_slots, n_obs, ts->nA, pb, td, pop) > 64 * 1024) waves >>= 1;
+    const size_t lds = exo_lds_bytes(waves, ts->n_slots, tx->n_slots, n_obs, ts->nA, pb, td, pop);
+    if (lds > 160 * 1024) return fail(OFFSIM_EUNSUPPORTED, "%s: obs_of, policy, Q table and cursors exceed 160 KiB of LDS", who);
     *waves_out = waves;
     *lds_out = lds;
     return OFFSIM_OK;
 }
 
-template <typename PL, typename PROB, bool TD>
-static int exo_launch(const offsim_table *ts, const offsim_table *tx, offsim_rollouts *rs, offsim_rollouts *rx, const void *pi, const ExoArgs &xa,
-                      double gamma, const double *gamma_pow, int64_t n_gamma_pow, int64_t max_episodes, const offsim_evalmc_out *out,
-                      const offsim_td &td, int waves, size_t lds, void *stream) {
-    if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_eval_mc_exo<PL, PROB, TD>), (int)lds));
-    hipLaunchKernelGGL((k_eval_mc_exo<PL, PROB, TD>), dim3((rs->R + waves - 1) / waves), dim3(waves * WAVE), lds, (hipStream_t)stream, *ts, *tx, *rs, *rx,
+template <typename PL, typename PROB, bool TD, bool POP = false>
+static int exo_launch(const offsim_table *ts, const offsim_table *tx, offsim_rollouts *rs, offsim_rollouts *rx, const void *pi,
+                      const ExoKernelArgs<POP> &xa, double gamma, const double *gamma_pow, int64_t n_gamma_pow, int64_t max_episodes,
+                      const offsim_evalmc_out *out, const offsim_td &td, int waves, size_t lds, void *stream) {
+    if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_eval_mc_exo<PL, PROB, TD, POP>), (int)lds));
+    unsigned grid = (unsigned)((rs->R + waves - 1) / waves);
+    if constexpr (POP) grid = (unsigned)(rs->R / xa.S) * (unsigned)((xa.S + waves - 1) / waves);  // a workgroup holds rollouts of one learner
+    hipLaunchKernelGGL((k_eval_mc_exo<PL, PROB, TD, POP>), dim3(grid), dim3(waves * WAVE), lds, (hipStream_t)stream, *ts, *tx, *rs, *rx,
                        (const PROB *)pi, xa, gamma, gamma_pow, n_gamma_pow, max_episodes, *out, td);
     LAUNCH_CHECK();
+    return OFFSIM_OK;
+}
+
+// what offsim_eval_mc_exo and offsim_eval_td_exo_pop check alike: the two tables, rs / rx, obs_of / n_obs, the reseed / provider pair, out
+static int exo_check_common(const char *who, const offsim_table *ts, const offsim_table *tx, const offsim_rollouts *rs, const offsim_rollouts *rx,
+                            const int32_t *obs_of, int32_t n_obs, int32_t reseed, const offsim_evalmc_out *out, const double *gamma_pow,
+                            int64_t n_gamma_pow) {
+    int rc = check_table(ts);
+    if (rc) return rc;
+    if ((rc = check_table(tx))) return rc;
+    if (ts->N != tx->N || ts->N0 != tx->N0) return fail(OFFSIM_EINVAL, "%s: the s-table and the x-table hold different logs (N / N0 differ)", who);
+    if (ts->N0 > 0 && (!ts->init_slot || !tx->init_slot || !ts->init_orig)) return fail(OFFSIM_EINVAL, "%s: table without its init rows", who);
+    if (!rs || !rx || rs->R < 0 || rs->R != rx->R) return fail(OFFSIM_EINVAL, "%s: rs / rx NULL or of different R", who);
+    if (n_obs <= 0 || !obs_of) return fail(OFFSIM_EINVAL, "%s: bad n_obs, or obs_of / pi is NULL", who);
+    if (reseed != OFFSIM_EXO_RESEED_NONE && reseed != OFFSIM_EXO_RESEED_EPISODE) return fail(OFFSIM_EINVAL, "%s: bad reseed mode", who);
+    if (rs->rng_kind != OFFSIM_STREAM_PCG64 && rs->rng_kind != OFFSIM_STREAM_PHILOX) return fail(OFFSIM_EINVAL, "%s: unknown stream provider", who);
+    if (reseed == OFFSIM_EXO_RESEED_EPISODE && rs->rng_kind == OFFSIM_STREAM_PHILOX)
+        return fail(OFFSIM_EUNSUPPORTED, "%s: OFFSIM_EXO_RESEED_EPISODE seeds default_rng(episode): the stream must be OFFSIM_STREAM_PCG64", who);
+    if (!out) return fail(OFFSIM_EINVAL, "%s: out is NULL", who);
+    if ((rc = check_evalmc_out(who, out, gamma_pow, n_gamma_pow))) return rc;
+    if (out->ep_cap < 0 || out->trace_cap < 0) return fail(OFFSIM_EINVAL, "%s: negative ep_cap / trace_cap", who);
     return OFFSIM_OK;
 }
 
@@ -300,21 +390,10 @@ extern "C" int offsim_eval_mc_exo(const offsim_table *ts, const offsim_table *tx
                                   const int32_t *obs_of, int32_t n_obs, int32_t prob_mode, int32_t reseed, uint64_t episode0, double gamma,
                                   const double *gamma_pow, int64_t n_gamma_pow, int64_t max_episodes, const offsim_evalmc_out *out,
                                   const offsim_exo_out *xout, const offsim_td *td, void *stream) {
-    int rc = check_table(ts);
+    int rc = exo_check_common("eval_mc_exo", ts, tx, rs, rx, obs_of, n_obs, reseed, out, gamma_pow, n_gamma_pow);
     if (rc) return rc;
-    if ((rc = check_table(tx))) return rc;
-    if (ts->N != tx->N || ts->N0 != tx->N0) return fail(OFFSIM_EINVAL, "eval_mc_exo: the s-table and the x-table hold different logs (N / N0 differ)%s");
-    if (ts->N0 > 0 && (!ts->init_slot || !tx->init_slot || !ts->init_orig)) return fail(OFFSIM_EINVAL, "eval_mc_exo: table without its init rows%s");
-    if (!rs || !rx || rs->R < 0 || rs->R != rx->R) return fail(OFFSIM_EINVAL, "eval_mc_exo: rs / rx NULL or of different R%s");
-    if (n_obs <= 0 || !obs_of || !pi) return fail(OFFSIM_EINVAL, "eval_mc_exo: bad n_obs, or obs_of / pi is NULL%s");
+    if (!pi) return fail(OFFSIM_EINVAL, "eval_mc_exo: bad n_obs, or obs_of / pi is NULL%s");
     if ((rc = check_prob_mode("eval_mc_exo", ts, prob_mode))) return rc;
-    if (reseed != OFFSIM_EXO_RESEED_NONE && reseed != OFFSIM_EXO_RESEED_EPISODE) return fail(OFFSIM_EINVAL, "eval_mc_exo: bad reseed mode%s");
-    if (rs->rng_kind != OFFSIM_STREAM_PCG64 && rs->rng_kind != OFFSIM_STREAM_PHILOX) return fail(OFFSIM_EINVAL, "eval_mc_exo: unknown stream provider%s");
-    if (reseed == OFFSIM_EXO_RESEED_EPISODE && rs->rng_kind == OFFSIM_STREAM_PHILOX)
-        return fail(OFFSIM_EUNSUPPORTED, "eval_mc_exo: OFFSIM_EXO_RESEED_EPISODE seeds default_rng(episode): the stream must be OFFSIM_STREAM_PCG64%s");
-    if (!out) return fail(OFFSIM_EINVAL, "eval_mc_exo: out is NULL%s");
-    if ((rc = check_evalmc_out("eval_mc_exo", out, gamma_pow, n_gamma_pow))) return rc;
-    if (out->ep_cap < 0 || out->trace_cap < 0) return fail(OFFSIM_EINVAL, "eval_mc_exo: negative ep_cap / trace_cap%s");
     if (td) {
         if ((td->mode != OFFSIM_TD_QLEARN && td->mode != OFFSIM_TD_EXPSARSA) || !td->q) return fail(OFFSIM_EINVAL, "eval_mc_exo: bad td mode or NULL q%s");
         if (prob_mode != OFFSIM_PROB_F64) return fail(OFFSIM_EINVAL, "eval_mc_exo: the learner drivers take an f64 pi (OFFSIM_PROB_F64)%s");
@@ -347,5 +426,43 @@ extern "C" int offsim_eval_mc_exo(const offsim_table *ts, const offsim_table *tx
             if (td) return exo_launch<PL, PROB, true>(ts, tx, rs, rx, pi, xa, gamma, gamma_pow, n_gamma_pow, max_episodes, out, tdv, waves, lds, stream);
         }
         return exo_launch<PL, PROB, false>(ts, tx, rs, rx, pi, xa, gamma, gamma_pow, n_gamma_pow, max_episodes, out, tdv, waves, lds, stream);
+    });
+}
+
+// ---- offsim_eval_mc_exo's learner drivers for L learners on the same S seeds in one launch, every learner on its own Q with any behaviour
+// policy of the reference (k_eval_mc_exo<.., TD, POP>, csrc/td_pop_exo.hpp); L = 1 is the single learner with a greedy behaviour
+extern "C" int offsim_eval_td_exo_pop(const offsim_table *ts, const offsim_table *tx, offsim_rollouts *rs, offsim_rollouts *rx, int32_t L, int32_t S,
+                                      const offsim_td_pop *pop, const int32_t *obs_of, int32_t n_obs, int32_t reseed, uint64_t episode0,
+                                      int64_t max_episodes, const offsim_evalmc_out *out, const offsim_exo_out *xout, void *stream) {
+    static const char *who = "eval_td_exo_pop";
+    if (!pop) return fail(OFFSIM_EINVAL, "%s: pop is NULL", who);
+    int rc = exo_check_common(who, ts, tx, rs, rx, obs_of, n_obs, reseed, out, pop->gamma_pow, pop->n_gamma_pow);
+    if (rc || (rc = check_td_pop(who, L, S, rs->R, pop))) return rc;
+    if (pop->td_cap < 0) return fail(OFFSIM_EINVAL, "%s: negative td_cap", who);
+    int waves = 0;
+    size_t lds = 0;
+    if ((rc = exo_launch_shape(ts, tx, n_obs, 8, true, &waves, &lds, true, who))) return rc;
+    if (rs->R == 0) return OFFSIM_OK;
+    TdPopExoArgs xa{};
+    xa.obs_of = obs_of;
+    xa.n_obs = n_obs;
+    xa.reseed = reseed;
+    xa.episode0 = episode0;
+    xa.xout.trace_row_x = xout ? xout->trace_row_x : nullptr;
+    xa.xout.last = xout ? xout->last : nullptr;
+    xa.S = S;
+    xa.alpha = pop->alpha;
+    xa.epsilon = pop->epsilon;
+    xa.gamma = pop->gamma;
+    xa.gamma_pow = pop->gamma_pow;
+    xa.behaviour = pop->behaviour;
+    xa.alpha_ep = pop->alpha_ep;
+    xa.epsilon_ep = pop->epsilon_ep;
+    xa.pi = pop->pi;
+    xa.pi_stride = pop->pi_stride;
+    const offsim_td td = td_of_pop(pop);
+    return with_plog(ts, [&](auto pl) -> int {
+        return exo_launch<decltype(pl), double, true, true>(ts, tx, rs, rx, nullptr, xa, 0.0, nullptr, pop->n_gamma_pow, max_episodes, out, td, waves, lds,
+                                                            stream);
     });
 }

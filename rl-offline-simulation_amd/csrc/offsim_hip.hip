@@ -914,6 +914,44 @@ __device__ __forceinline__ uint32_t mt_bounded(volatile uint32_t *mt, uint32_t &
     return v;
 }
 
+// The learner's own behaviour policy on its Q row `qs` (offsim4rl/agents/tabular.py), rebuilt in beh_lds [nA] before every step of
+// rollout r: the one definition for k_eval_mc (Q row of the slot) and k_eval_mc_exo (Q row of the observation, csrc/eval_exo.hpp).  Called
+// by the whole wavefront with td.behaviour != OFFSIM_BEHAVIOUR_FIXED; mt_lds / mt_pos: the rollout's copy of the tie stream.
+__device__ __forceinline__ void td_behaviour(const offsim_td &td, const double *qs, int nA, double *beh_lds, volatile uint32_t *mt_lds,
+                                             uint32_t &mt_pos, int lane, int r, int64_t ep, int64_t steps) {
+    double mx = qs[0];
+    for (int k = 1; k < nA; k++) mx = qs[k] > mx ? qs[k] : mx;
+    __builtin_amdgcn_s_waitcnt(0xc07f);
+    if (td.behaviour == OFFSIM_BEHAVIOUR_EPS_GREEDY) {
+        // epsilon_greedy_policy (tabular.py:24-32; epsilon = 0: greedy_policy, :11-16): epsilon / nA everywhere and
+        // 1 - epsilon + epsilon / nA at _random_argmax -- np.random.choice(np.where(x == np.max(x))[0]), tabular.py:4-5:
+        // one bounded integer from the tie stream when several actions hold the maximum, none otherwise
+        int n_max = 0;
+        for (int k = 0; k < nA; k++) n_max += qs[k] == mx ? 1 : 0;
+        uint32_t pick = 0;
+        if (n_max > 1 && td.tie_mt) pick = mt_bounded(mt_lds, mt_pos, lane, (uint32_t)n_max - 1u);
+        int best = 0, seen = 0;
+        for (int k = 0; k < nA; k++) {
+            if (qs[k] == mx) {
+                if ((uint32_t)seen == pick) best = k;
+                seen++;
+            }
+        }
+        const double eps = td.epsilon_ep ? td.epsilon_ep[ep < td.n_sched ? ep : td.n_sched - 1] : td.epsilon;
+        const double lo = eps / (double)nA, hi = 1.0 - eps + lo;
+        for (int k = lane; k < nA; k += WAVE) beh_lds[k] = k == best ? hi : lo;
+        if (lane == 0 && td.beh_arg && steps < td.td_cap) td.beh_arg[(int64_t)r * td.td_cap + steps] = best;
+    } else {
+        // soft_greedy_policy (tabular.py:18-22): uniform over np.isclose(Q[s], max) (rtol 1e-5, atol 1e-8)
+        const double tol = 1e-8 + 1e-5 * fabs(mx);
+        int n_close = 0;
+        for (int k = 0; k < nA; k++) n_close += fabs(qs[k] - mx) <= tol ? 1 : 0;
+        const double w = 1.0 / (double)n_close;
+        for (int k = lane; k < nA; k += WAVE) beh_lds[k] = fabs(qs[k] - mx) <= tol ? w : 0.0;
+    }
+    __builtin_amdgcn_s_waitcnt(0xc07f);
+}
+
 // ROWP = true: the row-policy mode (offsim_eval_mc_rows_policy) -- p_new is not pi[slot] but a per-row table: rp.p_next[g] after the
 // accepted grouped row g, rp.p_init[k] right after the reset that popped initial row k (a policy over observations asked at next_obs of
 // the accepted row, psrs.py:49-51, or at obs of the popped initial row, :32-37).  No pi block in LDS; rp.obs_row gets which row the
@@ -1042,39 +1080,7 @@ __global__ void __launch_bounds__(256, 4) k_eval_mc(offsim_table t, offsim_rollo
             const double gp = discount_at(gamma_pow, (uint64_t)n_gamma_pow, gamma, (uint64_t)tt);  // issued ahead of the step
             const PROB *p_step = ROWP ? (g_prev >= 0 ? p_next + (int64_t)g_prev * nA : p_init + (int64_t)k_init * nA) : pi_lds + (size_t)slot * nA;
             if (TD && td.behaviour != OFFSIM_BEHAVIOUR_FIXED) {
-                // the learner's own behaviour policy on its Q row (offsim4rl/agents/tabular.py), rebuilt in LDS before every step
-                const double *qs = q_lds + (size_t)slot * nA;
-                double mx = qs[0];
-                for (int k = 1; k < nA; k++) mx = qs[k] > mx ? qs[k] : mx;
-                __builtin_amdgcn_s_waitcnt(0xc07f);
-                if (td.behaviour == OFFSIM_BEHAVIOUR_EPS_GREEDY) {
-                    // epsilon_greedy_policy (tabular.py:24-32; epsilon = 0: greedy_policy, :11-16): epsilon / nA everywhere and
-                    // 1 - epsilon + epsilon / nA at _random_argmax -- np.random.choice(np.where(x == np.max(x))[0]), tabular.py:4-5:
-                    // one bounded integer from the tie stream when several actions hold the maximum, none otherwise
-                    int n_max = 0;
-                    for (int k = 0; k < nA; k++) n_max += qs[k] == mx ? 1 : 0;
-                    uint32_t pick = 0;
-                    if (n_max > 1 && td.tie_mt) pick = mt_bounded(mt_lds, mt_pos, lane, (uint32_t)n_max - 1u);
-                    int best = 0, seen = 0;
-                    for (int k = 0; k < nA; k++) {
-                        if (qs[k] == mx) {
-                            if ((uint32_t)seen == pick) best = k;
-                            seen++;
-                        }
-                    }
-                    const double eps = td.epsilon_ep ? td.epsilon_ep[ep < td.n_sched ? ep : td.n_sched - 1] : td.epsilon;
-                    const double lo = eps / (double)nA, hi = 1.0 - eps + lo;
-                    for (int k = lane; k < nA; k += WAVE) beh_lds[k] = k == best ? hi : lo;
-                    if (lane == 0 && td.beh_arg && steps < td.td_cap) td.beh_arg[(int64_t)r * td.td_cap + steps] = best;
-                } else {
-                    // soft_greedy_policy (tabular.py:18-22): uniform over np.isclose(Q[s], max) (rtol 1e-5, atol 1e-8)
-                    const double tol = 1e-8 + 1e-5 * fabs(mx);
-                    int n_close = 0;
-                    for (int k = 0; k < nA; k++) n_close += fabs(qs[k] - mx) <= tol ? 1 : 0;
-                    const double w = 1.0 / (double)n_close;
-                    for (int k = lane; k < nA; k += WAVE) beh_lds[k] = fabs(qs[k] - mx) <= tol ? w : 0.0;
-                }
-                __builtin_amdgcn_s_waitcnt(0xc07f);
+                td_behaviour(td, q_lds + (size_t)slot * nA, nA, beh_lds, mt_lds, mt_pos, lane, r, ep, steps);
                 p_step = (const PROB *)beh_lds;
             }
             StepResult s = psrs_step<PL, PROB>(t, seg_lds, perm_row, slot, cur_lds, p_step, reject_mode, 0u, rng, consumed);
@@ -1788,17 +1794,10 @@ extern "C" int offsim_eval_td(const offsim_table *t, offsim_rollouts *ro, const 
     });
 }
 
-// ---- offsim_eval_td for L learners on the same S seeds in one launch (k_eval_mc<.., TD, false, POP>, csrc/td_pop.hpp): every learner has its
-// own hyper-parameters, behaviour and target policy; the queue orders are the seeds', shared by all learners and only read.
-extern "C" int offsim_eval_td_pop(const offsim_table *t, offsim_rollouts *ro, int32_t L, int32_t S, const offsim_td_pop *pop, int32_t reject_mode,
-                                  int64_t max_episodes, const offsim_evalmc_out *out, void *stream) {
-    static const char *who = "eval_td_pop";
-    int rc = check_table(t);
-    if (rc) return rc;
-    if (!ro || ro->R < 0 || !pop || !out) return fail(OFFSIM_EINVAL, "%s: bad argument", who);
+// What the population entry points (offsim_eval_td_pop, offsim_eval_td_exo_pop) check about L, S, R = L * S and struct offsim_td_pop ...
+static int check_td_pop(const char *who, int32_t L, int32_t S, int64_t R, const offsim_td_pop *pop) {
     if (L < 1 || L > 65535 || S < 1) return fail(OFFSIM_EINVAL, "%s: L must be 1..65535 and S >= 1", who);
-    if (ro->R != 0 && (int64_t)ro->R != (int64_t)L * S) return fail(OFFSIM_EINVAL, "%s: ro->R must be L * S", who);
-    if ((rc = check_evalmc_out(who, out, pop->gamma_pow, pop->n_gamma_pow))) return rc;
+    if (R != 0 && R != (int64_t)L * S) return fail(OFFSIM_EINVAL, "%s: ro->R must be L * S", who);
     if ((pop->mode != OFFSIM_TD_QLEARN && pop->mode != OFFSIM_TD_EXPSARSA) || !pop->q) return fail(OFFSIM_EINVAL, "%s: bad td mode or NULL q", who);
     if (!pop->alpha || !pop->epsilon || !pop->gamma || !pop->behaviour || !pop->behaviour_host || !pop->pi || pop->pi_stride < 0 || pop->n_gamma_pow < 0)
         return fail(OFFSIM_EINVAL, "%s: a per-learner array is NULL (alpha, epsilon, gamma, behaviour and its host copy, pi)", who);
@@ -1808,8 +1807,11 @@ extern "C" int offsim_eval_td_pop(const offsim_table *t, offsim_rollouts *ro, in
     }
     if ((pop->alpha_ep || pop->epsilon_ep) && pop->n_sched <= 0) return fail(OFFSIM_EINVAL, "%s: schedules need n_sched > 0", who);
     if (pop->q_snap && (pop->snap_stride <= 0 || pop->snap_cap < 0)) return fail(OFFSIM_EINVAL, "%s: bad snapshot stride / capacity", who);
-    if (ro->R == 0) return OFFSIM_OK;
-    offsim_td td{};  // per rollout: the members of offsim_td as they are; per learner: filled in by the kernel from rp
+    return OFFSIM_OK;
+}
+// ... and the launch's offsim_td -- per rollout: the members of offsim_td as they are; per learner: filled in by the kernel from its arguments
+static offsim_td td_of_pop(const offsim_td_pop *pop) {
+    offsim_td td{};
     td.mode = pop->mode;
     td.q = pop->q;
     td.td_err = pop->td_err;
@@ -1820,6 +1822,20 @@ extern "C" int offsim_eval_td_pop(const offsim_table *t, offsim_rollouts *ro, in
     td.snap_stride = pop->snap_stride;
     td.tie_mt = pop->tie_mt;
     td.beh_arg = pop->beh_arg;
+    return td;
+}
+
+// ---- offsim_eval_td for L learners on the same S seeds in one launch (k_eval_mc<.., TD, false, POP>, csrc/td_pop.hpp): every learner has its
+// own hyper-parameters, behaviour and target policy; the queue orders are the seeds', shared by all learners and only read.
+extern "C" int offsim_eval_td_pop(const offsim_table *t, offsim_rollouts *ro, int32_t L, int32_t S, const offsim_td_pop *pop, int32_t reject_mode,
+                                  int64_t max_episodes, const offsim_evalmc_out *out, void *stream) {
+    static const char *who = "eval_td_pop";
+    int rc = check_table(t);
+    if (rc) return rc;
+    if (!ro || ro->R < 0 || !pop || !out) return fail(OFFSIM_EINVAL, "%s: bad argument", who);
+    if ((rc = check_evalmc_out(who, out, pop->gamma_pow, pop->n_gamma_pow)) || (rc = check_td_pop(who, L, S, ro->R, pop))) return rc;
+    if (ro->R == 0) return OFFSIM_OK;
+    const offsim_td td = td_of_pop(pop);
     TdPopArgs rp{};
     rp.S = S;
     rp.alpha = pop->alpha;

@@ -21,7 +21,7 @@ import torch
 from .. import _lib as L
 from ..table import RolloutState, TransitionTable, seed_streams, seeds_tensor, shuffle_queues
 from .rollout_io import (HOST_KEYS, _gamma_pow, _prob_mode, collect_host, episode_bound, host_result, population_result,  # noqa: F401
-                         population_state, rollout_outputs, seed_tiles, td_outputs, tie_stream)
+                         population_state, rollout_outputs, seed_tiles, td_outputs, td_population_launch, tie_stream)
 
 SHUFFLE_PER_ROLLOUT = "per_rollout"  # reset_sampler(seed_r) for every rollout r: the reference's meaning
 SHUFFLE_SHARED = "shared"            # one queue order (shuffle_seed) shared by all rollouts, per-rollout rejection streams
@@ -690,78 +690,12 @@ class BatchedPSRS:
         self._quiesce()
         self._orders_for_generic()
         t, dev, S = self.table, self.table.device, self.R
-        f64 = lambda x: np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float64)  # noqa: E731
-        per = {"alpha": np.atleast_1d(f64(alpha)), "gamma": np.atleast_1d(f64(gamma)), "epsilon": np.atleast_1d(f64(epsilon)),
-               "behaviour": np.atleast_1d(np.asarray(behaviour, dtype=np.int64))}
-        if any(v.ndim != 1 for v in per.values()):
-            raise ValueError("eval_td_population: alpha, gamma, behaviour and epsilon are scalars or [L]")
-        lens = {k: len(v) for k, v in per.items() if len(v) != 1}
-        pi_t = None if pi_slots is None else torch.as_tensor(pi_slots if isinstance(pi_slots, torch.Tensor) else np.ascontiguousarray(pi_slots), dtype=torch.float64)
-        if pi_t is not None:
-            if pi_t.dim() not in (2, 3) or tuple(pi_t.shape[-2:]) != (t.n_slots, t.nA):
-                raise ValueError(f"eval_td_population: pi_slots [n_slots,nA] or [L,n_slots,nA] expected, got {tuple(pi_t.shape)}")
-            if pi_t.dim() == 3:
-                lens["pi_slots"] = int(pi_t.shape[0])
-        q_t = None if q_slots is None else torch.as_tensor(q_slots if isinstance(q_slots, torch.Tensor) else np.ascontiguousarray(q_slots), dtype=torch.float64)
-        if q_t is not None:
-            if q_t.dim() not in (2, 3, 4) or tuple(q_t.shape[-2:]) != (t.n_slots, t.nA) or (q_t.dim() == 4 and q_t.shape[1] != S):
-                raise ValueError(f"eval_td_population: q_slots [n_slots,nA], [L,n_slots,nA] or [L,S,n_slots,nA] expected, got {tuple(q_t.shape)}")
-            if q_t.dim() > 2:
-                lens["q_slots"] = int(q_t.shape[0])
-        sched = {}
-        for k, x in (("alpha_ep", alpha_ep), ("epsilon_ep", epsilon_ep)):
-            if x is not None:
-                sched[k] = np.atleast_1d(f64(x))
-                if sched[k].ndim not in (1, 2) or sched[k].shape[-1] < 1:
-                    raise ValueError(f"eval_td_population: {k} [n_sched] or [L,n_sched] expected")
-                if sched[k].ndim == 2:
-                    lens[k] = sched[k].shape[0]
-        mt = None
-        if tie_mt is not None:
-            mt = tie_stream(tie_mt)
-            if mt.dim() != 3 or tuple(mt.shape[1:]) != (S, 625):
-                raise ValueError(f"eval_td_population: tie_mt [L,S,625] expected, got {tuple(mt.shape)}")
-            lens["tie_mt"] = int(mt.shape[0])
-        if len(set(lens.values())) > 1:
-            raise ValueError(f"eval_td_population: per-learner arguments of different lengths: {lens}")
-        n_l = next(iter(lens.values())) if lens else 1
-        if n_l < 1:
-            raise ValueError("eval_td_population: no learner")
-        R = n_l * S
-        beh_host = np.ascontiguousarray(np.broadcast_to(per["behaviour"], (n_l,)), dtype=np.int32)
-        dev_f64 = lambda a: torch.from_numpy(np.array(a, dtype=np.float64, order="C")).to(dev)  # noqa: E731  (a copy: broadcasts are read-only)
-        alpha_d, eps_d, gamma_d = (dev_f64(np.broadcast_to(per[k], (n_l,))) for k in ("alpha", "epsilon", "gamma"))
-        beh_d = torch.from_numpy(beh_host).to(dev)
-        n_sched = max([v.shape[-1] for v in sched.values()], default=0)
-        assert all(v.shape[-1] == n_sched for v in sched.values()), "alpha_ep and epsilon_ep cover the same episodes"
-        a_ep, e_ep = (dev_f64(np.broadcast_to(sched[k], (n_l, n_sched))) if k in sched else None for k in ("alpha_ep", "epsilon_ep"))
-        if pi_t is None:
-            pi_t = torch.full((t.n_slots, t.nA), 1.0 / t.nA, dtype=torch.float64)
-        pi_d = pi_t.to(dev).contiguous()
-        # the discount tables, one row per learner: each as eval_td builds it, the shorter ones (stationary) padded with their last entry
-        rows = [_gamma_pow(g, n_gamma_pow, dev, cap=t.N + 2) for g in np.broadcast_to(per["gamma"], (n_l,)).tolist()]
-        n_gp = max(r.numel() for r in rows)
-        gp = torch.stack([r if r.numel() == n_gp else torch.cat([r, r[-1:].expand(n_gp - r.numel())]) for r in rows]).contiguous()
-        n_episodes = episode_bound(n_episodes)
-        if q_t is None:
-            q = torch.zeros((R, t.n_slots, t.nA), dtype=torch.float64, device=dev)
-        else:
-            q_t = q_t.to(dev)
-            q = (q_t if q_t.dim() == 4 else q_t.reshape(-1, 1, t.n_slots, t.nA)).expand(n_l, S, t.n_slots, t.nA).reshape(R, t.n_slots, t.nA).contiguous().clone()
+        n_l, o, oc, pc, keep = td_population_launch("eval_td_population", dev, S, t.n_slots, t.nA, t.N, mode, alpha, gamma, behaviour, epsilon, pi_slots,
+                                                    q_slots, alpha_ep, epsilon_ep, tie_mt, n_gamma_pow, ep_cap, trace_cap, snap_cap, snap_stride)
         ro, copies = population_state(self.state, n_l)
-        o, oc = rollout_outputs(R, dev, ep_cap, trace_cap)
-        td_outputs(o, q, trace_cap, snap_cap, beh_arg=(beh_host == L.BEHAVIOUR_EPS_GREEDY).any())
-        if mt is not None:  # (a copy: the caller's states stay where they were)
-            mt = o["tie_mt"] = mt.to(dev).reshape(R, 625).contiguous().clone()
-        pc = L.TDPop(mode=int(mode), alpha=L.ptr(alpha_d), epsilon=L.ptr(eps_d), gamma=L.ptr(gamma_d), gamma_pow=L.ptr(gp), n_gamma_pow=n_gp,
-                     behaviour=L.ptr(beh_d), behaviour_host=beh_host.ctypes.data_as(C.POINTER(C.c_int32)), alpha_ep=L.ptr(a_ep), epsilon_ep=L.ptr(e_ep),
-                     n_sched=n_sched, pi=L.ptr(pi_d), pi_stride=t.n_slots * t.nA if pi_d.dim() == 3 else 0, q=L.ptr(q), td_err=L.ptr(o.get("td_err")),
-                     td_cap=trace_cap, q_snap=L.ptr(o.get("q_snap")), snap_cap=snap_cap, snap_stride=max(int(snap_stride), 1), tie_mt=L.ptr(mt),
-                     beh_arg=L.ptr(o.get("beh_arg")))
-        L.check(L.load().offsim_eval_td_pop(C.byref(t.c), C.byref(ro), n_l, S, C.byref(pc), self.reject_mode, int(n_episodes), C.byref(oc),
+        L.check(L.load().offsim_eval_td_pop(C.byref(t.c), C.byref(ro), n_l, S, C.byref(pc), self.reject_mode, int(episode_bound(n_episodes)), C.byref(oc),
                                             L.stream_ptr()))
-        o["q"] = q
-        return population_result(o, n_l, S, copies, (pi_d, gp, alpha_d, eps_d, gamma_d, beh_d, a_ep, e_ep), "k_eval_td_pop", state=True)
+        return population_result(o, n_l, S, copies, keep, "k_eval_td_pop", state=True)
 
     def scan_variant(self):
         """Name of the kernel eval_mc's fast path launches for this table and batch size (measurement label)."""

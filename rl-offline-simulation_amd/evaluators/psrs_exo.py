@@ -8,6 +8,8 @@ Both queue families reuse the ordinary device tables, shuffles and resets; the s
 Whole rollouts -- the reference's drivers evalMC_psrs / qlearn_psrs / expSARSA_psrs on a PSRS_Exo (evaluators/psrs.py hands them here) and
 many sampler seeds per launch -- run in offsim_eval_mc_exo (csrc/eval_exo.hpp): BatchedPSRSExo, evalmc_rollouts_exo.  The policy and Q are
 indexed by the observation o = o_combine_func(s, x); tabulate_obs lays that map out over the grid of state slots.
+BatchedPSRSExo.eval_td_population runs L learners on every seed in one launch (offsim_eval_td_exo_pop), each with any behaviour policy of
+the reference on its own Q; TDPopulation.run_exo (td_population.py) is its seed-tile driver.
 """
 import ctypes as C
 import numbers
@@ -18,7 +20,8 @@ import torch
 
 from .. import _lib as L
 from ..table import RolloutState, TransitionTable, seed_streams, seeds_tensor, shuffle_queues
-from .rollout_io import HOST_KEYS, _gamma_pow, _prob_mode, collect_host, episode_bound, host_result, rollout_outputs, seed_tiles, td_outputs
+from .rollout_io import (HOST_KEYS, _gamma_pow, _prob_mode, collect_host, episode_bound, host_result, population_result, population_state,
+                         rollout_outputs, seed_tiles, td_outputs, td_population_launch)
 
 
 def tabulate_obs(s_values, x_values, o_combine_func, n_rows):
@@ -138,6 +141,45 @@ class BatchedPSRSExo:
         alpha_ep: alpha per episode; snap_cap > 0: out["q_snap"] [R, snap_cap, n_obs, nA] = Q after every snap_stride-th step."""
         td = dict(mode=mode, alpha=alpha, q_obs=q_obs, behaviour=behaviour, alpha_ep=alpha_ep, snap_cap=int(snap_cap), snap_stride=snap_stride)
         return self._run(pi_obs, obs_of, gamma, n_episodes, reseed, episode0, ep_cap, trace_cap, n_gamma_pow, td)
+
+    # -- the learner drivers for L learners on this environment's R seeds, any behaviour policy on the learner's own Q, in one launch --
+    def eval_td_population(self, mode, alpha, gamma, obs_of, behaviour=L.BEHAVIOUR_FIXED, epsilon=0.0, pi_obs=None, q_obs=None, alpha_ep=None,
+                           epsilon_ep=None, n_episodes=None, reseed="episode", episode0=0, ep_cap=0, trace_cap=0, snap_cap=0, tie_mt=None,
+                           snap_stride=1, n_gamma_pow=4096):
+        """qlearn_psrs / expSARSA_psrs for L learners, each on every one of this environment's S = R rollouts (its seeds): L * S rollouts in
+        one launch that share the S queue orders of both families (include/offsim.h, offsim_eval_td_exo_pop).  behaviour (_lib.BEHAVIOUR_*):
+        FIXED rejects against pi_obs; EPS_GREEDY (epsilon 0: greedy) and SOFT_GREEDY act on the learner's own Q row of the current
+        observation, pi_obs then being only the target of expected SARSA.  alpha, gamma, behaviour and epsilon are each a scalar or [L];
+        pi_obs [n_obs,nA] or [L,n_obs,nA] (None: uniform) and q_obs [n_obs,nA], [L,...], [L,S,...] (None: zeros) in the compact rows of
+        obs_of [ns_slots, nx_slots] (tabulate_obs), whose largest entry + 1 is n_obs unless pi_obs / q_obs say more; alpha_ep / epsilon_ep
+        [n_sched] or [L,n_sched]; tie_mt [L,S,625] NumPy MT19937 states for ties between maxima (None: the first maximum).  L is the
+        common length of the per-learner arguments; L = 1 is the single learner.  reseed / episode0: eval_td's.
+        Returns eval_td's dict with [L, S, ...] leading dimensions (+ beh_arg, tie_mt where they apply); with BEHAVIOUR_FIXED entry [l, j]
+        is, bit for bit, what eval_td gives rollout j under learner l's setting.  It is a query, like BatchedPSRS.eval_td_population: it
+        runs on copies of the sampler state of both families (every learner of seed j sees the same queues and, with reseed "none", the
+        same stream state), and this environment's own cursors, rejection streams and current slots are left as they were; o["_state"]
+        holds where every learner's sampler stands afterwards (rng, cursor, init_cursor, cur_slot of the s family; *_x of the x family)."""
+        ts, tx, dev, S = self.ts, self.tx, self.ts.device, self.R
+        if reseed not in _RESEED:
+            raise ValueError(f"reseed must be 'episode' or 'none', got {reseed!r}")
+        ob = torch.as_tensor(np.ascontiguousarray(obs_of, dtype=np.int32) if not isinstance(obs_of, torch.Tensor) else obs_of)
+        ob = ob.to(device=dev, dtype=torch.int32).reshape(ts.n_slots, tx.n_slots).contiguous()
+        given = next((x for x in (pi_obs, q_obs) if x is not None), None)
+        n_obs = int(given.shape[-2]) if given is not None else max(int(ob.max()) + 1, 1)
+        n_l, o, oc, pc, keep = td_population_launch("eval_td_population", dev, S, n_obs, ts.nA, ts.N, mode, alpha, gamma, behaviour, epsilon, pi_obs, q_obs,
+                                                    alpha_ep, epsilon_ep, tie_mt, n_gamma_pow, ep_cap, trace_cap, snap_cap, snap_stride,
+                                                    names=("pi_obs", "q_obs", "n_obs"))
+        R = n_l * S
+        o["last"] = torch.full((R, 3), -1, dtype=torch.int32, device=dev)
+        if trace_cap:
+            o["trace_row_x"] = torch.full((R, trace_cap), -1, dtype=torch.int32, device=dev)
+        ro_s, cp_s = population_state(self.rs, n_l)
+        ro_x, cp_x = population_state(self.rx, n_l)
+        xo = L.ExoOut(trace_row_x=L.ptr(o.get("trace_row_x")), last=L.ptr(o["last"]))
+        L.check(L.load().offsim_eval_td_exo_pop(C.byref(ts.c), C.byref(tx.c), C.byref(ro_s), C.byref(ro_x), n_l, S, C.byref(pc), L.ptr(ob), n_obs,
+                                                _RESEED[reseed], int(episode0), int(episode_bound(n_episodes)), C.byref(oc), C.byref(xo), L.stream_ptr()))
+        copies = dict(cp_s, **{k + "_x": v for k, v in cp_x.items() if k != "rng"})
+        return population_result(o, n_l, S, copies, keep + (ob, cp_x["rng"]), "k_eval_td_exo_pop", state=True)
 
 
 def evalmc_rollouts_exo(env_or_tables, seeds, pi, gamma, obs_of=None, reseed="episode", n_episodes=None, tile=None):

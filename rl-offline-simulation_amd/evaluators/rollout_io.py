@@ -3,12 +3,15 @@
   rollout_outputs     the output dict of a launch and its struct offsim_evalmc_out (the one place that states dtypes, fills, shapes)
   td_outputs          the learner kernels' extras: td_err, beh_arg, q_snap
   tie_stream          a caller's MT19937 states as the int32 tensor the kernels read
+  td_population_launch   the per-learner arguments of a population of learners as struct offsim_td_pop, with its outputs
   population_state / population_result   a population launch's copies of the sampler state, and its dict as [n, S, ...]
   seed_tiles / collect_host / host_result   the loop over tiles of sampler seeds and the host arrays it returns
   episode_bound, _gamma_pow, _prob_mode     the episode limit, the discount table and the probability mode of a launch
 
-A leaf: it imports _lib, torch and NumPy only, so batched.py, psrs_exo.py and td_population.py all import it at module top.
+A leaf: it imports _lib, ctypes, torch and NumPy only, so batched.py, psrs_exo.py and td_population.py all import it at module top.
 """
+import ctypes as C
+
 import numpy as np
 import torch
 
@@ -99,6 +102,87 @@ def tie_stream(tie_mt, device=None):
     tensor that already is one comes back as itself, so a launch advances the caller's states in place."""
     mt = torch.as_tensor(np.ascontiguousarray(tie_mt).view(np.int32) if not isinstance(tie_mt, torch.Tensor) else tie_mt)
     return mt.to(device=device, dtype=torch.int32)
+
+
+def td_population_launch(who, device, S, rows, nA, n_log, mode, alpha, gamma, behaviour, epsilon, pi, q, alpha_ep, epsilon_ep, tie_mt, n_gamma_pow,
+                         ep_cap, trace_cap, snap_cap, snap_stride, names=("pi_slots", "q_slots", "n_slots")):
+    """The arguments of a launch of L learners on S seeds (offsim_eval_td_pop, offsim_eval_td_exo_pop), from what `who` -- a method
+    eval_td_population -- was given: alpha, gamma, behaviour (_lib.BEHAVIOUR_*) and epsilon a scalar or [L]; pi [rows,nA] or [L,rows,nA]
+    (None: uniform); q [rows,nA], [L,...], [L,S,...] or None (zeros); alpha_ep / epsilon_ep [n_sched] or [L,n_sched]; tie_mt [L,S,625] or
+    None.  L is the common length of the per-learner arguments (1 when every one is shared); lengths that disagree raise ValueError.
+    `rows`: the rows of pi / Q (state slots, or compact observation rows); n_log: the log's rows (an episode's longest); names: what the
+    messages call pi, q and rows.  Returns (L, output dict with q / tie_mt / the learner extras, struct offsim_evalmc_out, struct
+    offsim_td_pop, what the launch must keep alive)."""
+    dev = device
+    pi_name, q_name, rows_name = names
+    f64 = lambda x: np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float64)  # noqa: E731
+    per = {"alpha": np.atleast_1d(f64(alpha)), "gamma": np.atleast_1d(f64(gamma)), "epsilon": np.atleast_1d(f64(epsilon)),
+           "behaviour": np.atleast_1d(np.asarray(behaviour, dtype=np.int64))}
+    if any(v.ndim != 1 for v in per.values()):
+        raise ValueError(f"{who}: alpha, gamma, behaviour and epsilon are scalars or [L]")
+    lens = {k: len(v) for k, v in per.items() if len(v) != 1}
+    pi_t = None if pi is None else torch.as_tensor(pi if isinstance(pi, torch.Tensor) else np.ascontiguousarray(pi), dtype=torch.float64)
+    if pi_t is not None:
+        if pi_t.dim() not in (2, 3) or tuple(pi_t.shape[-2:]) != (rows, nA):
+            raise ValueError(f"{who}: {pi_name} [{rows_name},nA] or [L,{rows_name},nA] expected, got {tuple(pi_t.shape)}")
+        if pi_t.dim() == 3:
+            lens[pi_name] = int(pi_t.shape[0])
+    q_t = None if q is None else torch.as_tensor(q if isinstance(q, torch.Tensor) else np.ascontiguousarray(q), dtype=torch.float64)
+    if q_t is not None:
+        if q_t.dim() not in (2, 3, 4) or tuple(q_t.shape[-2:]) != (rows, nA) or (q_t.dim() == 4 and q_t.shape[1] != S):
+            raise ValueError(f"{who}: {q_name} [{rows_name},nA], [L,{rows_name},nA] or [L,S,{rows_name},nA] expected, got {tuple(q_t.shape)}")
+        if q_t.dim() > 2:
+            lens[q_name] = int(q_t.shape[0])
+    sched = {}
+    for k, x in (("alpha_ep", alpha_ep), ("epsilon_ep", epsilon_ep)):
+        if x is not None:
+            sched[k] = np.atleast_1d(f64(x))
+            if sched[k].ndim not in (1, 2) or sched[k].shape[-1] < 1:
+                raise ValueError(f"{who}: {k} [n_sched] or [L,n_sched] expected")
+            if sched[k].ndim == 2:
+                lens[k] = sched[k].shape[0]
+    mt = None
+    if tie_mt is not None:
+        mt = tie_stream(tie_mt)
+        if mt.dim() != 3 or tuple(mt.shape[1:]) != (S, 625):
+            raise ValueError(f"{who}: tie_mt [L,S,625] expected, got {tuple(mt.shape)}")
+        lens["tie_mt"] = int(mt.shape[0])
+    if len(set(lens.values())) > 1:
+        raise ValueError(f"{who}: per-learner arguments of different lengths: {lens}")
+    n_l = next(iter(lens.values())) if lens else 1
+    if n_l < 1:
+        raise ValueError(f"{who}: no learner")
+    R = n_l * S
+    beh_host = np.ascontiguousarray(np.broadcast_to(per["behaviour"], (n_l,)), dtype=np.int32)
+    dev_f64 = lambda a: torch.from_numpy(np.array(a, dtype=np.float64, order="C")).to(dev)  # noqa: E731  (a copy: broadcasts are read-only)
+    alpha_d, eps_d, gamma_d = (dev_f64(np.broadcast_to(per[k], (n_l,))) for k in ("alpha", "epsilon", "gamma"))
+    beh_d = torch.from_numpy(beh_host).to(dev)
+    n_sched = max([v.shape[-1] for v in sched.values()], default=0)
+    assert all(v.shape[-1] == n_sched for v in sched.values()), "alpha_ep and epsilon_ep cover the same episodes"
+    a_ep, e_ep = (dev_f64(np.broadcast_to(sched[k], (n_l, n_sched))) if k in sched else None for k in ("alpha_ep", "epsilon_ep"))
+    if pi_t is None:
+        pi_t = torch.full((rows, nA), 1.0 / nA, dtype=torch.float64)
+    pi_d = pi_t.to(dev).contiguous()
+    # the discount tables, one row per learner: each as eval_td builds it, the shorter ones (stationary) padded with their last entry
+    gp_rows = [_gamma_pow(g, n_gamma_pow, dev, cap=n_log + 2) for g in np.broadcast_to(per["gamma"], (n_l,)).tolist()]
+    n_gp = max(r.numel() for r in gp_rows)
+    gp = torch.stack([r if r.numel() == n_gp else torch.cat([r, r[-1:].expand(n_gp - r.numel())]) for r in gp_rows]).contiguous()
+    if q_t is None:
+        qd = torch.zeros((R, rows, nA), dtype=torch.float64, device=dev)
+    else:
+        q_t = q_t.to(dev)
+        qd = (q_t if q_t.dim() == 4 else q_t.reshape(-1, 1, rows, nA)).expand(n_l, S, rows, nA).reshape(R, rows, nA).contiguous().clone()
+    o, oc = rollout_outputs(R, dev, ep_cap, trace_cap)
+    td_outputs(o, qd, trace_cap, snap_cap, beh_arg=(beh_host == L.BEHAVIOUR_EPS_GREEDY).any())
+    if mt is not None:  # (a copy: the caller's states stay where they were)
+        mt = o["tie_mt"] = mt.to(dev).reshape(R, 625).contiguous().clone()
+    pc = L.TDPop(mode=int(mode), alpha=L.ptr(alpha_d), epsilon=L.ptr(eps_d), gamma=L.ptr(gamma_d), gamma_pow=L.ptr(gp), n_gamma_pow=n_gp,
+                 behaviour=L.ptr(beh_d), behaviour_host=beh_host.ctypes.data_as(C.POINTER(C.c_int32)), alpha_ep=L.ptr(a_ep), epsilon_ep=L.ptr(e_ep),
+                 n_sched=n_sched, pi=L.ptr(pi_d), pi_stride=rows * nA if pi_d.dim() == 3 else 0, q=L.ptr(qd), td_err=L.ptr(o.get("td_err")),
+                 td_cap=trace_cap, q_snap=L.ptr(o.get("q_snap")), snap_cap=snap_cap, snap_stride=max(int(snap_stride), 1), tie_mt=L.ptr(mt),
+                 beh_arg=L.ptr(o.get("beh_arg")))
+    o["q"] = qd
+    return n_l, o, oc, pc, (pi_d, gp, alpha_d, eps_d, gamma_d, beh_d, a_ep, e_ep, beh_host)
 
 
 def population_state(st, n_pop):

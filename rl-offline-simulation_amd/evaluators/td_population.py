@@ -9,6 +9,7 @@ per learner on the device.  Learners never interact: learner l on seed j is, bit
   TDPopulation(mode, alpha, gamma, epsilon, behaviour, pi, Q_init)   the settings, each a scalar or one value per learner
   TDPopulation.grid(mode, alpha=[..], epsilon=[..], gamma=[..])      their Cartesian product
   population.run(table, seeds, ...)                                  -> TDPopulationResult of device tensors
+  population.run_exo(env_or_tables, seeds, ...)                      the same on an exogenous-state log (PSRS_Exo), tables by observation
 """
 import itertools
 from dataclasses import dataclass, field
@@ -41,7 +42,8 @@ class TDPopulationResult:
     Q [L,S,nS,nA] by caller state id; Gs [L,S,ep_cap] the returns in episode order (entry n_ep of a row: the episode the end of the log
     cut short, as qlearn_psrs appends it); n_ep, steps, status [L,S]; curve_n / curve_mean / curve_var [L,ep_cap]: per learner and
     episode, over the seeds that completed that episode, their number, the mean return and its population variance (NaN where no seed
-    did); td_err [L,S,trace_cap] when the run was asked for the trace."""
+    did); td_err [L,S,trace_cap] when the run was asked for the trace; tie_mt [L,S,625] int32 (run_exo with tie streams): where every
+    rollout's MT19937 stream stands afterwards."""
     Q: torch.Tensor
     Gs: torch.Tensor
     n_ep: torch.Tensor
@@ -52,6 +54,7 @@ class TDPopulationResult:
     curve_n: torch.Tensor
     learners: list = field(default_factory=list)
     td_err: Optional[torch.Tensor] = None
+    tie_mt: Optional[torch.Tensor] = None
 
     def best(self, last=1):
         """The learner with the highest mean of its last `last` curve points that every seed reached (curve_n == S); points fewer
@@ -181,12 +184,86 @@ class TDPopulation:
                 parts[k].append(o[k])
             env.check_faults()
         res = {k: v[0] if len(v) == 1 else torch.cat(v, dim=1).contiguous() for k, v in parts.items()}
+        return self._result(res, self._q_by_state(table, res["q"], Q0), ep_cap)
+
+    def _result(self, res, Q, ep_cap):
+        """The TDPopulationResult of the concatenated tiles `res` ([L, S, ...]): offsim_td_curves over all seeds."""
+        n_l, S = res["n_ep"].shape
+        dev = res["n_ep"].device
         curve_n = torch.empty((n_l, ep_cap), dtype=torch.int64, device=dev)
         curve_mean, curve_var = (torch.empty((n_l, ep_cap), dtype=torch.float64, device=dev) for _ in range(2))
         L.check(L.load().offsim_td_curves(L.ptr(res["ep_g"]), L.ptr(res["n_ep"]), n_l, S, ep_cap, L.ptr(curve_n), L.ptr(curve_mean), L.ptr(curve_var),
                                           L.stream_ptr()))
-        return TDPopulationResult(Q=self._q_by_state(table, res["q"], Q0), Gs=res["ep_g"], n_ep=res["n_ep"], steps=res["steps"], status=res["status"],
-                                  curve_mean=curve_mean, curve_var=curve_var, curve_n=curve_n, learners=self.learners, td_err=res.get("td_err"))
+        return TDPopulationResult(Q=Q, Gs=res["ep_g"], n_ep=res["n_ep"], steps=res["steps"], status=res["status"], curve_mean=curve_mean,
+                                  curve_var=curve_var, curve_n=curve_n, learners=self.learners, td_err=res.get("td_err"), tie_mt=res.get("tie_mt"))
+
+    def run_exo(self, env_or_tables, seeds, obs_of=None, n_episodes=None, reseed="episode", tile=None, tie_mt=None, rejection="pcg64", trace_cap=0):
+        """Every learner on every seed of an exogenous-state log (PSRS_Exo: two queue families, tables indexed by the observation
+        o = o_combine_func(s, x)), with any behaviour policy of the reference on the learner's own Q; one learner is qlearn_psrs /
+        expSARSA_psrs with a greedy behaviour, which those drivers refuse on a PSRS_Exo.
+        env_or_tables: a PSRS_Exo -- pi and Q_init are then [nO,nA] (or [L,nO,nA]) tables BY OBSERVATION, compacted through env.obs_table --
+        or a pair (ts, tx) of TransitionTables with obs_of [ns_slots, nx_slots] (tabulate_obs) and pi / Q_init in its compact rows.
+        One reset_sampler of both families per tile of seeds, one launch per tile (BatchedPSRSExo.eval_td_population), then offsim_td_curves
+        over all seeds.  reseed = "episode": episode e of every rollout draws from default_rng(e), the reference's protocol (PCG64);
+        "none": every seed's own stream (`rejection`: "pcg64" or "philox"), the learners of a seed starting from the same state.
+        tile (None): the queue orders of BOTH families stay resident per seed, so it is resident_rollouts(ts, keyed=False) scaled by
+        bytes(ts) / (bytes(ts) + bytes(tx)) with rollout_resident_bytes(table, keyed=False) each, at least 1, at most S; it does not shrink
+        with L (the orders are the seeds', shared by all learners).  tie_mt: None (the first maximum, as run), or NumPy MT19937 states
+        [L,S,625], or one [625] every rollout starts from; the advanced states come back as result.tie_mt [L,S,625].
+        Returns a TDPopulationResult with Q [L,S,nO,nA] by observation (rows the slot grid has no observation for keep Q_init's values;
+        for a pair of tables: the compact rows)."""
+        from .psrs_exo import PSRS_Exo, BatchedPSRSExo
+        from .batched import rollout_resident_bytes, resident_rollouts
+        seeds = np.asarray(seeds, dtype=np.uint64)
+        S, n_l = len(seeds), self.L
+        if S < 1:
+            raise ValueError("TDPopulation.run_exo: no seed")
+        given = next((x for x in (self.Q_init, self.pi) if x is not None), None)
+        if isinstance(env_or_tables, PSRS_Exo):
+            ts, tx = env_or_tables.ts, env_or_tables.tx
+            nO = int(given.shape[-2]) if given is not None else int(env_or_tables.nO)
+            obs_of, ids = env_or_tables.obs_table(nO)
+        else:
+            ts, tx = env_or_tables
+            if obs_of is None:
+                raise ValueError("TDPopulation.run_exo: a pair of tables needs obs_of")
+            obs_of = np.ascontiguousarray(obs_of.cpu().numpy() if isinstance(obs_of, torch.Tensor) else obs_of, dtype=np.int32)
+            nO = int(given.shape[-2]) if given is not None else max(int(obs_of.max()) + 1, 1)
+            ids = np.arange(nO)
+        for k, x in (("pi", self.pi), ("Q_init", self.Q_init)):
+            if x is not None and x.shape[-2:] != (nO, ts.nA):
+                raise ValueError(f"TDPopulation.run_exo: {k} [nO,nA] = {(nO, ts.nA)} expected, got {x.shape}")
+        Q0 = np.zeros((nO, ts.nA)) if self.Q_init is None else self.Q_init
+        pi = np.full((nO, ts.nA), 1.0 / ts.nA) if self.pi is None else self.pi
+        n_ep = int(min(n_episodes if n_episodes is not None else ts.N0 + 1, ts.N0 + 1))
+        ep_cap = max(n_ep, 1)
+        a_const, e_const, a_tab, e_tab = self.tabulate(n_ep)
+        beh = np.array([_BEHAVIOUR[b] for b in self.behaviour], dtype=np.int32)
+        if tie_mt is not None:
+            tie_mt = tie_stream(tie_mt)
+            if tuple(tie_mt.shape) == (625,):
+                tie_mt = tie_mt.expand(n_l, S, 625)
+            if tuple(tie_mt.shape) != (n_l, S, 625):
+                raise ValueError(f"TDPopulation.run_exo: tie_mt [625] or [L,S,625] = {(n_l, S, 625)} expected, got {tuple(tie_mt.shape)}")
+        if tile is None:
+            n_res, per_s = resident_rollouts(ts, keyed=False)[:2]
+            tile = max(1, min(S, n_res * per_s // (per_s + rollout_resident_bytes(tx, keyed=False))))
+        keys = ["q", "ep_g", "n_ep", "steps", "status"] + (["td_err"] if trace_cap else []) + (["tie_mt"] if tie_mt is not None else [])
+        parts = {k: [] for k in keys}
+        for b, sd, env in seed_tiles(seeds, int(tile), lambda n: BatchedPSRSExo(ts, tx, n)):
+            env.reset_sampler(sd, rejection=rejection)
+            o = env.eval_td_population(self.mode, a_const, self.gamma, obs_of, beh, e_const, pi_obs=pi[..., ids, :], q_obs=Q0[..., ids, :], alpha_ep=a_tab,
+                                       epsilon_ep=e_tab, n_episodes=n_ep, reseed=reseed, ep_cap=ep_cap, trace_cap=int(trace_cap),
+                                       tie_mt=None if tie_mt is None else tie_mt[:, b:b + len(sd)])
+            for k in keys:
+                parts[k].append(o[k])
+            BatchedPSRS.check_faults()
+        res = {k: v[0] if len(v) == 1 else torch.cat(v, dim=1).contiguous() for k, v in parts.items()}
+        dev = res["q"].device
+        q0 = torch.from_numpy(np.ascontiguousarray(Q0, dtype=np.float64)).to(dev)
+        Q = (q0[:, None] if q0.dim() == 3 else q0[None, None]).expand(n_l, S, nO, ts.nA).contiguous().clone()
+        Q[:, :, torch.from_numpy(np.asarray(ids, dtype=np.int64)).to(dev)] = res["q"]
+        return self._result(res, Q, ep_cap)
 
     @staticmethod
     def _q_by_state(table, q_slots, Q0):
