@@ -504,6 +504,48 @@ int offsim_eval_td_exo_pop(const offsim_table *ts, const offsim_table *tx, offsi
                            const offsim_td_pop *pop, const int32_t *obs_of, int32_t n_obs, int32_t reseed, uint64_t episode0,
                            int64_t max_episodes, const offsim_evalmc_out *out, const offsim_exo_out *xout, void *stream);
 
+/* offsim_eval_queue: whole rollouts on QueueEvaluator (offsim4rl/evaluators/queue_evaluator.py:90-131) under the reference's tabular drivers
+ * -- evalMC (td = NULL; offsim4rl/agents/tabular.py:247-270), qlearn (:71-139) and expSARSA (:141-191) by td->mode -- for all rollouts in ONE
+ * launch (csrc/eval_queue.hpp).  The queues are keyed by (z, a), the agent draws its own action and the simulator pops the head of queue
+ * (z, A): no rejection, one row per step.
+ *   t    the table grouped by the COMPOSITE slot z * nA + a (z counted from the smallest state), so t->n_slots = nZ * nA_actions; z_next and
+ *        init_slot hold BASE slots z' * nA (what evaluators/queue_evaluator.py: BatchedQueueEvaluator builds).  ro->cursor [R, n_slots],
+ *        ro->cur_slot [R] the base slot of the current state (-1: none), ro->perm / init_perm as everywhere.
+ *   pi   [nZ, nA] f64 by state (the row of base slot b starts at b), or NULL for Q-learning with a behaviour on the learner's own Q.
+ *   ro->rng   the ACTION stream of each rollout: PCG64 rows as offsim_seed_streams writes them (tabular.py:75: default_rng(seed)).
+ *        OFFSIM_STREAM_PHILOX is refused with OFFSIM_EUNSUPPORTED and nothing is stepped: its double lies in (0, 1], and u = 1.0 would
+ *        select action nA.
+ * Per step: p = pi[z], or the behaviour policy on Q[z] (td->behaviour, td->epsilon / epsilon_ep: offsim_eval_td's rules, one definition on
+ *   the device); A = Generator.choice(nA, p=p) (tabular.py:120, :172, :259) -- c_k = c_{k-1} + p_k sequentially in f64 from 0,
+ *   cdf_k = c_k / c_{nA-1}, u = (next64 >> 11) * 2^-53, A the first k with cdf_k > u: exactly one draw per step; then the head of queue
+ *   (z, A) is popped (queue_evaluator.py:121-131).  A pair (z, A) that was never logged: OFFSIM_ST_KEYERROR (self.queues[z, a] raises); the
+ *   queue at its end: OFFSIM_ST_EXHAUSTED (:125-126); state and cursors stay in both cases, the draw is consumed.  A row p without a cdf
+ *   entry above u (NaN, all zeros) draws A = nA: OFFSIM_ST_KEYERROR.
+ * td: the update of offsim_eval_td on Q[z, A] with Q[z'] (tabular.py:123-126 / :175-178, the same arithmetic and order), q [R, nZ, nA],
+ *   td_err, alpha_ep, q_snap [R, snap_cap, nZ, nA] / snap_stride / snap_cap, beh_arg as there.  The reference's tabular drivers do not
+ *   survive exhaustion (None flows on into Q[None]); the rule here is the *_psrs drivers': the rollout stops with the status, evalMC drops
+ *   the partial episode and appends its length (n_len = n_ep + 1), the learner drivers store the partial return past the completed ones.
+ * Ties of the epsilon-greedy arg max: td->tie_mt = NULL the first maximum; td->tie_mt [R,625] the rollout's MT19937 stream, read, advanced
+ *   and written back (offsim_eval_td); tie_reseed_episode = 1 (needs td->tie_mt, episode0 >= 0): at the start of episode e of this call the
+ *   stream is re-initialised as np.random.seed(episode0 + e) does (tabular.py:114, :166; mt[0] = seed, mt[i] = 1812433253 * (mt[i-1] ^
+ *   (mt[i-1] >> 30)) + i, position 624, the seed taken modulo 2^32) -- for every behaviour, so td->tie_mt comes back as the global stream
+ *   the reference leaves.
+ * out: offsim_eval_mc's; cand = steps; trace_pop [R, trace_cap] holds the ACTION drawn at every step, the last, unserved one of a rollout
+ *   that stopped with OFFSIM_ST_KEYERROR / OFFSIM_ST_EXHAUSTED included (at index steps).  out_obs_row [R] (optional): where env.s comes
+ *   from when the loop stops, the convention of offsim_eval_mc_rows_policy.
+ * On exit cursors, init_cursor, cur_slot, the action stream (the state after the last draw), q and tie_mt are written back: a second call
+ *   continues the first.
+ * LDS per workgroup: per rollout the cursors (n_slots * 4), Q (n_slots * 8), the behaviour row (nA * 8) and the tie stream (2496 bytes)
+ *   (the last three with td), shared pi (n_slots * 8, when given) and seg_off; 4 rollouts per workgroup, then 2, then 1 while the carve
+ *   exceeds 64 KiB, one rollout up to 160 KiB, beyond that OFFSIM_EUNSUPPORTED.
+ * OFFSIM_EINVAL: t->nA != nA_actions, t->n_slots % nA_actions != 0, NULL ro / rollout state / out / required outputs / q, pi = NULL where a
+ *   policy is read, a bad mode / behaviour / snapshot stride / tie_reseed_episode, schedules without n_sched, negative capacities.
+ * Argument validation happens before any HIP call; ro->R = 0 launches nothing. */
+int offsim_eval_queue(const offsim_table *t, offsim_rollouts *ro, int32_t nA_actions,
+                      const double *pi /* [nZ,nA] or NULL with a Q-dependent behaviour */, double gamma, const double *gamma_pow,
+                      int64_t n_gamma_pow, int64_t max_episodes, const offsim_evalmc_out *out, const offsim_td *td /* NULL: evalMC */,
+                      int32_t tie_reseed_episode, int64_t episode0, int32_t *out_obs_row, void *stream);
+
 /* Fast path of evalMC_psrs for a fixed tabular policy (the headline scan).
  * offsim_compile_policy folds psrs.py:53-57 for policy pi [n_slots,nA] f64 into one 64-bit key per grouped row:
  *   key = T << 11 | done << 10 | z_next_slot,  T = floor(2^53 * pi[z][a]/p_log[a]/max_a'(pi[z][a']/p_log[a'])),

@@ -1870,6 +1870,9 @@ extern "C" int offsim_td_curves(const double *ep_g, const int64_t *n_ep, int32_t
 // ---- whole rollouts on PSRS_Exo: evalMC_psrs / qlearn_psrs / expSARSA_psrs over two queue families (csrc/eval_exo.hpp) ----
 #include "eval_exo.hpp"
 
+// ---- whole rollouts on QueueEvaluator: the tabular drivers evalMC / qlearn / expSARSA over (z, a)-keyed queues (csrc/eval_queue.hpp) ----
+#include "eval_queue.hpp"
+
 // ------------------------------------------------------------------------------------------------
 // Fast evalMC scan: compiled-policy keys + LDS candidate windows (scan_win.hpp)
 // ------------------------------------------------------------------------------------------------
