@@ -546,6 +546,33 @@ int offsim_eval_queue(const offsim_table *t, offsim_rollouts *ro, int32_t nA_act
                       int64_t n_gamma_pow, int64_t max_episodes, const offsim_evalmc_out *out, const offsim_td *td /* NULL: evalMC */,
                       int32_t tie_reseed_episode, int64_t episode0, int32_t *out_obs_row, void *stream);
 
+/* offsim_eval_queue_pop: the learner drivers of offsim_eval_queue (qlearn, expSARSA; tabular.py:71-191) for a population of L learners on the
+ * same S seeds in ONE launch: what offsim_eval_td_pop is to offsim_eval_td, on QueueEvaluator (queue_evaluator.py:90-131).  Every learner of
+ * a seed sees the same queues and starts from the same action stream, so differences between learners are paired.
+ *   t, nA_actions, max_episodes, out, tie_reseed_episode, episode0, out_obs_row [L * S]: offsim_eval_queue's.
+ *   ro->R = L * S, learner-major: rollout r = l * S + j is learner l on seed j.  ro->rng (the ACTION streams, OFFSIM_STREAM_PCG64;
+ *   OFFSIM_STREAM_PHILOX is refused with OFFSIM_EUNSUPPORTED: its double lies in (0, 1]), cursor [R, n_slots], init_cursor and cur_slot are
+ *   [R] rows (the caller's S rows replicated L times), advanced and written back per rollout.  ro->perm / ro->init_perm hold S orders, not
+ *   R: rollout r reads row j (stride 0: one shared order; NULL: table order).  The kernel only reads them.
+ *   pop: struct offsim_td_pop as offsim_eval_td_pop takes it, with nZ * nA in the place of n_slots * nA: q [L * S, nZ, nA], pi [L, nZ, nA]
+ *   with pi_stride = nZ * nA or one table with pi_stride = 0, q_snap [L * S, snap_cap, nZ, nA]; alpha, epsilon, gamma, behaviour
+ *   (+ behaviour_host), gamma_pow [L, n_gamma_pow], alpha_ep / epsilon_ep [L, n_sched], td_err / beh_arg [L * S, td_cap], tie_mt [L * S, 625]
+ *   or NULL (first maximum) unchanged.  pop->pi may be NULL only for OFFSIM_TD_QLEARN with no OFFSIM_BEHAVIOUR_FIXED learner in behaviour_host.
+ * Per step and per learner: p, the draw cdf_k = c_k / c_{nA-1} against u, the pop, the update, the tie stream and tie_reseed_episode are
+ *   offsim_eval_queue's, word for word (one definition on the device).
+ * Identity: rollout l * S + j equals, in every output bit and in the state it leaves, offsim_eval_queue's learner driver run alone with
+ *   learner l's setting from seed j's state, order and action stream -- for EVERY behaviour (unlike on PSRS_Exo, the single form has them
+ *   all).  The loop is the same code: k_eval_queue's learner instance under a population index (csrc/td_pop_queue.hpp).
+ * LDS per workgroup: offsim_eval_queue's learner carve; 4 / 2 / 1 rollouts per workgroup against 64 KiB, one rollout up to 160 KiB, beyond
+ *   that OFFSIM_EUNSUPPORTED.  A workgroup holds rollouts of one learner: grid = L * ceil(S / rollouts per workgroup).
+ * Argument validation happens before any HIP call -- everything offsim_eval_queue checks about the table, n_slots % nA, the rollout state,
+ * the provider, the outputs, the capacities, tie_reseed_episode in {0, 1} (needs pop->tie_mt and episode0 >= 0) and the LDS size; everything
+ * offsim_eval_td_pop checks about L (1..65535), S >= 1, R = L * S, the per-learner arrays, behaviour_host, the schedules and the snapshot
+ * stride: OFFSIM_EINVAL unless said otherwise --; ro->R = 0 launches nothing. */
+int offsim_eval_queue_pop(const offsim_table *t, offsim_rollouts *ro, int32_t nA_actions, int32_t L, int32_t S, const offsim_td_pop *pop,
+                          int64_t max_episodes, const offsim_evalmc_out *out, int32_t tie_reseed_episode, int64_t episode0,
+                          int32_t *out_obs_row, void *stream);
+
 /* Fast path of evalMC_psrs for a fixed tabular policy (the headline scan).
  * offsim_compile_policy folds psrs.py:53-57 for policy pi [n_slots,nA] f64 into one 64-bit key per grouped row:
  *   key = T << 11 | done << 10 | z_next_slot,  T = floor(2^53 * pi[z][a]/p_log[a]/max_a'(pi[z][a']/p_log[a'])),

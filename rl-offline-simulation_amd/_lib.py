@@ -256,6 +256,8 @@ SIGNATURES = {
                                          _i32, _i32, C.c_uint64, _i64, C.POINTER(EvalMCOut), C.POINTER(ExoOut), _vp]),
     "offsim_eval_queue": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), _i32, _vp, C.c_double, _vp, _i64, _i64, C.POINTER(EvalMCOut),
                                     C.POINTER(TD), _i32, _i64, _vp, _vp]),
+    "offsim_eval_queue_pop": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), _i32, _i32, _i32, C.POINTER(TDPop), _i64, C.POINTER(EvalMCOut), _i32,
+                                        _i64, _vp, _vp]),
     "offsim_compile_policy": (C.c_int, [C.POINTER(Table), _vp, _vp, _vp]),
     "offsim_eval_mc_keys_kernel": (C.c_char_p, [_i32, _i32]),
     "offsim_compile_digests": (C.c_int, [C.POINTER(Table), _vp, _i32, _vp, _vp]),

@@ -27,7 +27,10 @@
 //   [Q per wave (TD): waves * n f64][pi (when given): n f64][behaviour row per wave (TD): waves * nA f64][seg_off: n + 1 u32]
 //   [cursors per wave: waves * n u32][tie stream per wave (TD): waves * 624 u32]
 //
-// Included by offsim_hip.hip behind eval_exo.hpp: check_table, check_evalmc_out, td_behaviour, discount_at and allow_big_lds are that file's.
+// Many learners per launch (offsim_eval_queue_pop): the POP instance below, arguments and index rules in csrc/td_pop_queue.hpp.
+//
+// Included by offsim_hip.hip behind eval_exo.hpp: check_table, check_evalmc_out, check_td_pop, td_of_pop, td_behaviour, discount_at and
+// allow_big_lds are that file's.
 #pragma once
 
 // init_genrand(seed) of MT19937 into the rollout's LDS copy; every lane runs the recurrence, lane i % 64 stores word i
@@ -64,12 +67,34 @@ struct QueueArgs {
     int32_t *obs_row;
 };
 
-template <bool TD>
+// POP = true (with TD): a population of L tabular learners on the same S seeds (offsim_eval_queue_pop; arguments and index rules in
+// csrc/td_pop_queue.hpp).  The instance overwrites its per-launch hyper-parameters -- td.alpha / epsilon / behaviour / the schedule rows,
+// gamma, gamma_pow, pi -- with its workgroup's learner's before anything reads them; rollout r = l * S + j reads queue orders j.  The LDS
+// carve is the learner carve above.  The POP instance takes its own argument struct, so the kernel arguments of the other two are what they were.
+#include "td_pop_queue.hpp"
+template <bool POP>
+using QueueKernelArgs = std::conditional_t<POP, QueuePopArgs, QueueArgs>;
+
+template <bool TD, bool POP = false>
 __global__ void __launch_bounds__(256, 4) k_eval_queue(offsim_table t, offsim_rollouts ro, const double *__restrict__ pi, double gamma,
                                                     const double *__restrict__ gamma_pow, int64_t n_gamma_pow, int64_t max_episodes,
-                                                    offsim_evalmc_out out, offsim_td td, QueueArgs qa) {
+                                                    offsim_evalmc_out out, offsim_td td, QueueKernelArgs<POP> qa) {
+    static_assert(!POP || TD, "a population is a population of learners");
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const int waves = blockDim.x / WAVE;
+    int pop_l = 0, pop_nb = 1;  // POP: this workgroup's learner, workgroups per learner
+    if constexpr (POP) {
+        pop_nb = (qa.S + waves - 1) / waves;
+        pop_l = blockIdx.x / pop_nb;
+        td.alpha = qa.alpha[pop_l];
+        td.epsilon = qa.epsilon[pop_l];
+        td.behaviour = qa.behaviour[pop_l];
+        td.alpha_ep = qa.alpha_ep ? qa.alpha_ep + (int64_t)pop_l * td.n_sched : nullptr;
+        td.epsilon_ep = qa.epsilon_ep ? qa.epsilon_ep + (int64_t)pop_l * td.n_sched : nullptr;
+        gamma = qa.gamma[pop_l];
+        gamma_pow = qa.gamma_pow + (int64_t)pop_l * n_gamma_pow;
+        pi = qa.pi ? qa.pi + (int64_t)pop_l * qa.pi_stride : nullptr;
+    }
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE), lane = threadIdx.x & (WAVE - 1);  // uniform -> SGPR
     const int n = t.n_slots, nA = t.nA;
     double *q_lds = (double *)lds_raw + (TD ? (size_t)wave * n : 0);
@@ -82,8 +107,15 @@ __global__ void __launch_bounds__(256, 4) k_eval_queue(offsim_table t, offsim_ro
         for (int i = threadIdx.x; i < n; i += blockDim.x) pi_lds[i] = pi[i];
     for (int i = threadIdx.x; i <= n; i += blockDim.x) seg_lds[i] = t.seg_off[i];
     __syncthreads();
-    const int r = blockIdx.x * waves + wave;
-    if (r >= ro.R) return;
+    int r = blockIdx.x * waves + wave;
+    int ord = r;  // POP: the queue orders rollout r walks
+    if constexpr (POP) {
+        ord = __builtin_amdgcn_readfirstlane((blockIdx.x - pop_l * pop_nb) * waves + wave);
+        if (ord >= qa.S) return;
+        r = __builtin_amdgcn_readfirstlane(pop_l * qa.S + ord);
+    } else {
+        if (r >= ro.R) return;
+    }
     uint32_t *cur_glb = ro.cursor + (int64_t)r * n;
     for (int s = lane; s < n; s += WAVE) cur_lds[s] = cur_glb[s];
     uint32_t mt_pos = 624u;
@@ -98,8 +130,8 @@ __global__ void __launch_bounds__(256, 4) k_eval_queue(offsim_table t, offsim_ro
     const U128 inc = stream_row_inc(ro.rng, r);
     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): cursors, Q and the tie stream visible to the whole wave
 
-    const uint32_t *perm_row = ro.perm ? ro.perm + (int64_t)r * ro.perm_stride : nullptr;
-    const uint32_t *init_row = ro.init_perm ? ro.init_perm + (int64_t)r * ro.init_stride : nullptr;
+    const uint32_t *perm_row = ro.perm ? ro.perm + (int64_t)(POP ? ord : r) * ro.perm_stride : nullptr;
+    const uint32_t *init_row = ro.init_perm ? ro.init_perm + (int64_t)(POP ? ord : r) * ro.init_stride : nullptr;
     uint32_t ic = ro.init_cursor[r];
     int b = __builtin_amdgcn_readfirstlane(ro.cur_slot[r]);  // base slot z * nA of the current state
     int64_t ep = 0, n_len = 0, steps = 0;
@@ -269,22 +301,23 @@ static size_t queue_lds_bytes(int waves, int64_t n, int64_t nA, bool have_pi, bo
            (size_t)waves * n * 4 + (td ? (size_t)waves * 624 * 4 : 0);
 }
 
-template <bool TD>
+template <bool TD, bool POP = false>
 static int queue_launch(const offsim_table *t, offsim_rollouts *ro, const double *pi, double gamma, const double *gamma_pow, int64_t n_gamma_pow,
-                        int64_t max_episodes, const offsim_evalmc_out *out, const offsim_td &td, const QueueArgs &qa, int waves, size_t lds,
+                        int64_t max_episodes, const offsim_evalmc_out *out, const offsim_td &td, const QueueKernelArgs<POP> &qa, int waves, size_t lds,
                         void *stream) {
-    if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_eval_queue<TD>), (int)lds));
-    const unsigned grid = (unsigned)((ro->R + waves - 1) / waves);
-    hipLaunchKernelGGL((k_eval_queue<TD>), dim3(grid), dim3(waves * WAVE), lds, (hipStream_t)stream, *t, *ro, pi, gamma, gamma_pow, n_gamma_pow,
+    if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_eval_queue<TD, POP>), (int)lds));
+    unsigned grid = (unsigned)((ro->R + waves - 1) / waves);
+    if constexpr (POP) grid = (unsigned)(ro->R / qa.S) * (unsigned)((qa.S + waves - 1) / waves);  // a workgroup holds rollouts of one learner
+    hipLaunchKernelGGL((k_eval_queue<TD, POP>), dim3(grid), dim3(waves * WAVE), lds, (hipStream_t)stream, *t, *ro, pi, gamma, gamma_pow, n_gamma_pow,
                        max_episodes, *out, td, qa);
     LAUNCH_CHECK();
     return OFFSIM_OK;
 }
 
-extern "C" int offsim_eval_queue(const offsim_table *t, offsim_rollouts *ro, int32_t nA_actions, const double *pi, double gamma,
-                                 const double *gamma_pow, int64_t n_gamma_pow, int64_t max_episodes, const offsim_evalmc_out *out,
-                                 const offsim_td *td, int32_t tie_reseed_episode, int64_t episode0, int32_t *out_obs_row, void *stream) {
-    static const char *who = "eval_queue";
+// what offsim_eval_queue and offsim_eval_queue_pop check alike, in offsim_eval_queue's order: the table and its key, ro, the action stream's
+// provider, out, the capacities, the learner (td; NULL: evalMC) and the tie mode ...
+static int queue_check(const char *who, const offsim_table *t, const offsim_rollouts *ro, int32_t nA_actions, const double *gamma_pow,
+                       int64_t n_gamma_pow, const offsim_evalmc_out *out, const offsim_td *td, int32_t tie_reseed_episode, int64_t episode0) {
     int rc = check_table(t);
     if (rc) return rc;
     if (t->N0 > 0 && (!t->init_slot || !t->init_orig)) return fail(OFFSIM_EINVAL, "%s: table without its init rows", who);
@@ -311,13 +344,32 @@ extern "C" int offsim_eval_queue(const offsim_table *t, offsim_rollouts *ro, int
     } else if (tie_reseed_episode) {
         return fail(OFFSIM_EINVAL, "%s: tie_reseed_episode without a learner", who);
     }
-    if (!pi && !(td && td->behaviour != OFFSIM_BEHAVIOUR_FIXED && td->mode == OFFSIM_TD_QLEARN))
-        return fail(OFFSIM_EINVAL, "%s: pi is NULL (only Q-learning with a behaviour on the learner's own Q runs without one)", who);
+    return OFFSIM_OK;
+}
+
+// ... and the launch shape: 4 rollouts per workgroup, halved until the carve fits 64 KiB; up to 160 KiB with one rollout; beyond: refused
+static int queue_launch_shape(const char *who, const offsim_table *t, bool have_pi, bool td, int *waves_out, size_t *lds_out) {
     if (t->n_slots > 40960) return fail(OFFSIM_EUNSUPPORTED, "%s: cursors, policy and Q table exceed 160 KiB of LDS", who);  // (keeps the sums in range)
     int waves = 4;
-    while (waves > 1 && queue_lds_bytes(waves, t->n_slots, t->nA, pi != nullptr, td != nullptr) > 64 * 1024) waves >>= 1;
-    const size_t lds = queue_lds_bytes(waves, t->n_slots, t->nA, pi != nullptr, td != nullptr);
+    while (waves > 1 && queue_lds_bytes(waves, t->n_slots, t->nA, have_pi, td) > 64 * 1024) waves >>= 1;
+    const size_t lds = queue_lds_bytes(waves, t->n_slots, t->nA, have_pi, td);
     if (lds > 160 * 1024) return fail(OFFSIM_EUNSUPPORTED, "%s: cursors, policy and Q table exceed 160 KiB of LDS", who);
+    *waves_out = waves;
+    *lds_out = lds;
+    return OFFSIM_OK;
+}
+
+extern "C" int offsim_eval_queue(const offsim_table *t, offsim_rollouts *ro, int32_t nA_actions, const double *pi, double gamma,
+                                 const double *gamma_pow, int64_t n_gamma_pow, int64_t max_episodes, const offsim_evalmc_out *out,
+                                 const offsim_td *td, int32_t tie_reseed_episode, int64_t episode0, int32_t *out_obs_row, void *stream) {
+    static const char *who = "eval_queue";
+    int rc = queue_check(who, t, ro, nA_actions, gamma_pow, n_gamma_pow, out, td, tie_reseed_episode, episode0);
+    if (rc) return rc;
+    if (!pi && !(td && td->behaviour != OFFSIM_BEHAVIOUR_FIXED && td->mode == OFFSIM_TD_QLEARN))
+        return fail(OFFSIM_EINVAL, "%s: pi is NULL (only Q-learning with a behaviour on the learner's own Q runs without one)", who);
+    int waves = 0;
+    size_t lds = 0;
+    if ((rc = queue_launch_shape(who, t, pi != nullptr, td != nullptr, &waves, &lds))) return rc;
     if (ro->R == 0) return OFFSIM_OK;
     offsim_td tdv;
     memset(&tdv, 0, sizeof(tdv));
@@ -328,4 +380,41 @@ extern "C" int offsim_eval_queue(const offsim_table *t, offsim_rollouts *ro, int
     qa.obs_row = out_obs_row;
     if (td) return queue_launch<true>(t, ro, pi, gamma, gamma_pow, n_gamma_pow, max_episodes, out, tdv, qa, waves, lds, stream);
     return queue_launch<false>(t, ro, pi, gamma, gamma_pow, n_gamma_pow, max_episodes, out, tdv, qa, waves, lds, stream);
+}
+
+// ---- offsim_eval_queue's learner drivers for L learners on the same S seeds in one launch (k_eval_queue<TD, POP>, csrc/td_pop_queue.hpp): every
+// learner has its own hyper-parameters, behaviour and target policy; the queue orders are the seeds', shared by all learners and only read.
+extern "C" int offsim_eval_queue_pop(const offsim_table *t, offsim_rollouts *ro, int32_t nA_actions, int32_t L, int32_t S, const offsim_td_pop *pop,
+                                     int64_t max_episodes, const offsim_evalmc_out *out, int32_t tie_reseed_episode, int64_t episode0,
+                                     int32_t *out_obs_row, void *stream) {
+    static const char *who = "eval_queue_pop";
+    if (!pop) return fail(OFFSIM_EINVAL, "%s: pop is NULL", who);
+    const offsim_td td = td_of_pop(pop);
+    int rc = queue_check(who, t, ro, nA_actions, pop->gamma_pow, pop->n_gamma_pow, out, &td, tie_reseed_episode, episode0);
+    if (rc || (rc = check_td_pop(who, L, S, ro->R, pop, true))) return rc;
+    if (!pop->pi) {  // (behaviour_host has been validated)
+        bool fixed = false;
+        for (int32_t l = 0; l < L; l++) fixed = fixed || pop->behaviour_host[l] == OFFSIM_BEHAVIOUR_FIXED;
+        if (fixed || pop->mode != OFFSIM_TD_QLEARN)
+            return fail(OFFSIM_EINVAL, "%s: pi is NULL (only Q-learning with a behaviour on every learner's own Q runs without one)", who);
+    }
+    int waves = 0;
+    size_t lds = 0;
+    if ((rc = queue_launch_shape(who, t, pop->pi != nullptr, true, &waves, &lds))) return rc;
+    if (ro->R == 0) return OFFSIM_OK;
+    QueuePopArgs qa{};
+    qa.tie_reseed = tie_reseed_episode;
+    qa.episode0 = (uint32_t)episode0;
+    qa.obs_row = out_obs_row;
+    qa.S = S;
+    qa.alpha = pop->alpha;
+    qa.epsilon = pop->epsilon;
+    qa.gamma = pop->gamma;
+    qa.gamma_pow = pop->gamma_pow;
+    qa.behaviour = pop->behaviour;
+    qa.alpha_ep = pop->alpha_ep;
+    qa.epsilon_ep = pop->epsilon_ep;
+    qa.pi = pop->pi;
+    qa.pi_stride = pop->pi_stride;
+    return queue_launch<true, true>(t, ro, nullptr, 0.0, nullptr, pop->n_gamma_pow, max_episodes, out, td, qa, waves, lds, stream);
 }

@@ -1794,12 +1794,13 @@ extern "C" int offsim_eval_td(const offsim_table *t, offsim_rollouts *ro, const 
     });
 }
 
-// What the population entry points (offsim_eval_td_pop, offsim_eval_td_exo_pop) check about L, S, R = L * S and struct offsim_td_pop ...
-static int check_td_pop(const char *who, int32_t L, int32_t S, int64_t R, const offsim_td_pop *pop) {
+// What the population entry points (offsim_eval_td_pop, offsim_eval_td_exo_pop, offsim_eval_queue_pop) check about L, S, R = L * S and struct offsim_td_pop ...
+// (pi_optional: offsim_eval_queue_pop, which decides itself whether a NULL pi serves its learners)
+static int check_td_pop(const char *who, int32_t L, int32_t S, int64_t R, const offsim_td_pop *pop, bool pi_optional = false) {
     if (L < 1 || L > 65535 || S < 1) return fail(OFFSIM_EINVAL, "%s: L must be 1..65535 and S >= 1", who);
     if (R != 0 && R != (int64_t)L * S) return fail(OFFSIM_EINVAL, "%s: ro->R must be L * S", who);
     if ((pop->mode != OFFSIM_TD_QLEARN && pop->mode != OFFSIM_TD_EXPSARSA) || !pop->q) return fail(OFFSIM_EINVAL, "%s: bad td mode or NULL q", who);
-    if (!pop->alpha || !pop->epsilon || !pop->gamma || !pop->behaviour || !pop->behaviour_host || !pop->pi || pop->pi_stride < 0 || pop->n_gamma_pow < 0)
+    if (!pop->alpha || !pop->epsilon || !pop->gamma || !pop->behaviour || !pop->behaviour_host || (!pop->pi && !pi_optional) || pop->pi_stride < 0 || pop->n_gamma_pow < 0)
         return fail(OFFSIM_EINVAL, "%s: a per-learner array is NULL (alpha, epsilon, gamma, behaviour and its host copy, pi)", who);
     for (int32_t l = 0; l < L; l++) {
         const int32_t b = pop->behaviour_host[l];

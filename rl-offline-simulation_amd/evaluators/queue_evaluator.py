@@ -7,6 +7,8 @@ pop one" rule: offsim_group_by_state / offsim_shuffle_queues / offsim_env_set_st
 Whole rollouts -- the reference's tabular drivers evalMC / qlearn / expSARSA (offsim4rl/agents/tabular.py), which draw the action
 themselves and pop one row per step -- run in offsim_eval_queue (csrc/eval_queue.hpp), one launch: BatchedQueueEvaluator.eval_mc /
 eval_td, evalmc_rollouts_queue for many sampler seeds, and the drop-ins evalMC_queue / qlearn_queue / expSARSA_queue on a QueueEvaluator.
+Many learners on the same seeds in one launch (offsim_eval_queue_pop, csrc/td_pop_queue.hpp): BatchedQueueEvaluator.eval_td_population,
+driven over seed tiles by TDPopulation.run_queue (evaluators/td_population.py).
 """
 import ctypes as C
 import os
@@ -18,7 +20,8 @@ from .. import _lib as L
 from ..spaces import is_discrete
 from ..table import TransitionTable, gather_rows
 from .psrs import BatchedPSRS, SHUFFLE_PER_ROLLOUT, _behaviour_kind, _schedule
-from .rollout_io import HOST_KEYS, _gamma_pow, collect_host, episode_bound, host_result, rollout_outputs, seed_tiles, td_outputs, tie_stream
+from .rollout_io import (HOST_KEYS, _gamma_pow, collect_host, episode_bound, host_result, population_result, population_state, rollout_outputs,
+                         seed_tiles, td_outputs, td_population_launch, tie_stream)
 
 
 class BatchedQueueEvaluator:
@@ -142,6 +145,42 @@ class BatchedQueueEvaluator:
         td = dict(mode=mode, alpha=alpha, q=q, behaviour=behaviour, epsilon=epsilon, alpha_ep=alpha_ep, epsilon_ep=epsilon_ep, snap_cap=int(snap_cap),
                   snap_stride=snap_stride, tie=tie, episode0=episode0)
         return self._run(pi, gamma, n_episodes, ep_cap, trace_cap, n_gamma_pow, td)
+
+    def eval_td_population(self, mode, alpha, gamma, behaviour=L.BEHAVIOUR_FIXED, epsilon=0.0, pi=None, q=None, alpha_ep=None, epsilon_ep=None,
+                           tie=None, episode0=0, n_episodes=None, ep_cap=0, trace_cap=0, snap_cap=0, snap_stride=1, n_gamma_pow=4096, state=False):
+        """eval_td for L learners, each on every one of this environment's S = R rollouts (its sampler seeds and action streams): L * S
+        rollouts in one launch that share the S queue orders (include/offsim.h, offsim_eval_queue_pop).  alpha, gamma, behaviour
+        (_lib.BEHAVIOUR_*) and epsilon are each a scalar or [L]; pi [nZ,nA] or [L,nZ,nA] by state row (state_rows; None: uniform);
+        q [nZ,nA], [L,...], [L,S,...] or None (zeros); alpha_ep / epsilon_ep [n_sched] or [L,n_sched].  L is the common length of the
+        per-learner arguments (1 when every one is shared); lengths that disagree raise ValueError.  mode is one value for the launch.
+        tie: None / "first" the first maximum; "episode": every rollout's stream restarts as np.random.seed(episode0 + e) at the start of
+        episode e; [L,S,625] MT19937 states (copied: the caller's stay where they were).  out["tie_mt"] [L,S,625] is where the streams stand.
+        Returns eval_td's dict with [L, S, ...] leading dimensions; entry [l, j] is, bit for bit, what eval_td gives rollout j under learner
+        l's setting, for every behaviour.  It is a query: it runs on copies of the rollout state (every learner of seed j sees the same
+        queues and starts from the same action stream), and this environment's own cursors, action streams and current slots are left as
+        they were; with `state`, out["_state"] holds where every learner's rollouts stand afterwards (rng, cursor, init_cursor, cur_slot)."""
+        if self.nZ is None:
+            raise L.OffsimError("the one-launch queue drivers need dense state ids (this log's ids were compacted to ranks)")
+        env, t = self.env, self.table
+        env._quiesce()
+        env._orders_for_generic()
+        dev, S, nZ, nA = t.device, self.R, self.nZ, self.nA
+        by_episode = isinstance(tie, str) and tie == "episode"
+        if isinstance(tie, str) and tie not in ("episode", "first"):
+            raise ValueError(f"eval_td_population: tie must be None, 'first', 'episode' or [L,S,625] states, got {tie!r}")
+        n_l, o, oc, pc, keep = td_population_launch("eval_td_population", dev, S, nZ, nA, t.N, mode, alpha, gamma, behaviour, epsilon, pi, q, alpha_ep,
+                                                    epsilon_ep, None if isinstance(tie, str) else tie, n_gamma_pow, ep_cap, trace_cap, snap_cap,
+                                                    snap_stride, names=("pi", "q", "nZ"))
+        R = n_l * S
+        if by_episode:
+            mt = o["tie_mt"] = torch.zeros((R, 625), dtype=torch.int32, device=dev)
+            mt[:, 624] = 624
+            pc.tie_mt = L.ptr(mt)
+        o["obs_row"] = torch.full((R,), -(1 << 31), dtype=torch.int32, device=dev)
+        ro, copies = population_state(env.state, n_l)
+        L.check(L.load().offsim_eval_queue_pop(C.byref(t.c), C.byref(ro), nA, n_l, S, C.byref(pc), int(episode_bound(n_episodes)), C.byref(oc),
+                                               1 if by_episode else 0, int(episode0), L.ptr(o["obs_row"]), L.stream_ptr()))
+        return population_result(o, n_l, S, copies, keep, "k_eval_queue_pop", state=state)
 
     def reset(self, mask=None):
         return self.env.reset(mask)

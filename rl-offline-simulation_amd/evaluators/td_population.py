@@ -10,6 +10,7 @@ per learner on the device.  Learners never interact: learner l on seed j is, bit
   TDPopulation.grid(mode, alpha=[..], epsilon=[..], gamma=[..])      their Cartesian product
   population.run(table, seeds, ...)                                  -> TDPopulationResult of device tensors
   population.run_exo(env_or_tables, seeds, ...)                      the same on an exogenous-state log (PSRS_Exo), tables by observation
+  population.run_queue(env_or_arrays, seeds, ...)                    the same on the queue simulator (QueueEvaluator), tables by state
 """
 import itertools
 from dataclasses import dataclass, field
@@ -263,6 +264,78 @@ class TDPopulation:
         q0 = torch.from_numpy(np.ascontiguousarray(Q0, dtype=np.float64)).to(dev)
         Q = (q0[:, None] if q0.dim() == 3 else q0[None, None]).expand(n_l, S, nO, ts.nA).contiguous().clone()
         Q[:, :, torch.from_numpy(np.asarray(ids, dtype=np.int64)).to(dev)] = res["q"]
+        return self._result(res, Q, ep_cap)
+
+    def run_queue(self, env_or_arrays, seeds, n_episodes=None, action_seeds=None, tie="episode", episode0=0, tile=None, trace_cap=0):
+        """Every learner on every seed of the queue simulator (QueueEvaluator: queues keyed by (z, a), the agent draws its own action;
+        qlearn / expSARSA of offsim4rl/agents/tabular.py:71-191), the baseline run() on PSRS is compared against.
+        env_or_arrays: a QueueEvaluator, or the columns (z, a, r, z_next, done, p_log, t0) BatchedQueueEvaluator takes.  pi / Q_init are
+        [nS,nA] or [L,nS,nA] tables indexed by the state as the reference does (pi None: uniform).  Rollout (l, j) shuffles its queues
+        with seeds[j] and draws its actions from default_rng(action_seeds[j]) (default: seeds): all learners of a seed see the same queues
+        and start from the same action stream, so comparisons are paired.  One reset_sampler + set_action_seeds and one launch per tile of
+        seeds (BatchedQueueEvaluator.eval_td_population), then offsim_td_curves over all seeds.  tile (None):
+        default_tile(table, S, SHUFFLE_PER_ROLLOUT, keyed=False), as run -- the orders are the seeds', so it does not shrink with L.
+        tie: "episode" (the reference: ties between maximal Q values are broken with a stream restarted as np.random.seed(episode0 + e) at
+        every episode e), "first" (the first maximum), or NumPy MT19937 states [625] (every rollout starts from it) / [L,S,625].
+        Returns a TDPopulationResult with Q [L,S,nS,nA] by caller state id (rows without a state keep Q_init's values), tie_mt [L,S,625]
+        whenever a stream ran, td_err with trace_cap.  OFFSIM_ST_KEYERROR / _EXHAUSTED do not raise: they are in result.status."""
+        from .queue_evaluator import BatchedQueueEvaluator, QueueEvaluator
+        seeds = np.asarray(seeds, dtype=np.uint64)
+        S, n_l = len(seeds), self.L
+        if S < 1:
+            raise ValueError("TDPopulation.run_queue: no seed")
+        action_seeds = seeds if action_seeds is None else np.asarray(action_seeds, dtype=np.uint64)
+        if len(action_seeds) != S:
+            raise ValueError("TDPopulation.run_queue: one action seed per sampler seed (action_seeds)")
+        if isinstance(env_or_arrays, QueueEvaluator):
+            arrays, probe, nS = env_or_arrays._arrays, env_or_arrays._impl, int(env_or_arrays.nS)
+        else:
+            arrays = tuple(env_or_arrays)
+            probe, nS = BatchedQueueEvaluator(*arrays, R=1), None
+        if probe.nZ is None:
+            raise L.OffsimError("the one-launch queue drivers need dense state ids (this log's ids were compacted to ranks)")
+        t, nZ, nA = probe.table, probe.nZ, probe.nA
+        given = next((x for x in (self.Q_init, self.pi) if x is not None), None)
+        nS = int(given.shape[-2]) if given is not None else nZ if nS is None else nS
+        for k, x in (("pi", self.pi), ("Q_init", self.Q_init)):
+            if x is not None and x.shape[-2:] != (nS, nA):
+                raise ValueError(f"TDPopulation.run_queue: {k} [nS,nA] = {(nS, nA)} expected, got {x.shape}")
+        Q0 = np.zeros((nS, nA)) if self.Q_init is None else self.Q_init
+        rows = lambda x, fill: probe.state_rows(x, fill) if x.ndim == 2 else np.stack([probe.state_rows(v, fill) for v in x])  # noqa: E731
+        pi_rows, q_rows = None if self.pi is None else rows(self.pi, np.nan), rows(Q0, 0.0)
+        n_ep = int(min(n_episodes if n_episodes is not None else t.N0 + 1, t.N0 + 1))
+        ep_cap = max(n_ep, 1)
+        a_const, e_const, a_tab, e_tab = self.tabulate(n_ep)
+        beh = np.array([_BEHAVIOUR[b] for b in self.behaviour], dtype=np.int32)
+        if not isinstance(tie, str):
+            tie = tie_stream(tie)
+            if tuple(tie.shape) == (625,):
+                tie = tie.expand(n_l, S, 625)
+            if tuple(tie.shape) != (n_l, S, 625):
+                raise ValueError(f"TDPopulation.run_queue: tie_mt [625] or [L,S,625] = {(n_l, S, 625)} expected, got {tuple(tie.shape)}")
+        elif tie not in ("episode", "first"):
+            raise ValueError(f"TDPopulation.run_queue: tie must be 'episode', 'first' or MT19937 states, got {tie!r}")
+        if tile is None:
+            tile = default_tile(t, S, SHUFFLE_PER_ROLLOUT, keyed=False)
+        keys = ["q", "ep_g", "n_ep", "steps", "status"] + (["td_err"] if trace_cap else []) + (["tie_mt"] if not (isinstance(tie, str) and tie == "first") else [])
+        parts = {k: [] for k in keys}
+        for b, sd, env in seed_tiles(seeds, int(tile), lambda n: BatchedQueueEvaluator(*arrays, R=n)):
+            env.reset_sampler(sd)
+            env.set_action_seeds(action_seeds[b:b + len(sd)])
+            o = env.eval_td_population(self.mode, a_const, self.gamma, beh, e_const, pi=pi_rows, q=q_rows, alpha_ep=a_tab, epsilon_ep=e_tab,
+                                       tie=tie if isinstance(tie, str) else tie[:, b:b + len(sd)], episode0=episode0, n_episodes=n_ep, ep_cap=ep_cap,
+                                       trace_cap=int(trace_cap))
+            for k in keys:
+                parts[k].append(o[k])
+            BatchedPSRS.check_faults()
+        res = {k: v[0] if len(v) == 1 else torch.cat(v, dim=1).contiguous() for k, v in parts.items()}
+        # rows_to_state on the device: row i of the table's states goes to row z_lo + i of Q0's copy (NumPy's wrap for a negative state)
+        dev = res["q"].device
+        q0 = torch.from_numpy(np.ascontiguousarray(Q0, dtype=np.float64)).to(dev)
+        Q = (q0[:, None] if q0.dim() == 3 else q0[None, None]).expand(n_l, S, nS, nA).contiguous().clone()
+        last = {(probe.z_lo + i) % nS: i for i in range(nZ) if -nS <= probe.z_lo + i < nS}
+        if last:
+            Q[:, :, torch.tensor(list(last.keys()), dtype=torch.int64, device=dev)] = res["q"][:, :, torch.tensor(list(last.values()), dtype=torch.int64, device=dev)]
         return self._result(res, Q, ep_cap)
 
     @staticmethod
