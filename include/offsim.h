@@ -863,6 +863,47 @@ int offsim_vector_collect_ppo_pop(const offsim_table *t, offsim_rollouts *ro, co
                                   int32_t L, int32_t E, int32_t prob_mode, int32_t reject_mode, int64_t T, int32_t max_episode_steps,
                                   const offsim_collect_state *st, const offsim_collect_out *out, const offsim_collect_ppo_out *ppo, void *stream);
 
+/* ---- the same collection on QueueEvaluator (VectorQueueEvaluator.collect / collect_ppo / collect_ppo_population) -------------------
+ * The loop of the reference's PPOAgent on a QueueEvaluator (offsim4rl/agents/ppo.py:258-279 on offsim4rl/evaluators/queue_evaluator.py:
+ * 77-88): the agent draws its own action from its policy at the current observation, and the simulator pops the head of queue (z, a).
+ * offsim_queue_collect is offsim_vector_collect with that step in the place of PSRS.step; offsim_queue_collect_ppo and
+ * offsim_queue_collect_ppo_pop add what offsim_vector_collect_ppo and offsim_vector_collect_ppo_pop add.  The structs are theirs; the table
+ * and `ro` are offsim_eval_queue's: grouped by the composite slot (z - z_lo) * nA + a, cur_slot / z_next / init_slot hold BASE slots
+ * b = (z - z_lo) * nA, n_slots % nA == 0, nA_actions = t->nA, and ro->rng holds every environment's ACTION stream, OFFSIM_STREAM_PCG64
+ * only (a Philox row: OFFSIM_EUNSUPPORTED, as offsim_eval_queue).  There is no prob_mode and no reject_mode.
+ * Per step, for an environment with a state (0 <= b, b + nA <= n_slots; a state outside the table: OFFSIM_ST_KEYERROR):
+ *   1. the critic, then the policy p at the current observation, in offsim_vector_collect's forms.  OFFSIM_COLLECT_MLP: offsim_policy_mlp's
+ *      bits.  OFFSIM_COLLECT_ROWS: p_next / p_init [N,nA] in caller order.  OFFSIM_COLLECT_TABULAR: pi [n_slots / nA, nA] indexed by the
+ *      STATE (row b / nA), as offsim_eval_queue's.  For ROWS and TABULAR pol->x_dtype names the tables' element type, OFFSIM_F32 or
+ *      OFFSIM_F64.  The row is widened exactly to f64; probs [T,R,nA] records the f32 value;
+ *   2. A = Generator.choice(nA, p=p) as offsim_eval_queue draws it: c_k = c_{k-1} + p_k in f64 from 0, cdf_k = c_k / c_{nA-1},
+ *      u = (next64 >> 11) * 2^-53 from the environment's stream (one draw per asked step), A = the first k with cdf_k > u;
+ *   3. the pop: the head of segment b + A through perm and the cursor.  No k with cdf_k > u (a row of NaN or zeros) or an empty segment:
+ *      OFFSIM_ST_KEYERROR; the cursor at its end: OFFSIM_ST_EXHAUSTED.  Either way the environment stops for the rest of the launch with
+ *      state, observation and cursor as they were; the draw stays consumed;
+ *   4. records, ep_t, terminated / truncated and the reset: offsim_vector_collect's.  logp is taken at the drawn action, which is the served
+ *      row's logged action by construction.
+ * out_action [T,R] i32: the action drawn at every asked step, the unserved last one included (nA: none drawn); -1 where nothing was asked.
+ * On exit the stream row is the state after the last draw; cursors, cur_slot, init_cursor and st are written back as offsim_vector_collect
+ * does, so the call mixes with offsim_step_batch on the composite slot and with offsim_eval_queue.
+ * Limits: nA <= 16 for every form (beyond: OFFSIM_EUNSUPPORTED); the networks' floats as offsim_vector_collect[_ppo]'s; the workgroup's LDS
+ * -- [actor | pi as f64][critic][16 f64 + 16 f32 + 2 activation rows per environment], 8 environments -- at most 160 KiB.  There is no LDS
+ * bound on n_slots outside the TABULAR form: cursors stay in global memory.
+ * offsim_queue_collect_ppo_pop: L learners of E environments each, learner-major, grid (ceil(E / 8), L), stacked networks, MLP actors with
+ * MLP critics only -- offsim_vector_collect_ppo_pop's rules, and every environment equals offsim_queue_collect_ppo with its learner's
+ * networks bit for bit.
+ * Argument validation happens before any HIP call; T = 0 or R = 0 launches nothing (row / flags / out_action may then be NULL). */
+int offsim_queue_collect(const offsim_table *t, offsim_rollouts *ro, int32_t nA_actions, const offsim_collect_policy *pol, int64_t T,
+                         int32_t max_episode_steps, const offsim_collect_state *st, const offsim_collect_out *out, int32_t *out_action,
+                         void *stream);
+int offsim_queue_collect_ppo(const offsim_table *t, offsim_rollouts *ro, int32_t nA_actions, const offsim_collect_policy *pol,
+                             const offsim_collect_value *val, int64_t T, int32_t max_episode_steps, const offsim_collect_state *st,
+                             const offsim_collect_out *out, int32_t *out_action, const offsim_collect_ppo_out *ppo, void *stream);
+int offsim_queue_collect_ppo_pop(const offsim_table *t, offsim_rollouts *ro, int32_t nA_actions, const offsim_collect_policy *pol,
+                                 const offsim_collect_value *val, int32_t L, int32_t E, int64_t T, int32_t max_episode_steps,
+                                 const offsim_collect_state *st, const offsim_collect_out *out, int32_t *out_action,
+                                 const offsim_collect_ppo_out *ppo, void *stream);
+
 /* offsim_ppo_advantages: GAE-lambda advantages and rewards-to-go over step-major [T,E] records, with the path rules of the reference's
  * agent, and spinup's advantage normalisation (spinup PPOBuffer.finish_path / get, driven by offsim4rl/agents/ppo.py:106-158; E
  * environments = E MPI processes of local_steps_per_epoch = T).  Per environment e, over its valid steps t (flags & OFFSIM_COLLECT_SERVED):

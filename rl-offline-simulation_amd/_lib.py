@@ -296,6 +296,12 @@ SIGNATURES = {
                                     _vp, _vp]),
     "offsim_vector_collect_ppo_pop": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), C.POINTER(CollectPolicy), C.POINTER(CollectValue), _i32, _i32,
                                                 _i32, _i32, _i64, _i32, C.POINTER(CollectState), C.POINTER(CollectOut), C.POINTER(CollectPPOOut), _vp]),
+    "offsim_queue_collect": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), _i32, C.POINTER(CollectPolicy), _i64, _i32, C.POINTER(CollectState),
+                                       C.POINTER(CollectOut), _vp, _vp]),
+    "offsim_queue_collect_ppo": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), _i32, C.POINTER(CollectPolicy), C.POINTER(CollectValue), _i64, _i32,
+                                           C.POINTER(CollectState), C.POINTER(CollectOut), _vp, C.POINTER(CollectPPOOut), _vp]),
+    "offsim_queue_collect_ppo_pop": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), _i32, C.POINTER(CollectPolicy), C.POINTER(CollectValue), _i32,
+                                               _i32, _i64, _i32, C.POINTER(CollectState), C.POINTER(CollectOut), _vp, C.POINTER(CollectPPOOut), _vp]),
     "offsim_ppo_advantages_pop": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, C.c_double, C.c_double, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "offsim_ppo_epoch_log": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "offsim_ppo_epoch_log_pop": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),

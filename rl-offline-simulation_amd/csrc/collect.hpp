@@ -134,6 +134,115 @@ __device__ __forceinline__ float collect_value(const CollectValue &V, const floa
     }
 }
 
+// ---- k_collect's blocks as functions, for k_collect_queue (collect_queue.hpp): what a step records, the reset, the state written back ----
+// (KA: the kernel's arguments, CollectKArgs<VF> or a struct derived from it; k_collect itself: see the note above it)
+
+// The records of a step at which nothing is asked (no state, or stopped earlier in this launch): nothing served, zeros.
+template <int VF, typename KA>
+__device__ __forceinline__ void collect_dead_step(const KA &A, int64_t o, int nA, int64_t ob, int lane) {
+    if (lane == 0) {
+        A.out.row[o] = -1;
+        A.out.flags[o] = 0;
+    }
+    if (A.out.probs)
+        for (int a = lane; a < nA; a += WAVE) A.out.probs[o * nA + a] = 0.0f;
+    if (A.out.obs) wave_copy_row((unsigned char *)A.out.obs + o * ob, nullptr, ob, lane);
+    if constexpr (VF != COLLECT_VF_NONE)
+        if (lane == 0) A.V.rec.value[o] = A.V.rec.logp[o] = 0.0f;
+}
+
+// The records of a step that was asked and not served (None or KeyError): obs and probs stay as recorded.
+template <int VF, typename KA>
+__device__ __forceinline__ void collect_unserved_step(const KA &A, int64_t o, int lane) {
+    if (lane == 0) {
+        A.out.row[o] = -1;
+        A.out.flags[o] = 0;
+        if constexpr (VF != COLLECT_VF_NONE) A.V.rec.value[o] = A.V.rec.logp[o] = 0.0f;
+    }
+}
+
+// A served step, row g of the grouped table (done / z_next: its columns): the PPO records (v: the critic at the observation asked at;
+// logp of action `act`, or with act < 0 of the row's logged action t.a[g], from the logits or from pn), the step's record, ep_t, and
+// the reset at terminated / truncated (k_env_reset's logic).  The environment's state is the caller's registers.
+template <int FORM, typename XT, int VF, bool DRAWN, typename PROB, typename KA>
+__device__ __forceinline__ void collect_served_step(const offsim_table &t, const KA &A, const float *v_lds, float *act_lds, const uint32_t *init_row,
+                                                    int64_t o, int64_t r, int lane, int nA, int g, bool done, int32_t z_next, int act, float v,
+                                                    const float *logits, const PROB *pn, int &slot, uint32_t &ic, int32_t &ep_t, int32_t &xrow,
+                                                    bool &alive, bool &live, bool &moved, bool &none, int &status) {
+    if constexpr (VF != COLLECT_VF_NONE) {  // the PPO records of a served step: v(obs), logp of the served action (lane 0)
+        if (lane == 0) {
+            int a;
+            if constexpr (DRAWN) a = act;
+            else a = t.a[g];
+            A.V.rec.value[o] = v;
+            if constexpr (FORM == OFFSIM_COLLECT_MLP) A.V.rec.logp[o] = pmlp_logp(logits, nA, a);
+            else A.V.rec.logp[o] = logf((float)pn[a]);
+        }
+    }
+    // 3. the record, 4. the reset at terminated / truncated
+    const int32_t row = t.orig_idx[g];
+    ep_t++;
+    const bool term = done, trunc = A.max_ep > 0 && ep_t >= A.max_ep;
+    uint32_t fl = OFFSIM_COLLECT_SERVED | (term ? OFFSIM_COLLECT_TERMINATED : 0u) | (trunc ? OFFSIM_COLLECT_TRUNCATED : 0u);
+    if constexpr (VF != COLLECT_VF_NONE) {  // v(next_obs) of the served row, before a reset replaces the observation (spinup's bootstrap)
+        if (trunc && !term && A.V.rec.v_trunc) {
+            const float vt = collect_value<VF, XT>(A.V, v_lds, act_lds, A.mlp.w_max, true, r, row, lane);
+            if (lane == 0) A.V.rec.v_trunc[o] = vt;
+        }
+    }
+    slot = z_next;
+    xrow = row;
+    moved = true;
+    if (term || trunc) {
+        ep_t = 0;
+        if ((int64_t)ic >= t.N0) {  // psrs.py:33-35: reset() returned None; the observation stays next_obs of the row
+            slot = -1;
+            alive = false;
+            live = false;
+            none = true;
+            status = OFFSIM_ST_NO_INIT;
+        } else {
+            const uint32_t k = init_row ? init_row[ic] : ic;
+            ic++;
+            slot = t.init_slot[k];
+            xrow = -2 - t.init_orig[k];
+            fl |= OFFSIM_COLLECT_RESET;
+        }
+    }
+    if (alive) fl |= OFFSIM_COLLECT_ALIVE;
+    if (lane == 0) {
+        A.out.row[o] = row;
+        A.out.flags[o] = (uint8_t)fl;
+    }
+}
+
+// The end of the launch: the bootstrap of a path still open, the observation buffer, and (lane 0) the draw-stream row through `commit`
+// and the environment's state, for the next call.
+template <typename XT, int VF, typename KA, typename COMMIT>
+__device__ __forceinline__ void collect_write_back(const offsim_rollouts &ro, const KA &A, const float *v_lds, float *act_lds, unsigned char *obs_cur,
+                                                   int64_t ob, int64_t r, int lane, bool had_state, int slot, uint32_t ic, int32_t ep_t, int32_t xrow,
+                                                   bool alive, bool moved, bool none, int status, COMMIT &&commit) {
+    if constexpr (VF != COLLECT_VF_NONE) {  // the bootstrap of a path still open: v at the observation the environment holds (0: no state)
+        const float vf = had_state ? collect_value<VF, XT>(A.V, v_lds, act_lds, A.mlp.w_max, moved, r, xrow, lane) : 0.0f;
+        if (lane == 0) A.V.rec.final_value[r] = vf;
+    }
+    // the state, for the next call
+    if (moved) wave_copy_row(obs_cur, collect_obs_row(obs_cur, A.st.obs_next, A.st.obs_init, ob, moved, xrow), ob, lane);
+    if (lane == 0) {
+        commit();
+        ro.cur_slot[r] = slot;
+        ro.init_cursor[r] = ic;
+        A.st.ep_t[r] = ep_t;
+        if (moved) A.st.obs_row[r] = none ? -1 : xrow;
+        A.st.alive[r] = (uint8_t)alive;
+        if (A.out.status) A.out.status[r] = status;
+    }
+}
+
+// k_collect writes the four blocks above out itself: with any one of them called from here -- collect_dead_step and collect_unserved_step alone
+// were enough -- the register allocation and schedule of all 56 instances changed (profiles/queue_collect/isa_compare.txt), so the kernel's
+// text, and with it every instance's instructions, stays what it was and the helpers serve k_collect_queue.  A change to a block below
+// belongs in its helper too.
 template <typename PL, typename PROB, int FORM, typename XT, int VF>
 __global__ void __launch_bounds__(COLLECT_WAVES * WAVE) k_collect(offsim_table t, offsim_rollouts ro, CollectKArgs<VF> A) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -446,23 +555,18 @@ extern "C" int offsim_vector_collect(const offsim_table *t, offsim_rollouts *ro,
                                            1, ro->R);
 }
 
-// offsim_vector_collect_ppo (L = 1, E = ro->R) and offsim_vector_collect_ppo_pop: L learners' stacked networks, E environments each.
-// `who` / `who_critic` name the entry point in the error text.
-static int collect_ppo_run(const char *who, const char *who_critic, const offsim_table *t, offsim_rollouts *ro, const offsim_collect_policy *pol,
-                           const offsim_collect_value *val, int L, int E, int32_t prob_mode, int32_t reject_mode, int64_t T,
-                           int32_t max_episode_steps, const offsim_collect_state *st, const offsim_collect_out *out,
-                           const offsim_collect_ppo_out *ppo, void *stream) {
-    CollectPpoArgs A;
-    size_t shared;
-    int rc = collect_prepare(who, t, ro, pol, prob_mode, reject_mode, T, max_episode_steps, st, out, A, shared);
-    if (rc) return rc;
+// The critic's part of the arguments of a collect with the PPO records (k_collect's and k_collect_queue's): val and ppo checked, A.V filled,
+// the critic's network placed behind the actor's region, which starts `head` bytes into the workgroup's LDS (`shared`: in, the actor's bytes;
+// out, both networks').  x_dtype: in, the actor's observations' type; out, the type the in-kernel networks read.
+static int collect_prepare_value(const char *who, const char *who_critic, const offsim_table *t, const offsim_collect_policy *pol,
+                                 const offsim_collect_value *val, const offsim_collect_ppo_out *ppo, int64_t T, int E, size_t head, CollectPpoArgs &A,
+                                 size_t &shared, int &x_dtype) {
     memset(&A.V, 0, sizeof(A.V));
     if (!val || !ppo) return fail(OFFSIM_EINVAL, "%s: val / ppo is NULL", who);
     if (T > 0 && (!ppo->value || !ppo->logp || !ppo->final_value)) return fail(OFFSIM_EINVAL, "%s: ppo->value / logp / final_value is NULL", who);
     CollectValue &V = A.V;
-    int x_dtype = pol->form == OFFSIM_COLLECT_MLP ? pol->x_dtype : OFFSIM_F32;
     if (val->form == OFFSIM_VALUE_MLP) {
-        rc = collect_mlp(who_critic, t, *val, 1, V.mlp);
+        int rc = collect_mlp(who_critic, t, *val, 1, V.mlp);
         if (rc) return rc;
         if (pol->form == OFFSIM_COLLECT_MLP && val->x_dtype != pol->x_dtype)
             return fail(OFFSIM_EINVAL, "%s: the actor and the critic read observations of different types", who);
@@ -471,7 +575,7 @@ static int collect_ppo_run(const char *who, const char *who_critic, const offsim
         x_dtype = val->x_dtype;
         if (V.mlp.w_max > A.mlp.w_max) A.mlp.w_max = V.mlp.w_max;
         const size_t actor = (shared + 15) & ~(size_t)15;
-        V.off_w = (uint32_t)((size_t)COLLECT_WAVES * (WAVE + 1) * sizeof(Jump) + actor);
+        V.off_w = (uint32_t)(head + actor);
         shared = actor + (size_t)V.mlp.floats * sizeof(float);
     } else if (val->form == OFFSIM_VALUE_ROWS) {
         if (t->N > 0 && (!val->v_next || !val->v_init)) return fail(OFFSIM_EINVAL, "%s: v_next / v_init is NULL", who);
@@ -482,6 +586,21 @@ static int collect_ppo_run(const char *who, const char *who_critic, const offsim
     }
     V.rec = *ppo;
     V.envs = E;
+    return OFFSIM_OK;
+}
+
+// offsim_vector_collect_ppo (L = 1, E = ro->R) and offsim_vector_collect_ppo_pop: L learners' stacked networks, E environments each.
+// `who` / `who_critic` name the entry point in the error text.
+static int collect_ppo_run(const char *who, const char *who_critic, const offsim_table *t, offsim_rollouts *ro, const offsim_collect_policy *pol,
+                           const offsim_collect_value *val, int L, int E, int32_t prob_mode, int32_t reject_mode, int64_t T,
+                           int32_t max_episode_steps, const offsim_collect_state *st, const offsim_collect_out *out,
+                           const offsim_collect_ppo_out *ppo, void *stream) {
+    CollectPpoArgs A;
+    size_t shared;
+    int rc = collect_prepare(who, t, ro, pol, prob_mode, reject_mode, T, max_episode_steps, st, out, A, shared);
+    if (rc) return rc;
+    int x_dtype = pol->form == OFFSIM_COLLECT_MLP ? pol->x_dtype : OFFSIM_F32;
+    if ((rc = collect_prepare_value(who, who_critic, t, pol, val, ppo, T, E, (size_t)COLLECT_WAVES * (WAVE + 1) * sizeof(Jump), A, shared, x_dtype))) return rc;
     const size_t lds = collect_lds_layout(COLLECT_WAVES, shared, A.mlp.w_max, A);
     if (lds > 160 * 1024) return fail(OFFSIM_EUNSUPPORTED, "%s: the policy table, the critic and per-wave scratch exceed 160 KiB of LDS", who);
     if (ro->R == 0 || T == 0) return OFFSIM_OK;

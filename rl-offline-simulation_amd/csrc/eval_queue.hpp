@@ -314,10 +314,9 @@ static int queue_launch(const offsim_table *t, offsim_rollouts *ro, const double
     return OFFSIM_OK;
 }
 
-// what offsim_eval_queue and offsim_eval_queue_pop check alike, in offsim_eval_queue's order: the table and its key, ro, the action stream's
-// provider, out, the capacities, the learner (td; NULL: evalMC) and the tie mode ...
-static int queue_check(const char *who, const offsim_table *t, const offsim_rollouts *ro, int32_t nA_actions, const double *gamma_pow,
-                       int64_t n_gamma_pow, const offsim_evalmc_out *out, const offsim_td *td, int32_t tie_reseed_episode, int64_t episode0) {
+// the table rules of every queue entry point (also offsim_queue_collect's, csrc/collect_queue.hpp): the table and its key, ro, the action
+// stream's provider
+static int queue_check_table(const char *who, const offsim_table *t, const offsim_rollouts *ro, int32_t nA_actions) {
     int rc = check_table(t);
     if (rc) return rc;
     if (t->N0 > 0 && (!t->init_slot || !t->init_orig)) return fail(OFFSIM_EINVAL, "%s: table without its init rows", who);
@@ -328,6 +327,15 @@ static int queue_check(const char *who, const offsim_table *t, const offsim_roll
     if (ro->rng_kind == OFFSIM_STREAM_PHILOX)
         return fail(OFFSIM_EUNSUPPORTED, "%s: the action stream must be OFFSIM_STREAM_PCG64 (a Philox double lies in (0, 1]: u = 1.0 selects action nA)", who);
     if (ro->rng_kind != OFFSIM_STREAM_PCG64) return fail(OFFSIM_EINVAL, "%s: unknown stream provider", who);
+    return OFFSIM_OK;
+}
+
+// what offsim_eval_queue and offsim_eval_queue_pop check alike, in offsim_eval_queue's order: the table rules, out, the capacities, the
+// learner (td; NULL: evalMC) and the tie mode ...
+static int queue_check(const char *who, const offsim_table *t, const offsim_rollouts *ro, int32_t nA_actions, const double *gamma_pow,
+                       int64_t n_gamma_pow, const offsim_evalmc_out *out, const offsim_td *td, int32_t tie_reseed_episode, int64_t episode0) {
+    int rc = queue_check_table(who, t, ro, nA_actions);
+    if (rc) return rc;
     if (!out) return fail(OFFSIM_EINVAL, "%s: out is NULL", who);
     if ((rc = check_evalmc_out(who, out, gamma_pow, n_gamma_pow))) return rc;
     if (out->ep_cap < 0 || out->trace_cap < 0) return fail(OFFSIM_EINVAL, "%s: negative ep_cap / trace_cap", who);

@@ -2447,6 +2447,9 @@ extern "C" int offsim_value_mlp(const void *x, int32_t x_dtype, int64_t n_x, int
 // ---- a learner's data collection: T steps of policy -> PSRS.step -> reset per launch (csrc/collect.hpp) ----
 #include "collect.hpp"
 
+// ---- the same collection on QueueEvaluator: the agent draws its action, the simulator pops queue (z, a) (csrc/collect_queue.hpp) ----
+#include "collect_queue.hpp"
+
 // ---- the PPO buffer: GAE-lambda, rewards-to-go and spinup's normalisation over [T, E] records (csrc/ppo_buffer.hpp) ----
 #include "ppo_buffer.hpp"
 

@@ -36,28 +36,21 @@ except Exception:  # pragma: no cover
         pass
 
 
-class VectorPSRS:
-    def __init__(self, dataset, num_envs, num_states=None, encoder=None, device=None, strict=False):
-        # the validation of per_state_rejection.py:16-25
-        if not is_discrete(dataset.observation_space) and num_states is None and encoder is None:
-            raise ValueError("PerStateRejectionSampling only supports discrete observation spaces")
-        if (num_states is None or encoder is None) and (num_states != encoder):
-            raise ValueError("num_states and encoder either both need to be None, or both need to be specified")
-        if not is_discrete(dataset.action_space):
-            raise ValueError("PerStateRejectionSampling currently only supports discrete action spaces")
-        e = dataset.experience
-        if encoder is not None:
-            zs, next_zs = np.asarray(encoder.encode(e["observations"])), np.asarray(encoder.encode(e["next_observations"]))
-        else:
-            zs, next_zs = np.asarray(e["observations"]), np.asarray(e["next_observations"])
-        n = len(zs)
-        t0 = (np.asarray(e["steps"]) == 0) if "steps" in e else None
-        self.num_envs = int(num_envs)
-        self.strict = bool(strict)  # raise KeyError like the reference (costs a host sync per call); otherwise such environments just stop
-        self.table = TransitionTable(zs, e["actions"], e["rewards"], next_zs, e["terminals"],
-                                     np.asarray(e["action_distributions"]).reshape(n, -1), t0, device=device)
-        dev = self.table.device
-        self.env = BatchedPSRS(self.table, self.num_envs)
+class _Collector:
+    """collect / collect_ppo / collect_ppo_population of VectorPSRS and VectorQueueEvaluator (evaluators/vector_queue.py): argument checks,
+    the policy's and the critic's descriptors, the records' assembly.  A class that mixes this in has table, env (the BatchedPSRS holding the
+    rollout state), num_envs, strict, obs, alive, _ep_t, _obs_row, _obs, _next_obs, _a, _r, _encoded and _x_rows, and gives the simulator's part:
+      _launch_collect(pol, f32, T, cap, st, out, ppo, learners)  the library call; returns the drawn actions [T, E] or None (the served row's)
+      _raise_keyerror(status, action)                            strict mode's KeyError for the first environment that met one
+      _policy_f32(dtype)                                         whether a policy table of torch dtype `dtype` is passed as f32
+      _tabular_policy(pi, f32)                                   the device table of the TABULAR form from a host [nS, nA] array"""
+
+    # ---- a learner's data collection: T steps in one launch ----------------------------------------------------------------------
+    def _init_payload(self, dataset, encoded):
+        """The log's columns in caller order, the environments' observation / alive / ep_t / obs_row buffers and the gather descriptors of
+        reset and the per-step calls (needs table and num_envs)."""
+        e, dev = dataset.experience, self.table.device
+        n = len(e["actions"])
         # payload columns in the caller's row order (the kernels report rows of the caller's buffer)
         self._obs = torch.as_tensor(np.asarray(e["observations"])).to(dev)
         self._next_obs = torch.as_tensor(np.asarray(e["next_observations"])).to(dev)
@@ -77,7 +70,7 @@ class VectorPSRS:
         self._src_next = torch.arange(n, dtype=torch.int32, device=dev)
         self._src_init = -2 - self._src_next
         self._src_zero = torch.zeros(n, dtype=torch.int32, device=dev)
-        self._encoded = encoder is not None
+        self._encoded = bool(encoded)
         self._x_rows = None
         # outputs of step_dist_batch (overwritten by every call) and the column descriptors of offsim_vector_gather
         self._obs, self._next_obs, self._a, self._r, self._done = (x.contiguous() for x in (self._obs, self._next_obs, self._a, self._r, self._done))
@@ -97,90 +90,14 @@ class VectorPSRS:
                                (self._src_next, self._obs_row, False))
         self._cols_reset = cols((self._obs, self.obs, False), (self._src_init, self._obs_row, False), (self._src_zero, self._ep_t, False))
 
-    def reset_sampler(self, seeds, rejection="pcg64"):
-        """PSRS.reset_sampler(seed_k) for every environment (rejection: BatchedPSRS.reset_sampler's provider of the rejection stream)."""
-        self.env.reset_sampler(seeds, rejection=rejection)
-        self._sbuf.zero_()  # alive and ep_t
-        if self.strict:  # (strict mode synchronises with the host anyway: a sampler reset that gave up a bounded wait raises here)
-            self.check_faults()
-
-    def check_faults(self):
-        """Synchronise and raise OffsimError if the sampler reset gave up a bounded wait (include/offsim.h: offsim_async_faults).  With
-        strict=False nothing synchronises with the host, so the caller does this once after reset_sampler (or whenever it reads results)."""
-        self.env.check_faults()
-
-    def reset(self, mask=None):
-        """PSRS.reset (psrs.py:32-37) for the environments in `mask` (all if None).  Returns (obs [R, ...], alive [R])."""
+    def _reset_envs(self, mask):
+        """The simulator's reset for the environments in `mask` (all if None), with obs, obs_row, ep_t and alive kept in step"""
         m = None if mask is None else mask.to(torch.uint8).contiguous()
         row = self.env.reset(m)
         L.check(L.load().offsim_vector_gather(L.ptr(row), None, L.ptr(m), self.num_envs, self._cols_reset, len(self._cols_reset),
                                               L.ptr(self.alive), L.stream_ptr()))
         return self.obs, self.alive
 
-    def step_dist_batch(self, action_dists):
-        """per_state_rejection.py:85-95 for every environment at once.  action_dists: [R, nA] probabilities (tensor / array /
-        torch Distribution with .probs).  Returns device tensors (action, next_obs, reward, done, alive) -- the environment's own
-        buffers, overwritten by the next call (clone what has to outlive it); entries of environments with alive == False are
-        meaningless (the reference returns the all-None tuple there; action / reward keep their last value, done is False)."""
-        if isinstance(action_dists, Distribution):
-            action_dists = action_dists.probs
-        row, status, _ = self.env.step(action_dists)
-        if self.strict and bool((status == L.ST_KEYERROR).any()):  # psrs.py:44: the state has no queue
-            k = int(torch.nonzero(status == L.ST_KEYERROR)[0])
-            raise KeyError(self.table.z_of(int(self.env.state.cur_slot[k])))
-        L.check(L.load().offsim_vector_gather(L.ptr(row), L.ptr(status), None, self.num_envs, self._cols_step, len(self._cols_step),
-                                              L.ptr(self.alive), L.stream_ptr()))
-        return self.action, self.obs, self.reward, self.done, self.alive
-
-    def step_and_reset(self, action_dists):
-        """step_dist_batch followed by reset(mask=done) -- a whole driver iteration of the environments -- as ONE launch
-        (offsim_vector_step).  Returns (action, obs, reward, done, alive): obs is the next observation, or the initial observation of
-        the next episode where `done`; the same buffers as step_dist_batch's."""
-        if isinstance(action_dists, Distribution):
-            action_dists = action_dists.probs
-        env, t = self.env, self.table
-        env._orders_for_generic()
-        p = action_dists if isinstance(action_dists, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(action_dists))
-        f32 = p.dtype == torch.float32 and t.p_log.dtype == torch.float32
-        p = p.to(device=t.device, dtype=torch.float32 if f32 else torch.float64).reshape(self.num_envs, t.nA).contiguous()
-        L.check(L.load().offsim_vector_step(C.byref(t.c), C.byref(env.state.c), L.ptr(p), L.PROB_F32 if f32 else L.PROB_F64, env.reject_mode,
-                                            self._cols_step, len(self._cols_step), self._cols_reset, len(self._cols_reset), L.ptr(self.alive),
-                                            L.ptr(env._row), L.ptr(env._status), L.stream_ptr()))
-        if self.strict and bool((env._status == L.ST_KEYERROR).any()):
-            k = int(torch.nonzero(env._status == L.ST_KEYERROR)[0])
-            raise KeyError(self.table.z_of(int(env.state.cur_slot[k])))
-        self._keep = p
-        return self.action, self.obs, self.reward, self.done, self.alive
-
-    def graph_iteration(self, dist_fn, warmup=3, fused=True):
-        """Capture one driver iteration in a HIP graph: probs = dist_fn(self.obs); step_and_reset(probs) (fused=False: the four
-        launches of step_dist_batch(probs); reset(mask=done)).
-        Returns (graph, (action, reward, done)): every graph.replay() advances all environments by one step and leaves the
-        step's outputs in those three tensors (and in self.obs / self.alive).  `warmup` eager iterations run first on a side
-        stream (PyTorch's capture recipe; they are real steps of the environments).  strict must be False."""
-        if self.strict:
-            raise ValueError("graph capture needs strict=False (the KeyError check synchronises with the host)")
-
-        def iteration():
-            if fused:  # one launch for the environments' whole iteration
-                a, _, r, done, _ = self.step_and_reset(dist_fn(self.obs))
-                return a, r, done
-            a, _, r, done, _ = self.step_dist_batch(dist_fn(self.obs))
-            self.reset(mask=done)
-            return a, r, done
-
-        side = torch.cuda.Stream(device=self.table.device)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():
-            for _ in range(warmup):
-                iteration()
-        torch.cuda.current_stream().wait_stream(side)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g), torch.no_grad():
-            outs = iteration()
-        return g, outs
-
-    # ---- a learner's data collection: T steps in one launch ----------------------------------------------------------------------
     def collect(self, policy, num_steps, max_episode_steps=None, record_obs=True, record_probs=True, form="auto"):
         """The loop a learner runs inside PSRS (examples/cartpole/psrs_from_expert_heuristic.py:59-80, an epoch of a fixed network,
         offsim4rl/agents/ppo.py:122-160) for `num_steps` steps of every environment, in ONE launch (offsim_vector_collect):
@@ -216,8 +133,8 @@ class VectorPSRS:
         return self._collect_launch(pol, keep, f32, T, cap, record_obs, record_probs)
 
     def _collect_launch(self, pol, keep, f32, T, cap, record_obs, record_probs, ppo=None, learners=None):
-        """offsim_vector_collect (ppo None) or offsim_vector_collect_ppo (ppo = (offsim_collect_value, offsim_collect_ppo_out)) over T steps --
-        offsim_vector_collect_ppo_pop where the environments are those of `learners` learners with stacked networks; returns the
+        """The simulator's collect (ppo None) or collect_ppo (ppo = (offsim_collect_value, offsim_collect_ppo_out)) over T steps -- its
+        population form where the environments are those of `learners` learners with stacked networks (_launch_collect); returns the
         Collected records."""
         env, t = self.env, self.table
         E, dev = self.num_envs, t.device
@@ -232,21 +149,10 @@ class VectorPSRS:
         st.obs_bytes = self.obs.element_size() * int(np.prod(self.obs.shape[1:], dtype=np.int64))
         out = L.CollectOut()
         out.row, out.flags, out.obs, out.probs, out.status = L.ptr(row), L.ptr(flags), L.ptr(obs), L.ptr(probs), L.ptr(status)
-        if ppo is None:
-            L.check(L.load().offsim_vector_collect(C.byref(t.c), C.byref(env.state.c), C.byref(pol), L.PROB_F32 if f32 else L.PROB_F64,
-                                                   env.reject_mode, T, cap, C.byref(st), C.byref(out), L.stream_ptr()))
-        elif learners is not None:
-            L.check(L.load().offsim_vector_collect_ppo_pop(C.byref(t.c), C.byref(env.state.c), C.byref(pol), C.byref(ppo[0]), learners, E // learners,
-                                                           L.PROB_F32 if f32 else L.PROB_F64, env.reject_mode, T, cap, C.byref(st), C.byref(out),
-                                                           C.byref(ppo[1]), L.stream_ptr()))
-        else:
-            L.check(L.load().offsim_vector_collect_ppo(C.byref(t.c), C.byref(env.state.c), C.byref(pol), C.byref(ppo[0]),
-                                                       L.PROB_F32 if f32 else L.PROB_F64, env.reject_mode, T, cap, C.byref(st), C.byref(out),
-                                                       C.byref(ppo[1]), L.stream_ptr()))
+        drawn = self._launch_collect(pol, f32, T, cap, st, out, ppo, learners)
         self._keep = keep
         if self.strict and bool((status == L.ST_KEYERROR).any()):
-            k = int(torch.nonzero(status == L.ST_KEYERROR)[0])
-            raise KeyError(self.table.z_of(int(env.state.cur_slot[k])))
+            self._raise_keyerror(status, drawn)
         served = (flags & L.COLLECT_SERVED) != 0
         rl = row.clamp(min=0).to(torch.int64)
 
@@ -256,7 +162,8 @@ class VectorPSRS:
             v = col[rl]
             return torch.where(served.reshape(served.shape + (1,) * (v.dim() - 2)), v, torch.zeros((), dtype=v.dtype, device=dev))
 
-        return Collected(obs=obs, probs=probs, row=row, action=take(self._a), reward=take(self._r), next_obs=take(self._next_obs),
+        action = take(self._a) if drawn is None else torch.where(served, drawn, torch.zeros((), dtype=drawn.dtype, device=dev)).to(self._a.dtype)
+        return Collected(obs=obs, probs=probs, row=row, action=action, reward=take(self._r), next_obs=take(self._next_obs),
                          terminated=(flags & L.COLLECT_TERMINATED) != 0, truncated=(flags & L.COLLECT_TRUNCATED) != 0,
                          reset=(flags & L.COLLECT_RESET) != 0, alive=(flags & L.COLLECT_ALIVE) != 0, final_obs=self.obs.clone(), status=status)
 
@@ -350,7 +257,7 @@ class VectorPSRS:
         pol, val = L.CollectPolicy(), L.CollectValue()
         keep = self._collect_mlp(pol, L.COLLECT_MLP, pi, "collect_ppo_population: the actors") + \
             self._collect_mlp(val, L.VALUE_MLP, v, "collect_ppo_population: the critics")
-        return self._collect_ppo_records(pol, val, keep, t.p_log.dtype == torch.float32, T, cap, gamma, lam, normalize, bootstrap, learners=nl)
+        return self._collect_ppo_records(pol, val, keep, self._policy_f32(torch.float32), T, cap, gamma, lam, normalize, bootstrap, learners=nl)
 
     def _collect_policy(self, policy, form):
         """offsim_collect_policy for collect / collect_ppo: (struct, tensors to keep alive, whether p_new is compared in f32)."""
@@ -362,12 +269,12 @@ class VectorPSRS:
             if not isinstance(policy, MLPPolicy):
                 raise TypeError(f"collect: form='mlp' needs an MLPPolicy, got {type(policy).__name__}")
             keep += self._collect_mlp(pol, L.COLLECT_MLP, policy, "collect: the network")
-            f32 = t.p_log.dtype == torch.float32
+            f32 = self._policy_f32(torch.float32)
         elif form == "rows":
             if not isinstance(policy, ObsPolicy):
                 raise TypeError(f"collect: form='rows' needs an ObsPolicy, got {type(policy).__name__}")
             pn, p0 = self._caller_tables(policy)
-            f32 = pn.dtype == torch.float32 and t.p_log.dtype == torch.float32
+            f32 = self._policy_f32(pn.dtype)
             pn, p0 = (x.to(torch.float32 if f32 else torch.float64).contiguous() for x in (pn, p0))
             pol.form, pol.p_next, pol.p_init = L.COLLECT_ROWS, L.ptr(pn), L.ptr(p0)
             keep += [pn, p0]
@@ -380,10 +287,8 @@ class VectorPSRS:
             pi = policy.detach().cpu().numpy() if isinstance(policy, torch.Tensor) else np.asarray(policy)
             if pi.ndim != 2 or pi.shape[1] != t.nA:
                 raise ValueError(f"collect: pi must be a [nS, {t.nA}] table, got shape {pi.shape}")
-            if t.N and pi.shape[0] <= int(t.slot_z.max()):
-                raise IndexError("pi has no row for some latent state")
-            f32 = pi.dtype == np.float32 and t.p_log.dtype == torch.float32
-            ps = torch.from_numpy(np.ascontiguousarray(t.policy_slots(pi).astype(np.float32 if f32 else np.float64))).to(t.device)
+            f32 = self._policy_f32(torch.float32 if pi.dtype == np.float32 else torch.float64)
+            ps = self._tabular_policy(pi, f32)
             pol.form, pol.pi = L.COLLECT_TABULAR, L.ptr(ps)
             keep.append(ps)
         else:
@@ -429,5 +334,139 @@ class VectorPSRS:
             pn, p0 = pn.to(torch.float64), p0.to(torch.float64)
         return pn.contiguous(), p0.contiguous()
 
+
+class VectorPSRS(_Collector):
+    def __init__(self, dataset, num_envs, num_states=None, encoder=None, device=None, strict=False):
+        # the validation of per_state_rejection.py:16-25
+        if not is_discrete(dataset.observation_space) and num_states is None and encoder is None:
+            raise ValueError("PerStateRejectionSampling only supports discrete observation spaces")
+        if (num_states is None or encoder is None) and (num_states != encoder):
+            raise ValueError("num_states and encoder either both need to be None, or both need to be specified")
+        if not is_discrete(dataset.action_space):
+            raise ValueError("PerStateRejectionSampling currently only supports discrete action spaces")
+        e = dataset.experience
+        if encoder is not None:
+            zs, next_zs = np.asarray(encoder.encode(e["observations"])), np.asarray(encoder.encode(e["next_observations"]))
+        else:
+            zs, next_zs = np.asarray(e["observations"]), np.asarray(e["next_observations"])
+        n = len(zs)
+        t0 = (np.asarray(e["steps"]) == 0) if "steps" in e else None
+        self.num_envs = int(num_envs)
+        self.strict = bool(strict)  # raise KeyError like the reference (costs a host sync per call); otherwise such environments just stop
+        self.table = TransitionTable(zs, e["actions"], e["rewards"], next_zs, e["terminals"],
+                                     np.asarray(e["action_distributions"]).reshape(n, -1), t0, device=device)
+        dev = self.table.device
+        self.env = BatchedPSRS(self.table, self.num_envs)
+        self._init_payload(dataset, encoder is not None)
+
+    # ---- the simulator's part of collect / collect_ppo / collect_ppo_population (_Collector) ----
+    def _launch_collect(self, pol, f32, T, cap, st, out, ppo, learners):
+        """offsim_vector_collect (ppo None), offsim_vector_collect_ppo, or offsim_vector_collect_ppo_pop for `learners` learners"""
+        env, t = self.env, self.table
+        if ppo is None:
+            L.check(L.load().offsim_vector_collect(C.byref(t.c), C.byref(env.state.c), C.byref(pol), L.PROB_F32 if f32 else L.PROB_F64,
+                                                   env.reject_mode, T, cap, C.byref(st), C.byref(out), L.stream_ptr()))
+        elif learners is not None:
+            L.check(L.load().offsim_vector_collect_ppo_pop(C.byref(t.c), C.byref(env.state.c), C.byref(pol), C.byref(ppo[0]), learners,
+                                                           self.num_envs // learners, L.PROB_F32 if f32 else L.PROB_F64, env.reject_mode, T, cap,
+                                                           C.byref(st), C.byref(out), C.byref(ppo[1]), L.stream_ptr()))
+        else:
+            L.check(L.load().offsim_vector_collect_ppo(C.byref(t.c), C.byref(env.state.c), C.byref(pol), C.byref(ppo[0]),
+                                                       L.PROB_F32 if f32 else L.PROB_F64, env.reject_mode, T, cap, C.byref(st), C.byref(out),
+                                                       C.byref(ppo[1]), L.stream_ptr()))
+        return None
+
+    def _raise_keyerror(self, status, drawn):
+        k = int(torch.nonzero(status == L.ST_KEYERROR)[0])
+        raise KeyError(self.table.z_of(int(self.env.state.cur_slot[k])))
+
+    def _policy_f32(self, dtype):
+        """p_new is compared in f32 where the policy's probabilities and p_log are both f32 (step_and_reset's rule)"""
+        return dtype == torch.float32 and self.table.p_log.dtype == torch.float32
+
+    def _tabular_policy(self, pi, f32):
+        t = self.table
+        if t.N and pi.shape[0] <= int(t.slot_z.max()):
+            raise IndexError("pi has no row for some latent state")
+        return torch.from_numpy(np.ascontiguousarray(t.policy_slots(pi).astype(np.float32 if f32 else np.float64))).to(t.device)
+
+    def reset_sampler(self, seeds, rejection="pcg64"):
+        """PSRS.reset_sampler(seed_k) for every environment (rejection: BatchedPSRS.reset_sampler's provider of the rejection stream)."""
+        self.env.reset_sampler(seeds, rejection=rejection)
+        self._sbuf.zero_()  # alive and ep_t
+        if self.strict:  # (strict mode synchronises with the host anyway: a sampler reset that gave up a bounded wait raises here)
+            self.check_faults()
+
+    def check_faults(self):
+        """Synchronise and raise OffsimError if the sampler reset gave up a bounded wait (include/offsim.h: offsim_async_faults).  With
+        strict=False nothing synchronises with the host, so the caller does this once after reset_sampler (or whenever it reads results)."""
+        self.env.check_faults()
+
+    def reset(self, mask=None):
+        """PSRS.reset (psrs.py:32-37) for the environments in `mask` (all if None).  Returns (obs [R, ...], alive [R])."""
+        return self._reset_envs(mask)
+
+    def step_dist_batch(self, action_dists):
+        """per_state_rejection.py:85-95 for every environment at once.  action_dists: [R, nA] probabilities (tensor / array /
+        torch Distribution with .probs).  Returns device tensors (action, next_obs, reward, done, alive) -- the environment's own
+        buffers, overwritten by the next call (clone what has to outlive it); entries of environments with alive == False are
+        meaningless (the reference returns the all-None tuple there; action / reward keep their last value, done is False)."""
+        if isinstance(action_dists, Distribution):
+            action_dists = action_dists.probs
+        row, status, _ = self.env.step(action_dists)
+        if self.strict and bool((status == L.ST_KEYERROR).any()):  # psrs.py:44: the state has no queue
+            k = int(torch.nonzero(status == L.ST_KEYERROR)[0])
+            raise KeyError(self.table.z_of(int(self.env.state.cur_slot[k])))
+        L.check(L.load().offsim_vector_gather(L.ptr(row), L.ptr(status), None, self.num_envs, self._cols_step, len(self._cols_step),
+                                              L.ptr(self.alive), L.stream_ptr()))
+        return self.action, self.obs, self.reward, self.done, self.alive
+
+    def step_and_reset(self, action_dists):
+        """step_dist_batch followed by reset(mask=done) -- a whole driver iteration of the environments -- as ONE launch
+        (offsim_vector_step).  Returns (action, obs, reward, done, alive): obs is the next observation, or the initial observation of
+        the next episode where `done`; the same buffers as step_dist_batch's."""
+        if isinstance(action_dists, Distribution):
+            action_dists = action_dists.probs
+        env, t = self.env, self.table
+        env._orders_for_generic()
+        p = action_dists if isinstance(action_dists, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(action_dists))
+        f32 = p.dtype == torch.float32 and t.p_log.dtype == torch.float32
+        p = p.to(device=t.device, dtype=torch.float32 if f32 else torch.float64).reshape(self.num_envs, t.nA).contiguous()
+        L.check(L.load().offsim_vector_step(C.byref(t.c), C.byref(env.state.c), L.ptr(p), L.PROB_F32 if f32 else L.PROB_F64, env.reject_mode,
+                                            self._cols_step, len(self._cols_step), self._cols_reset, len(self._cols_reset), L.ptr(self.alive),
+                                            L.ptr(env._row), L.ptr(env._status), L.stream_ptr()))
+        if self.strict and bool((env._status == L.ST_KEYERROR).any()):
+            k = int(torch.nonzero(env._status == L.ST_KEYERROR)[0])
+            raise KeyError(self.table.z_of(int(env.state.cur_slot[k])))
+        self._keep = p
+        return self.action, self.obs, self.reward, self.done, self.alive
+
+    def graph_iteration(self, dist_fn, warmup=3, fused=True):
+        """Capture one driver iteration in a HIP graph: probs = dist_fn(self.obs); step_and_reset(probs) (fused=False: the four
+        launches of step_dist_batch(probs); reset(mask=done)).
+        Returns (graph, (action, reward, done)): every graph.replay() advances all environments by one step and leaves the
+        step's outputs in those three tensors (and in self.obs / self.alive).  `warmup` eager iterations run first on a side
+        stream (PyTorch's capture recipe; they are real steps of the environments).  strict must be False."""
+        if self.strict:
+            raise ValueError("graph capture needs strict=False (the KeyError check synchronises with the host)")
+
+        def iteration():
+            if fused:  # one launch for the environments' whole iteration
+                a, _, r, done, _ = self.step_and_reset(dist_fn(self.obs))
+                return a, r, done
+            a, _, r, done, _ = self.step_dist_batch(dist_fn(self.obs))
+            self.reset(mask=done)
+            return a, r, done
+
+        side = torch.cuda.Stream(device=self.table.device)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side), torch.no_grad():
+            for _ in range(warmup):
+                iteration()
+        torch.cuda.current_stream().wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g), torch.no_grad():
+            outs = iteration()
+        return g, outs
 
 Collected = namedtuple("Collected", "obs probs row action reward next_obs terminated truncated reset alive final_obs status")
