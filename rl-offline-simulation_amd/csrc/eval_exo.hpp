@@ -32,16 +32,19 @@ struct ExoArgs {
 };
 
 // POP = true (with TD): a population of L tabular learners on the same S seeds, every one acting on its own Q (offsim_eval_td_exo_pop;
-// arguments and index rules in csrc/td_pop_exo.hpp).  The instance overwrites its per-launch hyper-parameters -- td.alpha / epsilon /
+// arguments and index rule in csrc/td_pop.hpp).  The instance overwrites its per-launch hyper-parameters -- td.alpha / epsilon /
 // behaviour / the schedule rows, gamma, gamma_pow, pi -- with its workgroup's learner's before anything reads them, and before every step
 // rebuilds the behaviour distribution from the Q row of the current observation (td_behaviour, the block k_eval_mc calls) in beh_lds,
 // which the step then rejects against.  LDS: the carve above, then -- behind the x-cursors, so that every offset above stays --
 //   [beh_lds per wave: waves * nA f64, 8-byte aligned][tie stream per wave: waves * 624 u32]
 // The POP instances take their own argument struct, so the kernel arguments of every other instance are what they were.
-#include "td_pop_exo.hpp"
+struct TdPopExoArgs : ExoArgs, TdPopFields {};
+static_assert(td_pop_layout<TdPopExoArgs>(120, 40, 112), "kernel arguments of k_eval_mc_exo<.., TD, POP>");
 template <bool POP>
 using ExoKernelArgs = std::conditional_t<POP, TdPopExoArgs, ExoArgs>;
 
+// The learner blocks around the step (POP prologue and index, tie stream, TD update, episode close, outputs) are written out in each of the three
+// rollout kernels: called as shared inline functions they changed every instance's code (profiles/td_learner_one_definition/isa_compare.txt).
 template <typename PL, typename PROB, bool TD, bool POP = false>
 __global__ void __launch_bounds__(256, 4) k_eval_mc_exo(offsim_table ts, offsim_table tx, offsim_rollouts rs, offsim_rollouts rx,
                                                      const PROB *__restrict__ pi, ExoKernelArgs<POP> xa, double gamma,
@@ -338,17 +341,13 @@ static size_t exo_lds_bytes(int waves, int64_t ns, int64_t nx, int64_t n_obs, in
            (pop ? 8 + (size_t)waves * nA * 8 + (size_t)waves * 624 * 4 : 0);
 }
 
-// the launch shape of evalmc_launch: 4 rollouts per workgroup, halved until the carve fits 64 KiB; up to 160 KiB with one rollout
+// the launch shape (launch_shape) of the carve above
 static int exo_launch_shape(const offsim_table *ts, const offsim_table *tx, int32_t n_obs, size_t pb, bool td, int *waves_out, size_t *lds_out,
                             bool pop = false, const char *who = "eval_mc_exo") {
     if ((int64_t)ts->n_slots * tx->n_slots > 40960 || (int64_t)n_obs * ts->nA > 40960)  // (beyond 160 KiB whatever else: also keeps the sums below in range)
         return fail(OFFSIM_EUNSUPPORTED, "%s: obs_of, policy, Q table and cursors exceed 160 KiB of LDS", who);
-    int waves = 4;
-    while (waves > 1 && exo_lds_bytes(waves, ts->n_slots, tx->n_slots, n_obs, ts->nA, pb, td, pop) > 64 * 1024) waves >>= 1;
-    const size_t lds = exo_lds_bytes(waves, ts->n_slots, tx->n_slots, n_obs, ts->nA, pb, td, pop);
-    if (lds > 160 * 1024) return fail(OFFSIM_EUNSUPPORTED, "%s: obs_of, policy, Q table and cursors exceed 160 KiB of LDS", who);
-    *waves_out = waves;
-    *lds_out = lds;
+    if (!launch_shape([&](int w) { return exo_lds_bytes(w, ts->n_slots, tx->n_slots, n_obs, ts->nA, pb, td, pop); }, waves_out, lds_out))
+        return fail(OFFSIM_EUNSUPPORTED, "%s: obs_of, policy, Q table and cursors exceed 160 KiB of LDS", who);
     return OFFSIM_OK;
 }
 
@@ -358,7 +357,7 @@ static int exo_launch(const offsim_table *ts, const offsim_table *tx, offsim_rol
                       const offsim_evalmc_out *out, const offsim_td &td, int waves, size_t lds, void *stream) {
     if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_eval_mc_exo<PL, PROB, TD, POP>), (int)lds));
     unsigned grid = (unsigned)((rs->R + waves - 1) / waves);
-    if constexpr (POP) grid = (unsigned)(rs->R / xa.S) * (unsigned)((xa.S + waves - 1) / waves);  // a workgroup holds rollouts of one learner
+    if constexpr (POP) grid = pop_grid(rs->R, xa.S, waves);
     hipLaunchKernelGGL((k_eval_mc_exo<PL, PROB, TD, POP>), dim3(grid), dim3(waves * WAVE), lds, (hipStream_t)stream, *ts, *tx, *rs, *rx,
                        (const PROB *)pi, xa, gamma, gamma_pow, n_gamma_pow, max_episodes, *out, td);
     LAUNCH_CHECK();
@@ -385,37 +384,32 @@ static int exo_check_common(const char *who, const offsim_table *ts, const offsi
     if (out->ep_cap < 0 || out->trace_cap < 0) return fail(OFFSIM_EINVAL, "%s: negative ep_cap / trace_cap", who);
     return OFFSIM_OK;
 }
+static ExoArgs exo_args(const int32_t *obs_of, int32_t n_obs, int32_t reseed, uint64_t episode0, const offsim_exo_out *xout) {
+    return ExoArgs{obs_of, n_obs, reseed, episode0, offsim_exo_out{xout ? xout->trace_row_x : nullptr, xout ? xout->last : nullptr}};
+}
 
 extern "C" int offsim_eval_mc_exo(const offsim_table *ts, const offsim_table *tx, offsim_rollouts *rs, offsim_rollouts *rx, const void *pi,
                                   const int32_t *obs_of, int32_t n_obs, int32_t prob_mode, int32_t reseed, uint64_t episode0, double gamma,
                                   const double *gamma_pow, int64_t n_gamma_pow, int64_t max_episodes, const offsim_evalmc_out *out,
                                   const offsim_exo_out *xout, const offsim_td *td, void *stream) {
-    int rc = exo_check_common("eval_mc_exo", ts, tx, rs, rx, obs_of, n_obs, reseed, out, gamma_pow, n_gamma_pow);
+    static const char *who = "eval_mc_exo";
+    int rc = exo_check_common(who, ts, tx, rs, rx, obs_of, n_obs, reseed, out, gamma_pow, n_gamma_pow);
     if (rc) return rc;
-    if (!pi) return fail(OFFSIM_EINVAL, "eval_mc_exo: bad n_obs, or obs_of / pi is NULL%s");
-    if ((rc = check_prob_mode("eval_mc_exo", ts, prob_mode))) return rc;
-    if (td) {
-        if ((td->mode != OFFSIM_TD_QLEARN && td->mode != OFFSIM_TD_EXPSARSA) || !td->q) return fail(OFFSIM_EINVAL, "eval_mc_exo: bad td mode or NULL q%s");
-        if (prob_mode != OFFSIM_PROB_F64) return fail(OFFSIM_EINVAL, "eval_mc_exo: the learner drivers take an f64 pi (OFFSIM_PROB_F64)%s");
-        if (td->behaviour != OFFSIM_BEHAVIOUR_FIXED && td->behaviour != OFFSIM_BEHAVIOUR_EPS_GREEDY && td->behaviour != OFFSIM_BEHAVIOUR_SOFT_GREEDY)
-            return fail(OFFSIM_EINVAL, "eval_mc_exo: bad behaviour%s");
+    if (!pi) return fail(OFFSIM_EINVAL, "%s: bad n_obs, or obs_of / pi is NULL", who);
+    if ((rc = check_prob_mode(who, ts, prob_mode))) return rc;
+    if (td) {  // check_td around this entry point's own two rules; of the schedules it looks at alpha_ep only
+        if ((rc = check_td(who, td, TD_RULE_MODE))) return rc;
+        if (prob_mode != OFFSIM_PROB_F64) return fail(OFFSIM_EINVAL, "%s: the learner drivers take an f64 pi (OFFSIM_PROB_F64)", who);
+        if ((rc = check_td(who, td, TD_RULE_BEHAVIOUR))) return rc;
         if (td->behaviour != OFFSIM_BEHAVIOUR_FIXED || td->tie_mt)
-            return fail(OFFSIM_EUNSUPPORTED, "eval_mc_exo: only OFFSIM_BEHAVIOUR_FIXED (no greedy behaviour on the learner's own Q, no tie stream)%s");
-        if (td->alpha_ep && td->n_sched <= 0) return fail(OFFSIM_EINVAL, "eval_mc_exo: schedules need n_sched > 0%s");
-        if (td->td_cap < 0) return fail(OFFSIM_EINVAL, "eval_mc_exo: negative td_cap%s");
-        if (td->q_snap && (td->snap_stride <= 0 || td->snap_cap < 0)) return fail(OFFSIM_EINVAL, "eval_mc_exo: bad snapshot stride / capacity%s");
+            return fail(OFFSIM_EUNSUPPORTED, "%s: only OFFSIM_BEHAVIOUR_FIXED (no greedy behaviour on the learner's own Q, no tie stream)", who);
+        if ((rc = check_td(who, td, TD_RULE_SCHED_ALPHA | TD_RULE_CAP | TD_RULE_SNAP))) return rc;
     }
     int waves = 0;
     size_t lds = 0;
     if ((rc = exo_launch_shape(ts, tx, n_obs, prob_mode == OFFSIM_PROB_F32 ? 4 : 8, td != nullptr, &waves, &lds))) return rc;
     if (rs->R == 0) return OFFSIM_OK;
-    ExoArgs xa;
-    xa.obs_of = obs_of;
-    xa.n_obs = n_obs;
-    xa.reseed = reseed;
-    xa.episode0 = episode0;
-    xa.xout.trace_row_x = xout ? xout->trace_row_x : nullptr;
-    xa.xout.last = xout ? xout->last : nullptr;
+    const ExoArgs xa = exo_args(obs_of, n_obs, reseed, episode0, xout);
     offsim_td tdv;
     memset(&tdv, 0, sizeof(tdv));
     if (td) tdv = *td;
@@ -430,7 +424,7 @@ extern "C" int offsim_eval_mc_exo(const offsim_table *ts, const offsim_table *tx
 }
 
 // ---- offsim_eval_mc_exo's learner drivers for L learners on the same S seeds in one launch, every learner on its own Q with any behaviour
-// policy of the reference (k_eval_mc_exo<.., TD, POP>, csrc/td_pop_exo.hpp); L = 1 is the single learner with a greedy behaviour
+// policy of the reference (k_eval_mc_exo<.., TD, POP>, csrc/td_pop.hpp); L = 1 is the single learner with a greedy behaviour
 extern "C" int offsim_eval_td_exo_pop(const offsim_table *ts, const offsim_table *tx, offsim_rollouts *rs, offsim_rollouts *rx, int32_t L, int32_t S,
                                       const offsim_td_pop *pop, const int32_t *obs_of, int32_t n_obs, int32_t reseed, uint64_t episode0,
                                       int64_t max_episodes, const offsim_evalmc_out *out, const offsim_exo_out *xout, void *stream) {
@@ -443,23 +437,7 @@ extern "C" int offsim_eval_td_exo_pop(const offsim_table *ts, const offsim_table
     size_t lds = 0;
     if ((rc = exo_launch_shape(ts, tx, n_obs, 8, true, &waves, &lds, true, who))) return rc;
     if (rs->R == 0) return OFFSIM_OK;
-    TdPopExoArgs xa{};
-    xa.obs_of = obs_of;
-    xa.n_obs = n_obs;
-    xa.reseed = reseed;
-    xa.episode0 = episode0;
-    xa.xout.trace_row_x = xout ? xout->trace_row_x : nullptr;
-    xa.xout.last = xout ? xout->last : nullptr;
-    xa.S = S;
-    xa.alpha = pop->alpha;
-    xa.epsilon = pop->epsilon;
-    xa.gamma = pop->gamma;
-    xa.gamma_pow = pop->gamma_pow;
-    xa.behaviour = pop->behaviour;
-    xa.alpha_ep = pop->alpha_ep;
-    xa.epsilon_ep = pop->epsilon_ep;
-    xa.pi = pop->pi;
-    xa.pi_stride = pop->pi_stride;
+    const TdPopExoArgs xa{exo_args(obs_of, n_obs, reseed, episode0, xout), td_pop_fields(pop, S)};
     const offsim_td td = td_of_pop(pop);
     return with_plog(ts, [&](auto pl) -> int {
         return exo_launch<decltype(pl), double, true, true>(ts, tx, rs, rx, nullptr, xa, 0.0, nullptr, pop->n_gamma_pow, max_episodes, out, td, waves, lds,

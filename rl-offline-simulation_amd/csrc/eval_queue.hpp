@@ -27,7 +27,7 @@
 //   [Q per wave (TD): waves * n f64][pi (when given): n f64][behaviour row per wave (TD): waves * nA f64][seg_off: n + 1 u32]
 //   [cursors per wave: waves * n u32][tie stream per wave (TD): waves * 624 u32]
 //
-// Many learners per launch (offsim_eval_queue_pop): the POP instance below, arguments and index rules in csrc/td_pop_queue.hpp.
+// Many learners per launch (offsim_eval_queue_pop): the POP instance below, arguments and index rules in csrc/td_pop.hpp.
 //
 // Included by offsim_hip.hip behind eval_exo.hpp: check_table, check_evalmc_out, check_td_pop, td_of_pop, td_behaviour, discount_at and
 // allow_big_lds are that file's.
@@ -68,13 +68,16 @@ struct QueueArgs {
 };
 
 // POP = true (with TD): a population of L tabular learners on the same S seeds (offsim_eval_queue_pop; arguments and index rules in
-// csrc/td_pop_queue.hpp).  The instance overwrites its per-launch hyper-parameters -- td.alpha / epsilon / behaviour / the schedule rows,
+// csrc/td_pop.hpp).  The instance overwrites its per-launch hyper-parameters -- td.alpha / epsilon / behaviour / the schedule rows,
 // gamma, gamma_pow, pi -- with its workgroup's learner's before anything reads them; rollout r = l * S + j reads queue orders j.  The LDS
 // carve is the learner carve above.  The POP instance takes its own argument struct, so the kernel arguments of the other two are what they were.
-#include "td_pop_queue.hpp"
+struct QueuePopArgs : QueueArgs, TdPopFields {};
+static_assert(td_pop_layout<QueuePopArgs>(96, 16, 88), "kernel arguments of k_eval_queue<TD, POP>");
 template <bool POP>
 using QueueKernelArgs = std::conditional_t<POP, QueuePopArgs, QueueArgs>;
 
+// The learner blocks around the step (POP prologue and index, tie stream, TD update, episode close, outputs) are written out in each of the three
+// rollout kernels: called as shared inline functions they changed every instance's code (profiles/td_learner_one_definition/isa_compare.txt).
 template <bool TD, bool POP = false>
 __global__ void __launch_bounds__(256, 4) k_eval_queue(offsim_table t, offsim_rollouts ro, const double *__restrict__ pi, double gamma,
                                                     const double *__restrict__ gamma_pow, int64_t n_gamma_pow, int64_t max_episodes,
@@ -307,7 +310,7 @@ static int queue_launch(const offsim_table *t, offsim_rollouts *ro, const double
                         void *stream) {
     if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_eval_queue<TD, POP>), (int)lds));
     unsigned grid = (unsigned)((ro->R + waves - 1) / waves);
-    if constexpr (POP) grid = (unsigned)(ro->R / qa.S) * (unsigned)((qa.S + waves - 1) / waves);  // a workgroup holds rollouts of one learner
+    if constexpr (POP) grid = pop_grid(ro->R, qa.S, waves);
     hipLaunchKernelGGL((k_eval_queue<TD, POP>), dim3(grid), dim3(waves * WAVE), lds, (hipStream_t)stream, *t, *ro, pi, gamma, gamma_pow, n_gamma_pow,
                        max_episodes, *out, td, qa);
     LAUNCH_CHECK();
@@ -341,12 +344,7 @@ static int queue_check(const char *who, const offsim_table *t, const offsim_roll
     if (out->ep_cap < 0 || out->trace_cap < 0) return fail(OFFSIM_EINVAL, "%s: negative ep_cap / trace_cap", who);
     if (tie_reseed_episode != 0 && tie_reseed_episode != 1) return fail(OFFSIM_EINVAL, "%s: tie_reseed_episode is 0 or 1", who);
     if (td) {
-        if ((td->mode != OFFSIM_TD_QLEARN && td->mode != OFFSIM_TD_EXPSARSA) || !td->q) return fail(OFFSIM_EINVAL, "%s: bad td mode or NULL q", who);
-        if (td->behaviour != OFFSIM_BEHAVIOUR_FIXED && td->behaviour != OFFSIM_BEHAVIOUR_EPS_GREEDY && td->behaviour != OFFSIM_BEHAVIOUR_SOFT_GREEDY)
-            return fail(OFFSIM_EINVAL, "%s: bad behaviour", who);
-        if ((td->alpha_ep || td->epsilon_ep) && td->n_sched <= 0) return fail(OFFSIM_EINVAL, "%s: schedules need n_sched > 0", who);
-        if (td->td_cap < 0) return fail(OFFSIM_EINVAL, "%s: negative td_cap", who);
-        if (td->q_snap && (td->snap_stride <= 0 || td->snap_cap < 0)) return fail(OFFSIM_EINVAL, "%s: bad snapshot stride / capacity", who);
+        if ((rc = check_td(who, td, TD_RULES))) return rc;
         if (tie_reseed_episode && (!td->tie_mt || episode0 < 0))
             return fail(OFFSIM_EINVAL, "%s: tie_reseed_episode needs td->tie_mt (the stream is written back there) and episode0 >= 0", who);
     } else if (tie_reseed_episode) {
@@ -355,15 +353,11 @@ static int queue_check(const char *who, const offsim_table *t, const offsim_roll
     return OFFSIM_OK;
 }
 
-// ... and the launch shape: 4 rollouts per workgroup, halved until the carve fits 64 KiB; up to 160 KiB with one rollout; beyond: refused
+// ... and the launch shape (launch_shape) of the carve above; beyond 160 KiB: refused
 static int queue_launch_shape(const char *who, const offsim_table *t, bool have_pi, bool td, int *waves_out, size_t *lds_out) {
     if (t->n_slots > 40960) return fail(OFFSIM_EUNSUPPORTED, "%s: cursors, policy and Q table exceed 160 KiB of LDS", who);  // (keeps the sums in range)
-    int waves = 4;
-    while (waves > 1 && queue_lds_bytes(waves, t->n_slots, t->nA, have_pi, td) > 64 * 1024) waves >>= 1;
-    const size_t lds = queue_lds_bytes(waves, t->n_slots, t->nA, have_pi, td);
-    if (lds > 160 * 1024) return fail(OFFSIM_EUNSUPPORTED, "%s: cursors, policy and Q table exceed 160 KiB of LDS", who);
-    *waves_out = waves;
-    *lds_out = lds;
+    if (!launch_shape([&](int w) { return queue_lds_bytes(w, t->n_slots, t->nA, have_pi, td); }, waves_out, lds_out))
+        return fail(OFFSIM_EUNSUPPORTED, "%s: cursors, policy and Q table exceed 160 KiB of LDS", who);
     return OFFSIM_OK;
 }
 
@@ -382,15 +376,12 @@ extern "C" int offsim_eval_queue(const offsim_table *t, offsim_rollouts *ro, int
     offsim_td tdv;
     memset(&tdv, 0, sizeof(tdv));
     if (td) tdv = *td;
-    QueueArgs qa;
-    qa.tie_reseed = tie_reseed_episode;
-    qa.episode0 = (uint32_t)episode0;
-    qa.obs_row = out_obs_row;
+    const QueueArgs qa{tie_reseed_episode, (uint32_t)episode0, out_obs_row};
     if (td) return queue_launch<true>(t, ro, pi, gamma, gamma_pow, n_gamma_pow, max_episodes, out, tdv, qa, waves, lds, stream);
     return queue_launch<false>(t, ro, pi, gamma, gamma_pow, n_gamma_pow, max_episodes, out, tdv, qa, waves, lds, stream);
 }
 
-// ---- offsim_eval_queue's learner drivers for L learners on the same S seeds in one launch (k_eval_queue<TD, POP>, csrc/td_pop_queue.hpp): every
+// ---- offsim_eval_queue's learner drivers for L learners on the same S seeds in one launch (k_eval_queue<TD, POP>, csrc/td_pop.hpp): every
 // learner has its own hyper-parameters, behaviour and target policy; the queue orders are the seeds', shared by all learners and only read.
 extern "C" int offsim_eval_queue_pop(const offsim_table *t, offsim_rollouts *ro, int32_t nA_actions, int32_t L, int32_t S, const offsim_td_pop *pop,
                                      int64_t max_episodes, const offsim_evalmc_out *out, int32_t tie_reseed_episode, int64_t episode0,
@@ -410,19 +401,6 @@ extern "C" int offsim_eval_queue_pop(const offsim_table *t, offsim_rollouts *ro,
     size_t lds = 0;
     if ((rc = queue_launch_shape(who, t, pop->pi != nullptr, true, &waves, &lds))) return rc;
     if (ro->R == 0) return OFFSIM_OK;
-    QueuePopArgs qa{};
-    qa.tie_reseed = tie_reseed_episode;
-    qa.episode0 = (uint32_t)episode0;
-    qa.obs_row = out_obs_row;
-    qa.S = S;
-    qa.alpha = pop->alpha;
-    qa.epsilon = pop->epsilon;
-    qa.gamma = pop->gamma;
-    qa.gamma_pow = pop->gamma_pow;
-    qa.behaviour = pop->behaviour;
-    qa.alpha_ep = pop->alpha_ep;
-    qa.epsilon_ep = pop->epsilon_ep;
-    qa.pi = pop->pi;
-    qa.pi_stride = pop->pi_stride;
+    const QueuePopArgs qa{QueueArgs{tie_reseed_episode, (uint32_t)episode0, out_obs_row}, td_pop_fields(pop, S)};
     return queue_launch<true, true>(t, ro, nullptr, 0.0, nullptr, pop->n_gamma_pow, max_episodes, out, td, qa, waves, lds, stream);
 }

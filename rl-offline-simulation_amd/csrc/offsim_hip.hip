@@ -976,6 +976,8 @@ struct RowPolicyPopArgs : RowPolicyArgs {
 template <bool TD, bool POP>
 using RowArgs = std::conditional_t<!POP, RowPolicyArgs, std::conditional_t<TD, TdPopArgs, RowPolicyPopArgs>>;
 
+// The learner blocks around the step (POP prologue and index, tie stream, TD update, episode close, outputs) are written out in each of the three
+// rollout kernels: called as shared inline functions they changed every instance's code (profiles/td_learner_one_definition/isa_compare.txt).
 template <typename PL, typename PROB, bool TD, bool ROWP = false, bool POP = false>
 __global__ void __launch_bounds__(256, 4) k_eval_mc(offsim_table t, offsim_rollouts ro, const PROB *__restrict__ pi,
                                                  int reject_mode, double gamma, const double *__restrict__ gamma_pow,
@@ -1215,21 +1217,30 @@ static int check_evalmc_out(const char *who, const offsim_evalmc_out *out, const
     if (n_gamma_pow > 0 && !gamma_pow) return fail(OFFSIM_EINVAL, "%s: gamma_pow is NULL", who);
     return OFFSIM_OK;
 }
-// ... and the launch: 4 rollouts per workgroup, halved until the LDS carve fits 64 KiB; up to 160 KiB with one rollout.
+// ... the launch shape of every whole-rollout kernel (k_eval_mc, k_eval_mc_exo, k_eval_queue): 4 rollouts per workgroup, halved until the LDS
+// carve lds_bytes(waves) fits 64 KiB; up to 160 KiB with one rollout (false: beyond) ...
+template <typename F>
+static bool launch_shape(F &&lds_bytes, int *waves_out, size_t *lds_out) {
+    int waves = 4;
+    while (waves > 1 && lds_bytes(waves) > 64 * 1024) waves >>= 1;
+    *waves_out = waves;
+    *lds_out = lds_bytes(waves);
+    return *lds_out <= 160 * 1024;
+}
+// ... and the launch
 template <typename PL, typename PROB, bool TD, bool ROWP, bool POP = false>
 static int evalmc_launch(const char *who, const offsim_table *t, offsim_rollouts *ro, const void *pi, int32_t reject_mode, double gamma,
                          const double *gamma_pow, int64_t n_gamma_pow, int64_t max_episodes, const offsim_evalmc_out *out, const offsim_td &td,
                          const RowArgs<TD, POP> &rp, void *stream) {
     const size_t pb = ROWP ? 0 : sizeof(PROB);  // (ROWP: no pi block)
-    int waves = 4;
-    while (waves > 1 && evalmc_lds_bytes(waves, t->n_slots, t->nA, pb, TD) > 64 * 1024) waves >>= 1;
-    const size_t lds = evalmc_lds_bytes(waves, t->n_slots, t->nA, pb, TD);
-    if (lds > 160 * 1024)
+    int waves = 0;
+    size_t lds = 0;
+    if (!launch_shape([&](int w) { return evalmc_lds_bytes(w, t->n_slots, t->nA, pb, TD); }, &waves, &lds))
         return fail(OFFSIM_EUNSUPPORTED, TD ? "%s: Q table, cursors and policy exceed 160 KiB of LDS" : ROWP ? "%s: per-state cursors exceed 160 KiB of LDS"
                                                                                                               : "%s: per-state cursors and policy exceed 160 KiB of LDS", who);
     if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_eval_mc<PL, PROB, TD, ROWP, POP>), (int)lds));
     unsigned grid = (unsigned)((ro->R + waves - 1) / waves);
-    if constexpr (TD && POP) grid = (unsigned)(ro->R / rp.S) * (unsigned)((rp.S + waves - 1) / waves);  // a workgroup holds rollouts of one learner
+    if constexpr (TD && POP) grid = pop_grid(ro->R, rp.S, waves);
     hipLaunchKernelGGL((k_eval_mc<PL, PROB, TD, ROWP, POP>), dim3(grid), dim3(waves * WAVE), lds, (hipStream_t)stream, *t, *ro,
                        (const PROB *)pi, reject_mode, gamma, gamma_pow, n_gamma_pow, max_episodes, *out, td, rp);
     LAUNCH_CHECK();
@@ -1773,6 +1784,22 @@ extern "C" int offsim_step_exo(const offsim_table *ts, const offsim_table *tx, o
     });
 }
 
+// The learner rules of the six learner entry points, in the order every one of them checks those it has (`rules`: which).  The entry points do not
+// agree on all of them -- offsim_eval_td / _td_pop accept a negative td_cap, offsim_eval_mc_exo looks at alpha_ep only -- and which check
+// fails first is part of what they return, so an entry point with a rule of its own between two of these calls check_td around it.
+enum { TD_RULE_MODE = 1, TD_RULE_BEHAVIOUR = 2, TD_RULE_SCHED = 4, TD_RULE_SCHED_ALPHA = 8, TD_RULE_CAP = 16, TD_RULE_SNAP = 32,
+       TD_RULES = TD_RULE_MODE | TD_RULE_BEHAVIOUR | TD_RULE_SCHED | TD_RULE_CAP | TD_RULE_SNAP };
+static int check_td(const char *who, const offsim_td *td, unsigned rules) {
+    if ((rules & TD_RULE_MODE) && ((td->mode != OFFSIM_TD_QLEARN && td->mode != OFFSIM_TD_EXPSARSA) || !td->q)) return fail(OFFSIM_EINVAL, "%s: bad td mode or NULL q", who);
+    if ((rules & TD_RULE_BEHAVIOUR) && td->behaviour != OFFSIM_BEHAVIOUR_FIXED && td->behaviour != OFFSIM_BEHAVIOUR_EPS_GREEDY && td->behaviour != OFFSIM_BEHAVIOUR_SOFT_GREEDY)
+        return fail(OFFSIM_EINVAL, "%s: bad behaviour", who);
+    if ((((rules & (TD_RULE_SCHED | TD_RULE_SCHED_ALPHA)) && td->alpha_ep) || ((rules & TD_RULE_SCHED) && td->epsilon_ep)) && td->n_sched <= 0)
+        return fail(OFFSIM_EINVAL, "%s: schedules need n_sched > 0", who);
+    if ((rules & TD_RULE_CAP) && td->td_cap < 0) return fail(OFFSIM_EINVAL, "%s: negative td_cap", who);
+    if ((rules & TD_RULE_SNAP) && td->q_snap && (td->snap_stride <= 0 || td->snap_cap < 0)) return fail(OFFSIM_EINVAL, "%s: bad snapshot stride / capacity", who);
+    return OFFSIM_OK;
+}
+
 // qlearn_psrs / expSARSA_psrs (psrs.py:119-239) with a state-independent behaviour policy: evalMC's loop plus the
 // tabular TD update, all R rollouts in one launch (generic 64-candidate step; f64 probabilities).
 extern "C" int offsim_eval_td(const offsim_table *t, offsim_rollouts *ro, const double *pi, int32_t reject_mode, double gamma,
@@ -1782,11 +1809,7 @@ extern "C" int offsim_eval_td(const offsim_table *t, offsim_rollouts *ro, const 
     if (rc) return rc;
     if (!ro || ro->R < 0 || !pi || !out || !td) return fail(OFFSIM_EINVAL, "eval_td: bad argument%s");
     if ((rc = check_evalmc_out("eval_td", out, gamma_pow, n_gamma_pow))) return rc;
-    if ((td->mode != OFFSIM_TD_QLEARN && td->mode != OFFSIM_TD_EXPSARSA) || !td->q) return fail(OFFSIM_EINVAL, "eval_td: bad td mode or NULL q%s");
-    if (td->behaviour != OFFSIM_BEHAVIOUR_FIXED && td->behaviour != OFFSIM_BEHAVIOUR_EPS_GREEDY && td->behaviour != OFFSIM_BEHAVIOUR_SOFT_GREEDY)
-        return fail(OFFSIM_EINVAL, "eval_td: bad behaviour%s");
-    if ((td->alpha_ep || td->epsilon_ep) && td->n_sched <= 0) return fail(OFFSIM_EINVAL, "eval_td: schedules need n_sched > 0%s");
-    if (td->q_snap && (td->snap_stride <= 0 || td->snap_cap < 0)) return fail(OFFSIM_EINVAL, "eval_td: bad snapshot stride / capacity%s");
+    if ((rc = check_td("eval_td", td, TD_RULES & ~TD_RULE_CAP))) return rc;  // (a negative td_cap is not refused here)
     if (ro->R == 0) return OFFSIM_OK;
     return with_plog(t, [&](auto pl) -> int {
         return evalmc_launch<decltype(pl), double, true, false>("eval_td", t, ro, pi, reject_mode, gamma, gamma_pow, n_gamma_pow, max_episodes, out, *td,
@@ -1794,23 +1817,7 @@ extern "C" int offsim_eval_td(const offsim_table *t, offsim_rollouts *ro, const 
     });
 }
 
-// What the population entry points (offsim_eval_td_pop, offsim_eval_td_exo_pop, offsim_eval_queue_pop) check about L, S, R = L * S and struct offsim_td_pop ...
-// (pi_optional: offsim_eval_queue_pop, which decides itself whether a NULL pi serves its learners)
-static int check_td_pop(const char *who, int32_t L, int32_t S, int64_t R, const offsim_td_pop *pop, bool pi_optional = false) {
-    if (L < 1 || L > 65535 || S < 1) return fail(OFFSIM_EINVAL, "%s: L must be 1..65535 and S >= 1", who);
-    if (R != 0 && R != (int64_t)L * S) return fail(OFFSIM_EINVAL, "%s: ro->R must be L * S", who);
-    if ((pop->mode != OFFSIM_TD_QLEARN && pop->mode != OFFSIM_TD_EXPSARSA) || !pop->q) return fail(OFFSIM_EINVAL, "%s: bad td mode or NULL q", who);
-    if (!pop->alpha || !pop->epsilon || !pop->gamma || !pop->behaviour || !pop->behaviour_host || (!pop->pi && !pi_optional) || pop->pi_stride < 0 || pop->n_gamma_pow < 0)
-        return fail(OFFSIM_EINVAL, "%s: a per-learner array is NULL (alpha, epsilon, gamma, behaviour and its host copy, pi)", who);
-    for (int32_t l = 0; l < L; l++) {
-        const int32_t b = pop->behaviour_host[l];
-        if (b != OFFSIM_BEHAVIOUR_FIXED && b != OFFSIM_BEHAVIOUR_EPS_GREEDY && b != OFFSIM_BEHAVIOUR_SOFT_GREEDY) return fail(OFFSIM_EINVAL, "%s: bad behaviour", who);
-    }
-    if ((pop->alpha_ep || pop->epsilon_ep) && pop->n_sched <= 0) return fail(OFFSIM_EINVAL, "%s: schedules need n_sched > 0", who);
-    if (pop->q_snap && (pop->snap_stride <= 0 || pop->snap_cap < 0)) return fail(OFFSIM_EINVAL, "%s: bad snapshot stride / capacity", who);
-    return OFFSIM_OK;
-}
-// ... and the launch's offsim_td -- per rollout: the members of offsim_td as they are; per learner: filled in by the kernel from its arguments
+// The launch's offsim_td of a population -- per rollout: the members of offsim_td as they are; per learner: filled in by the kernel from its arguments
 static offsim_td td_of_pop(const offsim_td_pop *pop) {
     offsim_td td{};
     td.mode = pop->mode;
@@ -1825,6 +1832,24 @@ static offsim_td td_of_pop(const offsim_td_pop *pop) {
     td.beh_arg = pop->beh_arg;
     return td;
 }
+// What the population entry points (offsim_eval_td_pop, offsim_eval_td_exo_pop, offsim_eval_queue_pop) check about L, S, R = L * S and struct offsim_td_pop
+// (pi_optional: offsim_eval_queue_pop, which decides itself whether a NULL pi serves its learners)
+static int check_td_pop(const char *who, int32_t L, int32_t S, int64_t R, const offsim_td_pop *pop, bool pi_optional = false) {
+    if (L < 1 || L > 65535 || S < 1) return fail(OFFSIM_EINVAL, "%s: L must be 1..65535 and S >= 1", who);
+    if (R != 0 && R != (int64_t)L * S) return fail(OFFSIM_EINVAL, "%s: ro->R must be L * S", who);
+    offsim_td td = td_of_pop(pop);  // (with each learner's members in turn: the learner rules are check_td's)
+    td.alpha_ep = pop->alpha_ep;
+    td.epsilon_ep = pop->epsilon_ep;
+    int rc = check_td(who, &td, TD_RULE_MODE);
+    if (rc) return rc;
+    if (!pop->alpha || !pop->epsilon || !pop->gamma || !pop->behaviour || !pop->behaviour_host || (!pop->pi && !pi_optional) || pop->pi_stride < 0 || pop->n_gamma_pow < 0)
+        return fail(OFFSIM_EINVAL, "%s: a per-learner array is NULL (alpha, epsilon, gamma, behaviour and its host copy, pi)", who);
+    for (int32_t l = 0; l < L; l++) {
+        td.behaviour = pop->behaviour_host[l];
+        if ((rc = check_td(who, &td, TD_RULE_BEHAVIOUR))) return rc;
+    }
+    return check_td(who, &td, TD_RULE_SCHED | TD_RULE_SNAP);
+}
 
 // ---- offsim_eval_td for L learners on the same S seeds in one launch (k_eval_mc<.., TD, false, POP>, csrc/td_pop.hpp): every learner has its
 // own hyper-parameters, behaviour and target policy; the queue orders are the seeds', shared by all learners and only read.
@@ -1837,17 +1862,7 @@ extern "C" int offsim_eval_td_pop(const offsim_table *t, offsim_rollouts *ro, in
     if ((rc = check_evalmc_out(who, out, pop->gamma_pow, pop->n_gamma_pow)) || (rc = check_td_pop(who, L, S, ro->R, pop))) return rc;
     if (ro->R == 0) return OFFSIM_OK;
     const offsim_td td = td_of_pop(pop);
-    TdPopArgs rp{};
-    rp.S = S;
-    rp.alpha = pop->alpha;
-    rp.epsilon = pop->epsilon;
-    rp.gamma = pop->gamma;
-    rp.gamma_pow = pop->gamma_pow;
-    rp.behaviour = pop->behaviour;
-    rp.alpha_ep = pop->alpha_ep;
-    rp.epsilon_ep = pop->epsilon_ep;
-    rp.pi = pop->pi;
-    rp.pi_stride = pop->pi_stride;
+    const TdPopArgs rp{RowPolicyArgs{}, td_pop_fields(pop, S)};
     return with_plog(t, [&](auto pl) -> int {
         return evalmc_launch<decltype(pl), double, true, false, true>(who, t, ro, nullptr, reject_mode, 0.0, nullptr, pop->n_gamma_pow, max_episodes, out, td,
                                                                       rp, stream);

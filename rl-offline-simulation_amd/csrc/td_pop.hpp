@@ -13,15 +13,37 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-struct TdPopArgs : RowPolicyArgs {  // (the row-policy members stay NULL: the learner drivers index their tables by state)
+// The index rule is the same for the three learner kernels (k_eval_mc, k_eval_mc_exo, k_eval_queue; each applies it in its own text, see the
+// note above each kernel): the waves past S leave after the staging barrier, and rollout (l, j) walks queue orders j of every queue family
+// while its streams, cursors, current state and outputs are row r's own.
+//
+// The per-learner kernel arguments: what offsim_td_pop holds per learner, filled by td_pop_fields.  Every POP instance carries them behind
+// its kernel's own argument struct, so the arguments of the other instances are what they were.
+struct TdPopFields {
     int32_t S;
     const double *alpha, *epsilon, *gamma;  // [L]
     const double *gamma_pow;                // [L, n_gamma_pow]
     const int32_t *behaviour;               // [L]
     const double *alpha_ep, *epsilon_ep;    // [L, n_sched] or NULL
-    const double *pi;                       // [L, n_slots, nA], or one table when pi_stride == 0
+    const double *pi;                       // [L, rows, nA], or one table when pi_stride == 0 (k_eval_queue: NULL when no learner reads one)
     int64_t pi_stride;
 };
+static TdPopFields td_pop_fields(const offsim_td_pop *pop, int32_t S) {
+    return TdPopFields{S, pop->alpha, pop->epsilon, pop->gamma, pop->gamma_pow, pop->behaviour, pop->alpha_ep, pop->epsilon_ep, pop->pi, pop->pi_stride};
+}
+// the grid of a POP launch of R = L * S rollouts: a workgroup holds rollouts of one learner
+static unsigned pop_grid(int64_t R, int32_t S, int waves) { return (unsigned)(R / S) * (unsigned)((S + waves - 1) / waves); }
+// the kernel-argument layout of a POP instance must not move: pinned next to each struct
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"  // (two bases: not standard-layout; laid out base after base)
+template <typename ARGS>
+constexpr bool td_pop_layout(size_t size, size_t s_at, size_t pi_stride_at) {
+    return sizeof(ARGS) == size && offsetof(ARGS, S) == s_at && offsetof(ARGS, pi_stride) == pi_stride_at;
+}
+#pragma clang diagnostic pop
+
+struct TdPopArgs : RowPolicyArgs, TdPopFields {};  // (the row-policy members stay NULL: the learner drivers index their tables by state)
+static_assert(td_pop_layout<TdPopArgs>(104, 24, 96), "kernel arguments of k_eval_mc<.., TD, false, POP>");
 
 // curve of learner l at episode e over the seeds that completed it: one thread per (l, e), the seeds in order j = 0 .. S - 1, two passes,
 // no atomics -- the sums are a plain left-to-right f64 loop, so two calls give the same bits and a host loop in that order gives them too

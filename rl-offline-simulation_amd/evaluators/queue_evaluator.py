@@ -7,7 +7,7 @@ pop one" rule: offsim_group_by_state / offsim_shuffle_queues / offsim_env_set_st
 Whole rollouts -- the reference's tabular drivers evalMC / qlearn / expSARSA (offsim4rl/agents/tabular.py), which draw the action
 themselves and pop one row per step -- run in offsim_eval_queue (csrc/eval_queue.hpp), one launch: BatchedQueueEvaluator.eval_mc /
 eval_td, evalmc_rollouts_queue for many sampler seeds, and the drop-ins evalMC_queue / qlearn_queue / expSARSA_queue on a QueueEvaluator.
-Many learners on the same seeds in one launch (offsim_eval_queue_pop, csrc/td_pop_queue.hpp): BatchedQueueEvaluator.eval_td_population,
+Many learners on the same seeds in one launch (offsim_eval_queue_pop, csrc/td_pop.hpp): BatchedQueueEvaluator.eval_td_population,
 driven over seed tiles by TDPopulation.run_queue (evaluators/td_population.py).
 """
 import ctypes as C

@@ -147,6 +147,41 @@ class TDPopulation:
         out = table.policy_slots(x) if x.ndim == 2 else np.stack([table.policy_slots(v) for v in x])
         return out if nan is None else np.nan_to_num(out, nan=nan)
 
+    def _seeds(self, who, seeds):
+        seeds = np.asarray(seeds, dtype=np.uint64)
+        if len(seeds) < 1:
+            raise ValueError(f"TDPopulation.{who}: no seed")
+        return seeds, len(seeds)
+
+    def _run_tiles(self, who, seeds, N0, n_episodes, tile, make_env, launch, Q_of, tie=None, tie_one=True, tie_out=False, trace_cap=0):
+        """What run, run_exo and run_queue do alike once their tables are laid out: at most min(n_episodes, N0 + 1) episodes, the
+        schedules and behaviour codes, the tie states -- `tie` [L,S,625], or with tie_one one [625] every rollout starts from; a string or
+        None passes through -- then per tile of `tile` seeds make_env(n), launch(env, b, sd, tie of the tile, hp) with hp the keyword
+        arguments every eval_td_population takes, and the fault check; the tiles concatenated along the seeds, Q_of(q) the launch's Q
+        rows back by the caller's row ids, and offsim_td_curves over all seeds (_result)."""
+        S, n_l = len(seeds), self.L
+        n_ep = int(min(n_episodes if n_episodes is not None else N0 + 1, N0 + 1))
+        ep_cap = max(n_ep, 1)
+        a_const, e_const, a_tab, e_tab = self.tabulate(n_ep)
+        hp = dict(mode=self.mode, alpha=a_const, gamma=self.gamma, behaviour=np.array([_BEHAVIOUR[b] for b in self.behaviour], dtype=np.int32),
+                  epsilon=e_const, alpha_ep=a_tab, epsilon_ep=e_tab, n_episodes=n_ep, ep_cap=ep_cap, trace_cap=int(trace_cap))
+        states = tie is not None and not isinstance(tie, str)
+        if states:
+            tie = tie_stream(tie)
+            if tie_one and tuple(tie.shape) == (625,):
+                tie = tie.expand(n_l, S, 625)
+            if tuple(tie.shape) != (n_l, S, 625):
+                raise ValueError(f"TDPopulation.{who}: tie_mt {'[625] or ' if tie_one else ''}[L,S,625] = {(n_l, S, 625)} expected, got {tuple(tie.shape)}")
+        keys = ["q", "ep_g", "n_ep", "steps", "status"] + (["td_err"] if trace_cap else []) + (["tie_mt"] if tie_out else [])
+        parts = {k: [] for k in keys}
+        for b, sd, env in seed_tiles(seeds, int(tile(S) if callable(tile) else tile), make_env):
+            o = launch(env, b, sd, tie[:, b:b + len(sd)] if states else tie, hp)
+            for k in keys:
+                parts[k].append(o[k])
+            BatchedPSRS.check_faults()
+        res = {k: v[0] if len(v) == 1 else torch.cat(v, dim=1).contiguous() for k, v in parts.items()}
+        return self._result(res, Q_of(res["q"]), ep_cap)
+
     def run(self, table, seeds, n_episodes=None, shuffle=SHUFFLE_PER_ROLLOUT, tile=None, tie_mt=None, rejection="pcg64", shuffle_seed=None,
             trace_cap=0, reject_mode=L.REJECT_DEFAULT):
         """Every learner on every seed.  One reset_sampler per tile of `tile` seeds (default: resident_rollouts(keyed=False), as
@@ -154,38 +189,23 @@ class TDPopulation:
         launch per tile, then offsim_td_curves over all seeds.  n_episodes: at most that many episodes per learner and seed (None: until
         the log ends).  tie_mt [L,S,625]: NumPy MT19937 states for ties between maximal Q values (None: the first maximum).
         trace_cap > 0 also returns the TD errors of the first trace_cap steps."""
-        seeds = np.asarray(seeds, dtype=np.uint64)
-        S, n_l, dev = len(seeds), self.L, table.device
-        if S < 1:
-            raise ValueError("TDPopulation.run: no seed")
-        n_ep = int(min(n_episodes if n_episodes is not None else table.N0 + 1, table.N0 + 1))
-        ep_cap = max(n_ep, 1)
-        a_const, e_const, a_tab, e_tab = self.tabulate(n_ep)
+        seeds, S = self._seeds("run", seeds)
         nS = self._n_rows(table)
         Q0 = np.zeros((nS, table.nA)) if self.Q_init is None else self.Q_init
         pi = np.full((nS, table.nA), 1.0 / table.nA) if self.pi is None else self.pi
         if table.N and pi.shape[-2] <= int(table.slot_z.max()):
             raise IndexError("pi has no row for some latent state")
         pi_slots, q_slots = self._slots(table, pi), self._slots(table, Q0, nan=0.0)
-        beh = np.array([_BEHAVIOUR[b] for b in self.behaviour], dtype=np.int32)
-        if tie_mt is not None:
-            tie_mt = tie_stream(tie_mt)
-            if tuple(tie_mt.shape) != (n_l, S, 625):
-                raise ValueError(f"TDPopulation.run: tie_mt [L,S,625] = {(n_l, S, 625)} expected, got {tuple(tie_mt.shape)}")
-        if tile is None:
-            tile = default_tile(table, S, shuffle, keyed=False)
-        keys = ["q", "ep_g", "n_ep", "steps", "status"] + (["td_err"] if trace_cap else [])
-        parts = {k: [] for k in keys}
-        for b, sd, env in seed_tiles(seeds, int(tile), lambda n: BatchedPSRS(table, n, reject_mode)):
+
+        def launch(env, b, sd, tie, hp):
             env.reset_sampler(sd, shuffle, shuffle_seed, rejection=rejection)
-            o = env.eval_td_population(self.mode, a_const, self.gamma, beh, e_const, pi_slots=pi_slots, q_slots=q_slots, alpha_ep=a_tab,
-                                       epsilon_ep=e_tab, tie_mt=None if tie_mt is None else tie_mt[:, b:b + len(sd)], n_episodes=n_ep, ep_cap=ep_cap,
-                                       trace_cap=int(trace_cap))
-            for k in keys:
-                parts[k].append(o[k])
-            env.check_faults()
-        res = {k: v[0] if len(v) == 1 else torch.cat(v, dim=1).contiguous() for k, v in parts.items()}
-        return self._result(res, self._q_by_state(table, res["q"], Q0), ep_cap)
+            return env.eval_td_population(pi_slots=pi_slots, q_slots=q_slots, tie_mt=tie, **hp)
+
+        # slot s goes to row slot_z[s] (the rule of psrs._slots_to_q)
+        return self._run_tiles("run", seeds, table.N0, n_episodes, (lambda S: default_tile(table, S, shuffle, keyed=False)) if tile is None else tile,
+                               lambda n: BatchedPSRS(table, n, reject_mode), launch,
+                               lambda q: self._rows_into(Q0, q, [table.z_of(s) for s in range(table.n_slots)], range(table.n_slots), self.L, S),
+                               tie=tie_mt, tie_one=False, trace_cap=trace_cap)
 
     def _result(self, res, Q, ep_cap):
         """The TDPopulationResult of the concatenated tiles `res` ([L, S, ...]): offsim_td_curves over all seeds."""
@@ -215,10 +235,7 @@ class TDPopulation:
         for a pair of tables: the compact rows)."""
         from .psrs_exo import PSRS_Exo, BatchedPSRSExo
         from .batched import rollout_resident_bytes, resident_rollouts
-        seeds = np.asarray(seeds, dtype=np.uint64)
-        S, n_l = len(seeds), self.L
-        if S < 1:
-            raise ValueError("TDPopulation.run_exo: no seed")
+        seeds, S = self._seeds("run_exo", seeds)
         given = next((x for x in (self.Q_init, self.pi) if x is not None), None)
         if isinstance(env_or_tables, PSRS_Exo):
             ts, tx = env_or_tables.ts, env_or_tables.tx
@@ -236,35 +253,18 @@ class TDPopulation:
                 raise ValueError(f"TDPopulation.run_exo: {k} [nO,nA] = {(nO, ts.nA)} expected, got {x.shape}")
         Q0 = np.zeros((nO, ts.nA)) if self.Q_init is None else self.Q_init
         pi = np.full((nO, ts.nA), 1.0 / ts.nA) if self.pi is None else self.pi
-        n_ep = int(min(n_episodes if n_episodes is not None else ts.N0 + 1, ts.N0 + 1))
-        ep_cap = max(n_ep, 1)
-        a_const, e_const, a_tab, e_tab = self.tabulate(n_ep)
-        beh = np.array([_BEHAVIOUR[b] for b in self.behaviour], dtype=np.int32)
-        if tie_mt is not None:
-            tie_mt = tie_stream(tie_mt)
-            if tuple(tie_mt.shape) == (625,):
-                tie_mt = tie_mt.expand(n_l, S, 625)
-            if tuple(tie_mt.shape) != (n_l, S, 625):
-                raise ValueError(f"TDPopulation.run_exo: tie_mt [625] or [L,S,625] = {(n_l, S, 625)} expected, got {tuple(tie_mt.shape)}")
-        if tile is None:
+
+        def default(S):
             n_res, per_s = resident_rollouts(ts, keyed=False)[:2]
-            tile = max(1, min(S, n_res * per_s // (per_s + rollout_resident_bytes(tx, keyed=False))))
-        keys = ["q", "ep_g", "n_ep", "steps", "status"] + (["td_err"] if trace_cap else []) + (["tie_mt"] if tie_mt is not None else [])
-        parts = {k: [] for k in keys}
-        for b, sd, env in seed_tiles(seeds, int(tile), lambda n: BatchedPSRSExo(ts, tx, n)):
+            return max(1, min(S, n_res * per_s // (per_s + rollout_resident_bytes(tx, keyed=False))))
+
+        def launch(env, b, sd, tie, hp):
             env.reset_sampler(sd, rejection=rejection)
-            o = env.eval_td_population(self.mode, a_const, self.gamma, obs_of, beh, e_const, pi_obs=pi[..., ids, :], q_obs=Q0[..., ids, :], alpha_ep=a_tab,
-                                       epsilon_ep=e_tab, n_episodes=n_ep, reseed=reseed, ep_cap=ep_cap, trace_cap=int(trace_cap),
-                                       tie_mt=None if tie_mt is None else tie_mt[:, b:b + len(sd)])
-            for k in keys:
-                parts[k].append(o[k])
-            BatchedPSRS.check_faults()
-        res = {k: v[0] if len(v) == 1 else torch.cat(v, dim=1).contiguous() for k, v in parts.items()}
-        dev = res["q"].device
-        q0 = torch.from_numpy(np.ascontiguousarray(Q0, dtype=np.float64)).to(dev)
-        Q = (q0[:, None] if q0.dim() == 3 else q0[None, None]).expand(n_l, S, nO, ts.nA).contiguous().clone()
-        Q[:, :, torch.from_numpy(np.asarray(ids, dtype=np.int64)).to(dev)] = res["q"]
-        return self._result(res, Q, ep_cap)
+            return env.eval_td_population(obs_of=obs_of, pi_obs=pi[..., ids, :], q_obs=Q0[..., ids, :], reseed=reseed, tie_mt=tie, **hp)
+
+        return self._run_tiles("run_exo", seeds, ts.N0, n_episodes, default if tile is None else tile, lambda n: BatchedPSRSExo(ts, tx, n), launch,
+                               lambda q: self._rows_into(Q0, q, ids, range(len(ids)), self.L, S), tie=tie_mt, tie_out=tie_mt is not None,
+                               trace_cap=trace_cap)
 
     def run_queue(self, env_or_arrays, seeds, n_episodes=None, action_seeds=None, tie="episode", episode0=0, tile=None, trace_cap=0):
         """Every learner on every seed of the queue simulator (QueueEvaluator: queues keyed by (z, a), the agent draws its own action;
@@ -280,10 +280,7 @@ class TDPopulation:
         Returns a TDPopulationResult with Q [L,S,nS,nA] by caller state id (rows without a state keep Q_init's values), tie_mt [L,S,625]
         whenever a stream ran, td_err with trace_cap.  OFFSIM_ST_KEYERROR / _EXHAUSTED do not raise: they are in result.status."""
         from .queue_evaluator import BatchedQueueEvaluator, QueueEvaluator
-        seeds = np.asarray(seeds, dtype=np.uint64)
-        S, n_l = len(seeds), self.L
-        if S < 1:
-            raise ValueError("TDPopulation.run_queue: no seed")
+        seeds, S = self._seeds("run_queue", seeds)
         action_seeds = seeds if action_seeds is None else np.asarray(action_seeds, dtype=np.uint64)
         if len(action_seeds) != S:
             raise ValueError("TDPopulation.run_queue: one action seed per sampler seed (action_seeds)")
@@ -303,56 +300,30 @@ class TDPopulation:
         Q0 = np.zeros((nS, nA)) if self.Q_init is None else self.Q_init
         rows = lambda x, fill: probe.state_rows(x, fill) if x.ndim == 2 else np.stack([probe.state_rows(v, fill) for v in x])  # noqa: E731
         pi_rows, q_rows = None if self.pi is None else rows(self.pi, np.nan), rows(Q0, 0.0)
-        n_ep = int(min(n_episodes if n_episodes is not None else t.N0 + 1, t.N0 + 1))
-        ep_cap = max(n_ep, 1)
-        a_const, e_const, a_tab, e_tab = self.tabulate(n_ep)
-        beh = np.array([_BEHAVIOUR[b] for b in self.behaviour], dtype=np.int32)
-        if not isinstance(tie, str):
-            tie = tie_stream(tie)
-            if tuple(tie.shape) == (625,):
-                tie = tie.expand(n_l, S, 625)
-            if tuple(tie.shape) != (n_l, S, 625):
-                raise ValueError(f"TDPopulation.run_queue: tie_mt [625] or [L,S,625] = {(n_l, S, 625)} expected, got {tuple(tie.shape)}")
-        elif tie not in ("episode", "first"):
+        if isinstance(tie, str) and tie not in ("episode", "first"):
             raise ValueError(f"TDPopulation.run_queue: tie must be 'episode', 'first' or MT19937 states, got {tie!r}")
-        if tile is None:
-            tile = default_tile(t, S, SHUFFLE_PER_ROLLOUT, keyed=False)
-        keys = ["q", "ep_g", "n_ep", "steps", "status"] + (["td_err"] if trace_cap else []) + (["tie_mt"] if not (isinstance(tie, str) and tie == "first") else [])
-        parts = {k: [] for k in keys}
-        for b, sd, env in seed_tiles(seeds, int(tile), lambda n: BatchedQueueEvaluator(*arrays, R=n)):
+
+        def launch(env, b, sd, tie, hp):
             env.reset_sampler(sd)
             env.set_action_seeds(action_seeds[b:b + len(sd)])
-            o = env.eval_td_population(self.mode, a_const, self.gamma, beh, e_const, pi=pi_rows, q=q_rows, alpha_ep=a_tab, epsilon_ep=e_tab,
-                                       tie=tie if isinstance(tie, str) else tie[:, b:b + len(sd)], episode0=episode0, n_episodes=n_ep, ep_cap=ep_cap,
-                                       trace_cap=int(trace_cap))
-            for k in keys:
-                parts[k].append(o[k])
-            BatchedPSRS.check_faults()
-        res = {k: v[0] if len(v) == 1 else torch.cat(v, dim=1).contiguous() for k, v in parts.items()}
-        # rows_to_state on the device: row i of the table's states goes to row z_lo + i of Q0's copy (NumPy's wrap for a negative state)
-        dev = res["q"].device
-        q0 = torch.from_numpy(np.ascontiguousarray(Q0, dtype=np.float64)).to(dev)
-        Q = (q0[:, None] if q0.dim() == 3 else q0[None, None]).expand(n_l, S, nS, nA).contiguous().clone()
-        last = {(probe.z_lo + i) % nS: i for i in range(nZ) if -nS <= probe.z_lo + i < nS}
-        if last:
-            Q[:, :, torch.tensor(list(last.keys()), dtype=torch.int64, device=dev)] = res["q"][:, :, torch.tensor(list(last.values()), dtype=torch.int64, device=dev)]
-        return self._result(res, Q, ep_cap)
+            return env.eval_td_population(pi=pi_rows, q=q_rows, tie=tie, episode0=episode0, **hp)
+
+        # rows_to_state on the device: row i of the table's states goes to row z_lo + i of Q0's copy
+        return self._run_tiles("run_queue", seeds, t.N0, n_episodes, (lambda S: default_tile(t, S, SHUFFLE_PER_ROLLOUT, keyed=False)) if tile is None else tile,
+                               lambda n: BatchedQueueEvaluator(*arrays, R=n), launch,
+                               lambda q: self._rows_into(Q0, q, range(probe.z_lo, probe.z_lo + nZ), range(nZ), self.L, S), tie=tie,
+                               tie_out=not (isinstance(tie, str) and tie == "first"), trace_cap=trace_cap)
 
     @staticmethod
-    def _q_by_state(table, q_slots, Q0):
-        """q_slots [L,S,n_slots,nA] back into copies of Q0 [nS,nA] or [L,nS,nA] on the device, by the rule of psrs._slots_to_q: slot s goes
-        to row slot_z[s] with NumPy's negative-index wrap, the later slot winning a shared row; rows without a slot keep Q0's values."""
-        n_l, S = q_slots.shape[:2]
+    def _rows_into(Q0, q, dst_rows, src_rows, n_l, S):
+        """q [L,S,rows,nA], the launch's Q, back into copies of Q0 [nS,nA] or [L,nS,nA] on the device: row src_rows[i] of q goes to row
+        dst_rows[i] with NumPy's negative-index wrap, the later pair winning a shared row and a row outside [-nS, nS) dropped; rows
+        without a source keep Q0's values."""
         nS = Q0.shape[-2]
-        q0 = torch.from_numpy(np.ascontiguousarray(Q0, dtype=np.float64)).to(q_slots.device)
-        out = (q0[:, None] if q0.dim() == 3 else q0[None, None]).expand(n_l, S, nS, q_slots.shape[-1]).contiguous().clone()
-        last = {}
-        for s in range(table.n_slots):
-            z = table.z_of(s)
-            if -nS <= z < nS:
-                last[z % nS] = s
+        q0 = torch.from_numpy(np.ascontiguousarray(Q0, dtype=np.float64)).to(q.device)
+        out = (q0[:, None] if q0.dim() == 3 else q0[None, None]).expand(n_l, S, nS, q.shape[-1]).contiguous().clone()
+        last = {int(d) % nS: int(s) for d, s in zip(dst_rows, src_rows) if -nS <= d < nS}
         if last:
-            rows = torch.tensor(list(last.keys()), dtype=torch.int64, device=q_slots.device)
-            slots = torch.tensor(list(last.values()), dtype=torch.int64, device=q_slots.device)
-            out[:, :, rows] = q_slots[:, :, slots]
+            rows, src = (torch.tensor(list(v), dtype=torch.int64, device=q.device) for v in (last.keys(), last.values()))
+            out[:, :, rows] = q[:, :, src]
         return out
