@@ -573,6 +573,46 @@ int offsim_eval_queue_pop(const offsim_table *t, offsim_rollouts *ro, int32_t nA
                           int64_t max_episodes, const offsim_evalmc_out *out, int32_t tie_reseed_episode, int64_t episode0,
                           int32_t *out_obs_row, void *stream);
 
+/* offsim_eval_queue_rows_policy: offsim_eval_queue's evalMC (tabular.py:247-270 on queue_evaluator.py:113-131) for a policy over OBSERVATIONS
+ * (the PPO actor of offsim4rl/agents/ppo.py:258-279), all rollouts in ONE launch (csrc/eval_queue_rows.hpp).  What offsim_eval_mc_rows_policy is
+ * to offsim_eval_mc, on QueueEvaluator: the policy is two per-row tables,
+ *   p_next [N,nA]  the policy at next_obs of GROUPED row g (table order: caller row orig_idx[g]),
+ *   p_init [N0,nA] the policy at obs of initial row k (caller row init_orig[k]),
+ *   p_dtype        their element type, OFFSIM_F32 or OFFSIM_F64; a row is widened exactly to f64 before the draw.
+ * t, ro, nA_actions, gamma, gamma_pow, max_episodes, out, out_obs_row and the status codes are offsim_eval_queue's (the action stream is
+ * OFFSIM_STREAM_PCG64; OFFSIM_STREAM_PHILOX is refused with OFFSIM_EUNSUPPORTED).  Per step p = p_init[k] right after a reset that popped
+ * initial row k, p_next[g] after a served row g; A = Generator.choice(nA, p=p) exactly as offsim_eval_queue draws it (one definition on the
+ * device), one draw per step; a row without a cdf entry above u (NaN, all zeros): OFFSIM_ST_KEYERROR; trace_pop holds the action drawn.
+ *   cur_row [R] (optional, written on exit): the table row that holds the policy at the state the rollout stands in -- g >= 0 the last
+ *   served GROUPED row, -2 - k initial row k with no step since, -1 none (no initial row left); left as it was when the loop ran no reset.
+ *   It is never read: every episode of every call begins with env.reset() (tabular.py:255), exactly as in offsim_eval_queue, so no rollout
+ *   ever continues an episode of an earlier call and none needs the row an earlier call stood at.  A rollout that stands inside an episode
+ *   on entry (after OFFSIM_ST_EXHAUSTED, or after steps taken through offsim_step_batch) starts its next episode like any other, with
+ *   cur_row NULL or not; there is no refusal.
+ * Identity: with p_next[g] = pi[z_next[g]] and p_init[k] = pi[z of initial row k] the call equals offsim_eval_queue's evalMC with that pi,
+ * bit for bit, in every output and in the state it leaves.
+ * LDS per workgroup: seg_off (n_slots + 1 words), per rollout the cursors (n_slots * 4) and the current row (nA * 8); 4 / 2 / 1 rollouts per
+ * workgroup against 64 KiB, one rollout up to 160 KiB, beyond that OFFSIM_EUNSUPPORTED.
+ * OFFSIM_EINVAL: everything offsim_eval_queue checks about the table, n_slots % nA, ro, out and the capacities; p_next NULL with N > 0 or
+ * p_init NULL with N0 > 0; a p_dtype other than the two.  Argument validation happens before any HIP call; ro->R = 0 launches nothing. */
+int offsim_eval_queue_rows_policy(const offsim_table *t, offsim_rollouts *ro, int32_t nA_actions, const void *p_next, const void *p_init,
+                                  int32_t p_dtype /* OFFSIM_F32 | OFFSIM_F64 */, double gamma, const double *gamma_pow, int64_t n_gamma_pow,
+                                  int64_t max_episodes, const offsim_evalmc_out *out, int32_t *cur_row, int32_t *out_obs_row, void *stream);
+
+/* offsim_eval_queue_rows_policy_pop: offsim_eval_queue_rows_policy for L policies on the same S seeds in ONE launch: every policy of a seed
+ * sees the same queues and starts from the same action stream, so differences between policies are paired.
+ *   p_next [L,N,nA], p_init [L,N0,nA]   the tables, stacked, contiguous.
+ *   ro->R = L * S, policy-major: rollout r evaluates policy r / S on seed index r % S.  ro->rng, cursor, init_cursor, cur_slot, the outputs,
+ *   cur_row and out_obs_row are [R] rows (the caller's S rows replicated L times), advanced and written per rollout.  ro->perm /
+ *   ro->init_perm hold S orders, not R: rollout r reads row r % S (stride 0: one shared order; NULL: table order).  They are only read.
+ * Identity: rollout l * S + j equals, in every output bit and in the state it leaves, offsim_eval_queue_rows_policy with policy l from seed
+ * j's state, order and action stream.  No per-policy data lives in LDS, so a workgroup may hold rollouts of different policies:
+ * grid = ceil(L * S / rollouts per workgroup).
+ * OFFSIM_EINVAL as offsim_eval_queue_rows_policy, and L outside 1..65535, S < 1 or ro->R != L * S. */
+int offsim_eval_queue_rows_policy_pop(const offsim_table *t, offsim_rollouts *ro, int32_t nA_actions, const void *p_next, const void *p_init,
+                                      int32_t p_dtype, int32_t L, int32_t S, double gamma, const double *gamma_pow, int64_t n_gamma_pow,
+                                      int64_t max_episodes, const offsim_evalmc_out *out, int32_t *cur_row, int32_t *out_obs_row, void *stream);
+
 /* Fast path of evalMC_psrs for a fixed tabular policy (the headline scan).
  * offsim_compile_policy folds psrs.py:53-57 for policy pi [n_slots,nA] f64 into one 64-bit key per grouped row:
  *   key = T << 11 | done << 10 | z_next_slot,  T = floor(2^53 * pi[z][a]/p_log[a]/max_a'(pi[z][a']/p_log[a'])),

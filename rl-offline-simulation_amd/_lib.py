@@ -258,6 +258,10 @@ SIGNATURES = {
                                     C.POINTER(TD), _i32, _i64, _vp, _vp]),
     "offsim_eval_queue_pop": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), _i32, _i32, _i32, C.POINTER(TDPop), _i64, C.POINTER(EvalMCOut), _i32,
                                         _i64, _vp, _vp]),
+    "offsim_eval_queue_rows_policy": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), _i32, _vp, _vp, _i32, C.c_double, _vp, _i64, _i64,
+                                                C.POINTER(EvalMCOut), _vp, _vp, _vp]),
+    "offsim_eval_queue_rows_policy_pop": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), _i32, _vp, _vp, _i32, _i32, _i32, C.c_double, _vp, _i64,
+                                                    _i64, C.POINTER(EvalMCOut), _vp, _vp, _vp]),
     "offsim_compile_policy": (C.c_int, [C.POINTER(Table), _vp, _vp, _vp]),
     "offsim_eval_mc_keys_kernel": (C.c_char_p, [_i32, _i32]),
     "offsim_compile_digests": (C.c_int, [C.POINTER(Table), _vp, _i32, _vp, _vp]),

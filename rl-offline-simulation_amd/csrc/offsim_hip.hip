@@ -1889,6 +1889,9 @@ extern "C" int offsim_td_curves(const double *ep_g, const int64_t *n_ep, int32_t
 // ---- whole rollouts on QueueEvaluator: the tabular drivers evalMC / qlearn / expSARSA over (z, a)-keyed queues (csrc/eval_queue.hpp) ----
 #include "eval_queue.hpp"
 
+// ---- evalMC on QueueEvaluator for policies over observations, one or a population (csrc/eval_queue_rows.hpp) ----
+#include "eval_queue_rows.hpp"
+
 // ------------------------------------------------------------------------------------------------
 // Fast evalMC scan: compiled-policy keys + LDS candidate windows (scan_win.hpp)
 // ------------------------------------------------------------------------------------------------

@@ -1,8 +1,8 @@
 from .psrs import PSRS, BatchedPSRS, evalMC_psrs, evalmc_rollouts, qlearn_psrs, expSARSA_psrs, SHUFFLE_PER_ROLLOUT, SHUFFLE_SHARED, SHUFFLE_NONE  # noqa: F401
 from .per_state_rejection import PerStateRejectionSampling  # noqa: F401
 from .trivial_baselines import FollowObservationOnly, FollowActionOnly, ServeRandomTransitions  # noqa: F401
-from .queue_evaluator import (QueueEvaluator, BatchedQueueEvaluator, evalmc_rollouts_queue, evalMC_queue, qlearn_queue,  # noqa: F401
-                              expSARSA_queue)
+from .queue_evaluator import (QueueEvaluator, BatchedQueueEvaluator, evalmc_rollouts_queue, evalmc_rollouts_queue_population,  # noqa: F401
+                              evalMC_queue, qlearn_queue, expSARSA_queue)
 from .psrs_exo import PSRS_Exo, BatchedPSRSExo, evalmc_rollouts_exo, tabulate_obs  # noqa: F401
 from .vector_env import VectorPSRS  # noqa: F401
 from .vector_queue import VectorQueueEvaluator  # noqa: F401

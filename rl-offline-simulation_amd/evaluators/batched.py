@@ -13,15 +13,14 @@ drivers (PSRS, evalMC_psrs, qlearn_psrs, expSARSA_psrs) are in psrs.py, on top o
 import ctypes as C
 import os
 import time
-import warnings
 
 import numpy as np
 import torch
 
 from .. import _lib as L
 from ..table import RolloutState, TransitionTable, seed_streams, seeds_tensor, shuffle_queues
-from .rollout_io import (HOST_KEYS, _gamma_pow, _prob_mode, collect_host, episode_bound, host_result, population_result,  # noqa: F401
-                         population_state, rollout_outputs, seed_tiles, td_outputs, td_population_launch, tie_stream)
+from .rollout_io import (HOST_KEYS, _gamma_pow, _prob_mode, collect_host, episode_bound, host_result, population_host_result,  # noqa: F401
+                         population_result, population_state, rollout_outputs, seed_tiles, td_outputs, td_population_launch, tie_stream)
 
 SHUFFLE_PER_ROLLOUT = "per_rollout"  # reset_sampler(seed_r) for every rollout r: the reference's meaning
 SHUFFLE_SHARED = "shared"            # one queue order (shuffle_seed) shared by all rollouts, per-rollout rejection streams
@@ -844,9 +843,4 @@ def evalmc_rollouts_population(table, seeds, policies, gamma, shuffle=SHUFFLE_PE
             collect_host(cols, env.eval_mc_rows_policy_population(p_next, p_init, gamma, n_episodes))
         for k in HOST_KEYS:
             outs[k].append(np.concatenate(cols[k], axis=0))
-    res = host_result(outs, axis=1, empty=(n_pol, 0))
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore", RuntimeWarning)  # (a policy without one completed episode: its mean is NaN, as its values are)
-        res["mean_value"] = np.nanmean(res["value"], axis=1)
-    res["best"] = -1 if np.isnan(res["mean_value"]).all() else int(np.nanargmax(res["mean_value"]))
-    return res
+    return population_host_result(outs, n_pol)

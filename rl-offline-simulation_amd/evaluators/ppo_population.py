@@ -180,6 +180,14 @@ class PPOPopulation:
         from .obs_policy import PolicyPopulation
         return evalmc_rollouts_population(table, seeds, PolicyPopulation.from_ppo(self), gamma, obs=obs, next_obs=next_obs, **kw)
 
+    def evaluate_queue(self, env_or_arrays, seeds, gamma, obs, next_obs, **kw):
+        """evalMC on the queue simulator of every learner's actor, with its current weights, on the same sampler seeds and action streams:
+        evalmc_rollouts_queue_population (queue_evaluator.py) over PolicyPopulation.from_ppo(self); `env_or_arrays`, `kw` and the result
+        are its."""
+        from .obs_policy import PolicyPopulation
+        from .queue_evaluator import evalmc_rollouts_queue_population
+        return evalmc_rollouts_queue_population(env_or_arrays, seeds, PolicyPopulation.from_ppo(self), gamma, obs=obs, next_obs=next_obs, **kw)
+
     # ---- one learner, exported ----
     def actor(self, l):
         """learner l's actor as an MLPPolicy of its current weights (a copy)"""

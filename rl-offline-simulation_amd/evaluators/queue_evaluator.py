@@ -9,6 +9,11 @@ themselves and pop one row per step -- run in offsim_eval_queue (csrc/eval_queue
 eval_td, evalmc_rollouts_queue for many sampler seeds, and the drop-ins evalMC_queue / qlearn_queue / expSARSA_queue on a QueueEvaluator.
 Many learners on the same seeds in one launch (offsim_eval_queue_pop, csrc/td_pop.hpp): BatchedQueueEvaluator.eval_td_population,
 driven over seed tiles by TDPopulation.run_queue (evaluators/td_population.py).
+
+Policies over observations (evaluators/obs_policy.py: the PPO actor, ppo.py:258-279) are evaluated by offsim_eval_queue_rows_policy
+(csrc/eval_queue_rows.hpp) from their per-row tables: BatchedQueueEvaluator.eval_mc_rows_policy, evalmc_rollouts_queue and evalMC_queue with
+an ObsPolicy; L of them on the same seeds in one launch (offsim_eval_queue_rows_policy_pop): eval_mc_rows_policy_population and
+evalmc_rollouts_queue_population.
 """
 import ctypes as C
 import os
@@ -20,8 +25,9 @@ from .. import _lib as L
 from ..spaces import is_discrete
 from ..table import TransitionTable, gather_rows
 from .psrs import BatchedPSRS, SHUFFLE_PER_ROLLOUT, _behaviour_kind, _schedule
-from .rollout_io import (HOST_KEYS, _gamma_pow, collect_host, episode_bound, host_result, population_result, population_state, rollout_outputs,
-                         seed_tiles, td_outputs, td_population_launch, tie_stream)
+from .obs_policy import MLPPolicy, ObsPolicy, PolicyPopulation
+from .rollout_io import (HOST_KEYS, _gamma_pow, collect_host, episode_bound, host_result, population_host_result, population_result, population_state,
+                         rollout_outputs, seed_tiles, td_outputs, td_population_launch, tie_stream)
 
 
 class BatchedQueueEvaluator:
@@ -53,9 +59,11 @@ class BatchedQueueEvaluator:
         self.R = int(R)
         self.env = BatchedPSRS(t, R, L.REJECT_NEVER)
         self._dummy_p = torch.zeros((R, nA), dtype=torch.float64, device=t.device)
+        self.cur_row = torch.full((R,), -1, dtype=torch.int32, device=t.device)  # eval_mc_rows_policy: the table row each rollout stands at
 
     def reset_sampler(self, seeds):
         self.env.reset_sampler(seeds, SHUFFLE_PER_ROLLOUT)
+        self.cur_row.fill_(-1)
 
     def set_action_seeds(self, seeds):
         """The action streams of the one-launch drivers: rollout i draws its actions from default_rng(seeds[i]) (tabular.py:75, :145, :248).
@@ -182,6 +190,69 @@ class BatchedQueueEvaluator:
                                                1 if by_episode else 0, int(episode0), L.ptr(o["obs_row"]), L.stream_ptr()))
         return population_result(o, n_l, S, copies, keep, "k_eval_queue_pop", state=state)
 
+    # -- evalMC for policies over observations (evaluators/obs_policy.py): offsim_eval_queue_rows_policy --
+    def _row_tables(self, who, p_next, p_init, lead):
+        """p_next [*lead, N, nA] and p_init [*lead, N0, nA] on the device, contiguous, f32 when both are (widened in the kernel), else f64"""
+        t = self.table
+        dt = torch.float32 if p_next.dtype == p_init.dtype == torch.float32 else torch.float64
+        if tuple(p_next.shape) != (*lead, t.N, self.nA) or tuple(p_init.shape) != (*lead, t.N0, self.nA):
+            raise ValueError(f"{who}: p_next {[*lead, t.N, self.nA]} and p_init {[*lead, t.N0, self.nA]} expected, got {tuple(p_next.shape)} and "
+                             f"{tuple(p_init.shape)}")
+        return p_next.to(device=t.device, dtype=dt).contiguous(), p_init.to(device=t.device, dtype=dt).contiguous(), L.F32 if dt == torch.float32 else L.F64
+
+    def eval_mc_rows_policy(self, p_next, p_init, gamma, n_episodes=None, ep_cap=0, trace_cap=0, n_gamma_pow=4096):
+        """evalMC (tabular.py:247-270) of a policy over observations on every rollout in one launch, on this environment's own state.
+        p_next [N,nA]: the policy at next_obs of every GROUPED row (self.table.order); p_init [N0,nA]: at obs of every initial row
+        (self.table.init_orig) -- what ObsPolicy.row_tables(self.table, obs, next_obs) returns, as it is.  f32 tables stay f32 and are widened
+        in the kernel; anything else is f64.  Returns eval_mc's dict, and cur_row [R] (also kept as self.cur_row; reset_sampler sets it to
+        -1): g >= 0 the last served grouped row, -2 - k initial row k with no step since, -1 none."""
+        if self.nZ is None:
+            raise L.OffsimError("the one-launch queue drivers need dense state ids (this log's ids were compacted to ranks)")
+        env, t = self.env, self.table
+        env._quiesce()
+        env._orders_for_generic()
+        dev, R = t.device, self.R
+        pn, p0, dt = self._row_tables("eval_mc_rows_policy", p_next, p_init, ())
+        o, oc = rollout_outputs(R, dev, ep_cap, trace_cap)
+        o["obs_row"] = torch.full((R,), -(1 << 31), dtype=torch.int32, device=dev)
+        o["cur_row"] = self.cur_row
+        gp = _gamma_pow(gamma, n_gamma_pow, dev, cap=t.N + 2)
+        L.check(L.load().offsim_eval_queue_rows_policy(C.byref(t.c), C.byref(env.state.c), self.nA, L.ptr(pn) if t.N else None, L.ptr(p0) if t.N0 else None,
+                                                       dt, float(gamma), L.ptr(gp), gp.numel(), int(episode_bound(n_episodes)), C.byref(oc),
+                                                       L.ptr(self.cur_row), L.ptr(o["obs_row"]), L.stream_ptr()))
+        o["_keepalive"] = (pn, p0, gp)
+        o["_kernel"] = "k_eval_queue_rows"
+        return o
+
+    def eval_mc_rows_policy_population(self, p_next, p_init, gamma, n_episodes=None, ep_cap=0, trace_cap=0, n_gamma_pow=4096, state=False):
+        """eval_mc_rows_policy for L policies, each on every one of this environment's S = R rollouts (its sampler seeds and action
+        streams): L * S rollouts in one launch that share the S queue orders (include/offsim.h, offsim_eval_queue_rows_policy_pop).
+        p_next [L,N,nA], p_init [L,N0,nA]: the tables stacked (PolicyPopulation.row_tables).  Returns eval_mc_rows_policy's dict with [L, S]
+        leading dimensions; entry [l, j] is, bit for bit, what eval_mc_rows_policy gives rollout j with policy l.  It is a query: it runs
+        on copies of the rollout state, and this environment's own cursors, action streams, current slots and cur_row are left as they
+        were; with `state`, out["_state"] holds where every policy's rollouts stand afterwards."""
+        if self.nZ is None:
+            raise L.OffsimError("the one-launch queue drivers need dense state ids (this log's ids were compacted to ranks)")
+        env, t = self.env, self.table
+        env._quiesce()
+        env._orders_for_generic()
+        dev, S = t.device, self.R
+        if p_next.dim() != 3 or p_init.dim() != 3 or p_next.shape[0] != p_init.shape[0] or p_next.shape[0] < 1:
+            raise ValueError(f"eval_mc_rows_policy_population: p_next [L,N,nA] and p_init [L,N0,nA] expected, got {tuple(p_next.shape)} and "
+                             f"{tuple(p_init.shape)}")
+        n_pol = int(p_next.shape[0])
+        R = n_pol * S
+        pn, p0, dt = self._row_tables("eval_mc_rows_policy_population", p_next, p_init, (n_pol,))
+        o, oc = rollout_outputs(R, dev, ep_cap, trace_cap)
+        o["obs_row"] = torch.full((R,), -(1 << 31), dtype=torch.int32, device=dev)
+        o["cur_row"] = self.cur_row.repeat(n_pol)
+        ro, copies = population_state(env.state, n_pol)
+        gp = _gamma_pow(gamma, n_gamma_pow, dev, cap=t.N + 2)
+        L.check(L.load().offsim_eval_queue_rows_policy_pop(C.byref(t.c), C.byref(ro), self.nA, L.ptr(pn) if t.N else None, L.ptr(p0) if t.N0 else None,
+                                                           dt, n_pol, S, float(gamma), L.ptr(gp), gp.numel(), int(episode_bound(n_episodes)),
+                                                           C.byref(oc), L.ptr(o["cur_row"]), L.ptr(o["obs_row"]), L.stream_ptr()))
+        return population_result(o, n_pol, S, copies, (pn, p0, gp), "k_eval_queue_rows_pop", state=state)
+
     def reset(self, mask=None):
         return self.env.reset(mask)
 
@@ -278,37 +349,100 @@ class QueueEvaluator:
 # ---------------------------------------------------------------------------------------------------
 # Many sampler seeds per launch
 # ---------------------------------------------------------------------------------------------------
-def evalmc_rollouts_queue(env_or_arrays, seeds, pi, gamma, n_episodes=None, action_seeds=None, tile=None):
+def _queue_arrays(env_or_arrays):
+    return env_or_arrays._arrays if isinstance(env_or_arrays, QueueEvaluator) else tuple(env_or_arrays)
+
+
+def _queue_obs(who, env_or_arrays, obs, next_obs, needed):
+    """the log's observations for a policy over observations: the caller's, or a QueueEvaluator's own dataset's"""
+    if (obs is None or next_obs is None) and isinstance(env_or_arrays, QueueEvaluator):
+        e = env_or_arrays._dataset.experience
+        obs, next_obs = e["observations"], e["next_observations"]
+    if (obs is None or next_obs is None) and needed:
+        raise ValueError(f"{who}: a policy over observations needs the log's obs= and next_obs=")
+    return obs, next_obs
+
+
+def evalmc_rollouts_queue(env_or_arrays, seeds, pi, gamma, n_episodes=None, action_seeds=None, tile=None, obs=None, next_obs=None):
     """evalMC (tabular.py:247-270) on the queue simulator for many sampler seeds, one launch per tile of seeds.  `env_or_arrays`: a
     QueueEvaluator, or the columns (z, a, r, z_next, done, p_log, t0) BatchedQueueEvaluator takes.  `pi` [nS, nA] is indexed by the state
     as the reference does; rollout i shuffles its queues with seeds[i] and draws its actions from default_rng(action_seeds[i])
     (default: seeds).  Returns the dictionary of evalmc_rollouts_exo: host arrays sum_g, n_ep, steps, cand, status and
-    value = sum_g / n_ep."""
+    value = sum_g / n_ep.
+    `pi` may also be a policy over observations (evaluators/obs_policy.py: MLPPolicy, RowPolicy, CallablePolicy) with the log's observations
+    `obs` / `next_obs` [N, dO] in caller order (default: the QueueEvaluator's dataset's): its per-row tables are computed once and every
+    tile is one launch of offsim_eval_queue_rows_policy."""
     seeds = np.asarray(seeds, dtype=np.uint64)
     action_seeds = seeds if action_seeds is None else np.asarray(action_seeds, dtype=np.uint64)
     if len(action_seeds) != len(seeds):
         raise ValueError("evalmc_rollouts_queue: one action seed per sampler seed")
-    arrays = env_or_arrays._arrays if isinstance(env_or_arrays, QueueEvaluator) else tuple(env_or_arrays)
+    arrays = _queue_arrays(env_or_arrays)
+    rows = isinstance(pi, ObsPolicy)
+    if rows:
+        obs, next_obs = _queue_obs("evalmc_rollouts_queue", env_or_arrays, obs, next_obs, not hasattr(pi, "p_next"))
     tile = len(seeds) if tile is None else int(tile)
-    outs = {k: [] for k in HOST_KEYS}
+    outs, tables = {k: [] for k in HOST_KEYS}, None
     for b, sd, env in seed_tiles(seeds, max(tile, 1), lambda n: BatchedQueueEvaluator(*arrays, R=n)):
         env.reset_sampler(sd)
         env.set_action_seeds(action_seeds[b:b + len(sd)])
-        collect_host(outs, env.eval_mc(env.state_rows(pi), gamma, n_episodes))
+        if rows and tables is None:  # (every environment of the same columns groups them alike)
+            tables = pi.row_tables(env.table, obs, next_obs)
+        collect_host(outs, env.eval_mc_rows_policy(*tables, gamma, n_episodes) if rows else env.eval_mc(env.state_rows(pi), gamma, n_episodes))
     return host_result(outs, empty=0)
+
+
+def evalmc_rollouts_queue_population(env_or_arrays, seeds, policies, gamma, n_episodes=None, action_seeds=None, tile=None, policy_tile=None,
+                                     obs=None, next_obs=None):
+    """evalMC on the queue simulator of L policies over observations on the same S sampler seeds: evalmc_rollouts_population (batched.py) on
+    QueueEvaluator.  Every policy sees the same queue orders and the same action streams (default_rng(action_seeds[i]); default: seeds), so
+    the differences between policies are paired.  `policies`: a PolicyPopulation, or a list of policies over observations (MLPPolicy's of
+    one architecture are stacked, anything else goes through its own row tables); obs / next_obs [N, dO]: the log's observations in caller
+    order (default: the QueueEvaluator's dataset's).  One sampler reset per tile of `tile` seeds (default: all), and per seed tile one
+    forward launch and one launch of offsim_eval_queue_rows_policy_pop per tile of `policy_tile` policies (default: as many as keep the
+    [L, N + N0, nA] tables within a quarter of the free memory; with more than one policy tile the tables are recomputed per seed tile).
+    Returns evalmc_rollouts_population's dictionary: host arrays [L, S] sum_g, n_ep, steps, cand, status, value; mean_value [L]; best."""
+    seeds = np.asarray(seeds, dtype=np.uint64)
+    action_seeds = seeds if action_seeds is None else np.asarray(action_seeds, dtype=np.uint64)
+    if len(action_seeds) != len(seeds):
+        raise ValueError("evalmc_rollouts_queue_population: one action seed per sampler seed")
+    if not isinstance(policies, PolicyPopulation):
+        policies = list(policies)
+        policies = PolicyPopulation.from_policies(policies) if policies and all(isinstance(p, MLPPolicy) for p in policies) else PolicyPopulation.from_rows(policies)
+    n_pol = len(policies)
+    arrays = _queue_arrays(env_or_arrays)
+    obs, next_obs = _queue_obs("evalmc_rollouts_queue_population", env_or_arrays, obs, next_obs, policies.needs_obs())
+    tile = len(seeds) if tile is None else int(tile)
+    outs, tables = {k: [] for k in HOST_KEYS}, None
+    for b, sd, env in seed_tiles(seeds, max(tile, 1), lambda n: BatchedQueueEvaluator(*arrays, R=n)):
+        t = env.table
+        if policy_tile is None:
+            per_policy = max(1, (int(t.N) + int(t.N0)) * int(t.nA) * 8)
+            policy_tile = (torch.cuda.mem_get_info(t.device)[0] // 4) // per_policy
+        policy_tile = int(max(1, min(n_pol, policy_tile)))
+        env.reset_sampler(sd)
+        env.set_action_seeds(action_seeds[b:b + len(sd)])
+        if tables is None and policy_tile >= n_pol:  # (one policy tile: computed once)
+            tables = policies.row_tables(t, obs, next_obs)
+        cols = {k: [] for k in HOST_KEYS}
+        for lo in range(0, n_pol, policy_tile):
+            p_next, p_init = tables if tables is not None else policies.row_tables(t, obs, next_obs, lo, min(n_pol, lo + policy_tile))
+            collect_host(cols, env.eval_mc_rows_policy_population(p_next, p_init, gamma, n_episodes))
+        for k in HOST_KEYS:
+            outs[k].append(np.concatenate(cols[k], axis=0))
+    return population_host_result(outs, n_pol)
 
 
 # ---------------------------------------------------------------------------------------------------
 # The reference's tabular drivers (offsim4rl/agents/tabular.py) on a QueueEvaluator, one launch each
 # ---------------------------------------------------------------------------------------------------
-def _launch_queue(env, what, seed, run):
+def _launch_queue(env, what, seed, run, by_state=True):
     """One driver call on `env`: the action stream default_rng(seed) (tabular.py:75, :145, :248; None: OS entropy), the launch on the
     environment's own rollout state, the KeyError the reference raises, and env.s / env.z as its loop leaves them."""
     from .psrs import _all_equal
     if not isinstance(env, QueueEvaluator):
         raise TypeError(f"{what}: `env` must be the device-backed QueueEvaluator of this package, got {type(env).__name__}")
     e = env._dataset.experience
-    if not (_all_equal(e["observations"], env._z) and _all_equal(e["next_observations"], env._zn)):
+    if by_state and not (_all_equal(e["observations"], env._z) and _all_equal(e["next_observations"], env._zn)):
         raise NotImplementedError(f"{what}: the observations of this QueueEvaluator differ from its states, but the tabular drivers index their "
                                   "tables by the observation (tabular.py:119, :171, :258)")
     impl = env._impl
@@ -333,7 +467,18 @@ def _launch_queue(env, what, seed, run):
 def evalMC_queue(env, n_episodes, pi, gamma, seed=None):
     """tabular.py:247-270 on a QueueEvaluator: the whole loop -- env.reset(), A = rng.choice(nA, p=pi[S]), env.step(A), discounted returns
     -- in one kernel launch: (Gs, lengths).  A queue that runs out ends the run (the reference's loop does not survive it): Gs holds the
-    completed episodes, lengths also the cut-short one."""
+    completed episodes, lengths also the cut-short one.
+    `pi` may be a policy over observations (evaluators/obs_policy.py): p = pi(S) with S the dataset's own observation, whatever the
+    encoder makes of it (what evalMC_psrs does for PSRS); its per-row tables are computed once, then offsim_eval_queue_rows_policy runs
+    the loop.  A [nS, nA] table needs observations that are the states (NotImplementedError otherwise)."""
+    if isinstance(pi, ObsPolicy):
+        e, t = env._dataset.experience, env._impl.table
+        n_ep = int(min(n_episodes, t.N0 + 1))
+        p_next, p_init = pi.row_tables(t, e["observations"], e["next_observations"])
+        o, _, _ = _launch_queue(env, "evalMC_queue", seed, lambda b: b.eval_mc_rows_policy(p_next, p_init, gamma, n_ep, ep_cap=max(n_ep, 1),
+                                                                                           trace_cap=t.N + 1), by_state=False)
+        ne, nl = int(o["n_ep"].cpu()[0]), int(o["n_len"].cpu()[0])
+        return o["ep_g"].cpu().numpy()[0, :ne].copy(), o["ep_len"].cpu().numpy()[0, :nl].astype(np.int64)
     pi = np.asarray(pi, dtype=np.float64)
     if pi.ndim != 2:
         raise ValueError("evalMC_queue: pi must be a [nS, nA] table")

@@ -6,11 +6,13 @@
   td_population_launch   the per-learner arguments of a population of learners as struct offsim_td_pop, with its outputs
   population_state / population_result   a population launch's copies of the sampler state, and its dict as [n, S, ...]
   seed_tiles / collect_host / host_result   the loop over tiles of sampler seeds and the host arrays it returns
+  population_host_result   the same for a population of policies on the seeds: [L, S] arrays, mean_value, best
   episode_bound, _gamma_pow, _prob_mode     the episode limit, the discount table and the probability mode of a launch
 
 A leaf: it imports _lib, ctypes, torch and NumPy only, so batched.py, psrs_exo.py and td_population.py all import it at module top.
 """
 import ctypes as C
+import warnings
 
 import numpy as np
 import torch
@@ -235,4 +237,16 @@ def host_result(parts, axis=0, empty=None):
     res = {k: np.concatenate(v, axis=axis) if v or empty is None else np.zeros(empty) for k, v in parts.items()}
     with np.errstate(invalid="ignore", divide="ignore"):
         res["value"] = res["sum_g"] / res["n_ep"]
+    return res
+
+
+def population_host_result(parts, n_pop):
+    """The dictionary of the population drivers (evalmc_rollouts_population, evalmc_rollouts_queue_population): `parts` holds per seed tile
+    the [n_pop, tile] arrays; host_result along the seeds, then mean_value [n_pop], the mean of value over the seeds that have one (NaN
+    where none has), and best, the arg-max of mean_value (-1 when every mean is NaN)."""
+    res = host_result(parts, axis=1, empty=(n_pop, 0))
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)  # (a policy without one completed episode: its mean is NaN, as its values are)
+        res["mean_value"] = np.nanmean(res["value"], axis=1)
+    res["best"] = -1 if np.isnan(res["mean_value"]).all() else int(np.nanargmax(res["mean_value"]))
     return res
