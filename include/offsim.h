@@ -1248,6 +1248,75 @@ int offsim_homer_grad_pop(const offsim_homer_net *net, const offsim_homer_batch_
 int offsim_homer_step_pop(const offsim_homer_net *net, const offsim_homer_batch_pop *batch, int32_t L, double tau,
                           const offsim_homer_adam_pop *adam, const uint8_t *active, double *stats, double *work, void *stream);
 
+/* offsim_replay_td: a logged memory replayed through L tabular TD learners in ONE launch -- qlearn(..., memory=...) of the reference
+ * (offsim4rl/agents/tabular.py:90-104: the Q-learning update swept over logged (S, A, R, S', done) tuples in log order, no simulator), for a
+ * population of step sizes and discounts, on S streams of the same log.
+ *   log: device columns s, a [N] i32, r [N] f64, s_next [N] i32, done [N] u8; states in [0, nS), actions in [0, nA).
+ *   rp->order [S, M] i32 or NULL.  NULL: S must be 1 and the stream is the log in log order (M is ignored, the stream has N steps).
+ *     Otherwise stream j visits log rows order[j, 0 .. M - 1]; repeats are allowed and M is independent of N (shuffled replay, bootstrap
+ *     resamples of the log for paired error bars).  passes >= 1: the stream is swept that many times; the episode counter carries on.
+ *   Per learner, device arrays: alpha, gamma [L] f64; alpha_ep [L, n_sched] f64 or NULL with offsim_td's rule (entry min(e, n_sched - 1)
+ *     serves episode e; alpha is then not read).  mode: OFFSIM_TD_QLEARN or OFFSIM_TD_EXPSARSA (one per launch).  pi [L, nS, nA] f64 with
+ *     pi_stride = nS * nA, or one table shared by all learners with pi_stride = 0 (offsim_td_pop's rule); read by OFFSIM_TD_EXPSARSA only.
+ *   Rollout l * S + j is learner l on stream j.
+ * Per step k of a stream, with (s, a, r, s', d) its transition and e the number of done flags the stream has seen so far:
+ *     target = max_b Q[s', b]                                   OFFSIM_TD_QLEARN   (tabular.py:95-96)
+ *            | sum_b Q[s', b] * pi[s', b], b = 0 .. nA - 1      OFFSIM_TD_EXPSARSA (left to right from 0.0: the sum offsim_eval_td defines)
+ *     td     = (r + gamma * target) - Q[s, a]
+ *     Q[s,a] = Q[s, a] + alpha(e) * td
+ *     if d: e += 1
+ *   in f64, in exactly this order, without contraction.  done is not treated specially in the update (the reference does not either).  The
+ *   row maximum is offsim_eval_td's: m = Q[s', 0], then m = Q[s', b] > m ? Q[s', b] : m for b = 1 .. nA - 1 -- a NaN in entry 0 stays, a NaN
+ *   in a later entry is passed over (np.max would return it).
+ * Outputs: q [L * S, nS, nA] f64, read as Q_init and written back.  td_err [S, td_cap, L] f64 (optional): the TD errors of the first td_cap
+ *   steps, learner-MINOR (a wavefront stores one step of 64 learners as one contiguous vector).  q_snap [L * S, snap_cap, nS, nA] /
+ *   snap_stride / snap_cap: offsim_td's rule, Q after steps 0, stride, 2 stride, ....  n_ep [S] i64: the done flags stream j saw;
+ *   steps [L * S] i64; status [L * S] i32.  A step whose s, a or s' is out of range, or whose order entry is outside [0, N), stops that
+ *   stream's rollouts BEFORE the step: status OFFSIM_ST_KEYERROR, steps = k, Q as step k - 1 left it (the reference raises IndexError);
+ *   other streams are unaffected.  Otherwise OFFSIM_ST_OK and steps = passes * M.
+ * Launch: one wavefront per workgroup, grid = S x ceil(L / LPW), the lane is the learner within its group, its Q in LDS as
+ *   [nS * nA][LPW] f64.  LPW = offsim_replay_lpw(nS, nA, L): the largest of 64, 32, .., 1 that is no larger than L rounded up to a power of two
+ *   and whose Q image nS * nA * LPW * 8 bytes fits 160 KiB (offsim_eval_td's dynamic-LDS budget; the stream tile is staged in registers, so
+ *   nothing comes off it); 0 when one learner's table does not fit, and offsim_replay_td then returns OFFSIM_EUNSUPPORTED, the refusal of
+ *   offsim_eval_td past 160 KiB.
+ * OFFSIM_EINVAL, before any HIP call: NULL log columns, N < 1, L outside 1..65535, S < 1, S != 1 without an order, an order with M < 1,
+ *   passes < 1, a bad mode, NULL q / alpha / gamma / n_ep / steps / status, OFFSIM_TD_EXPSARSA without pi, alpha_ep without n_sched, a bad
+ *   snapshot stride (L and S are at least 1 in an accepted call, so there is no empty launch).  N or M above 2^31 - 1: OFFSIM_EUNSUPPORTED.
+ *   Asynchronous on `stream`. */
+typedef struct offsim_replay_log {
+    int64_t N;
+    int32_t nS;
+    int32_t nA;
+    const int32_t *s;
+    const int32_t *a;
+    const double *r;
+    const int32_t *s_next;
+    const uint8_t *done;
+} offsim_replay_log;
+typedef struct offsim_replay {
+    int32_t mode;
+    const int32_t *order;
+    int64_t M;
+    int64_t passes;
+    const double *alpha;
+    const double *gamma;
+    const double *alpha_ep;
+    int64_t n_sched;
+    const double *pi;
+    int64_t pi_stride;
+    double *q;
+    double *td_err;
+    int64_t td_cap;
+    double *q_snap;
+    int64_t snap_cap;
+    int64_t snap_stride;
+    int64_t *n_ep;
+    int64_t *steps;
+    int32_t *status;
+} offsim_replay;
+int32_t offsim_replay_lpw(int32_t nS, int32_t nA, int32_t L);
+int offsim_replay_td(const offsim_replay_log *log, int32_t L, int32_t S, const offsim_replay *rp, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -221,6 +221,18 @@ BEHAVIOUR_FIXED, BEHAVIOUR_EPS_GREEDY, BEHAVIOUR_SOFT_GREEDY = 0, 1, 2
 EXO_RESEED_NONE, EXO_RESEED_EPISODE = 0, 1
 
 
+class ReplayLog(C.Structure):
+    """struct offsim_replay_log"""
+    _fields_ = [("N", _i64), ("nS", _i32), ("nA", _i32), ("s", _vp), ("a", _vp), ("r", _vp), ("s_next", _vp), ("done", _vp)]
+
+
+class Replay(C.Structure):
+    """struct offsim_replay"""
+    _fields_ = [("mode", _i32), ("order", _vp), ("M", _i64), ("passes", _i64), ("alpha", _vp), ("gamma", _vp), ("alpha_ep", _vp), ("n_sched", _i64),
+                ("pi", _vp), ("pi_stride", _i64), ("q", _vp), ("td_err", _vp), ("td_cap", _i64), ("q_snap", _vp), ("snap_cap", _i64),
+                ("snap_stride", _i64), ("n_ep", _vp), ("steps", _vp), ("status", _vp)]
+
+
 class ExoOut(C.Structure):
     """struct offsim_exo_out"""
     _fields_ = [("trace_row_x", _vp), ("last", _vp)]
@@ -320,6 +332,8 @@ SIGNATURES = {
     "offsim_homer_grad_pop": (C.c_int, [C.POINTER(HomerNet), C.POINTER(HomerBatchPop), _i32, C.c_double, _i32, _vp, _vp, _vp, _vp, _vp]),
     "offsim_homer_step_pop": (C.c_int, [C.POINTER(HomerNet), C.POINTER(HomerBatchPop), _i32, C.c_double, C.POINTER(HomerAdamPop), _vp, _vp, _vp,
                                         _vp]),
+    "offsim_replay_lpw": (_i32, [_i32, _i32, _i32]),
+    "offsim_replay_td": (C.c_int, [C.POINTER(ReplayLog), _i32, _i32, C.POINTER(Replay), _vp]),
 }
 
 _lib = None

@@ -2479,3 +2479,6 @@ extern "C" int offsim_value_mlp(const void *x, int32_t x_dtype, int64_t n_x, int
 
 // ---- HOMER encoder training: fused forward / loss / backward, reduce, clip + Adam (csrc/homer_train.hpp) ----
 #include "homer_train.hpp"
+
+// ---- a logged memory replayed through many TD learners: the learner is the lane, its Q in LDS (csrc/replay_td.hpp) ----
+#include "replay_td.hpp"

@@ -13,3 +13,4 @@ from .ppo_learner import PPOLearner, PPOUpdateInfo, ppo_grad  # noqa: F401
 from .ppo_population import PPOPopulation, ppo_grad_population  # noqa: F401
 from .ppo_log import EpisodeTracker, PPOEpochLog, PPOEpisodes, PPOTrainLog, ppo_epoch_log, ppo_epoch_log_records  # noqa: F401
 from .td_population import TDPopulation, TDPopulationResult  # noqa: F401
+from .replay import ReplayLog, TDReplayResult, qlearn_replay, replay_orders, replay_td, replay_lpw  # noqa: F401

@@ -11,6 +11,7 @@ per learner on the device.  Learners never interact: learner l on seed j is, bit
   population.run(table, seeds, ...)                                  -> TDPopulationResult of device tensors
   population.run_exo(env_or_tables, seeds, ...)                      the same on an exogenous-state log (PSRS_Exo), tables by observation
   population.run_queue(env_or_arrays, seeds, ...)                    the same on the queue simulator (QueueEvaluator), tables by state
+  population.replay(log, orders, passes, ...)                        no simulator: the logged memory itself replayed through every learner
 """
 import itertools
 from dataclasses import dataclass, field
@@ -313,6 +314,37 @@ class TDPopulation:
                                lambda n: BatchedQueueEvaluator(*arrays, R=n), launch,
                                lambda q: self._rows_into(Q0, q, range(probe.z_lo, probe.z_lo + nZ), range(nZ), self.L, S), tie=tie,
                                tie_out=not (isinstance(tie, str) and tie == "first"), trace_cap=trace_cap)
+
+    def replay(self, log, orders=None, passes=1, td_cap=0, snap_stride=0, snap_cap=0):
+        """Every learner on the logged memory itself, no simulator: qlearn(..., memory=...) of offsim4rl/agents/tabular.py:90-104 (and the
+        same sweep with the expected-SARSA target) for all L learners in one launch (offsim_replay_td, evaluators/replay.py).
+        log: a ReplayLog.  orders: None -- one stream, the log in log order -- or an int32 [S, M] device tensor (replay_orders): stream j
+        visits log rows orders[j]; every learner sees every stream, so comparisons are paired.  passes: sweeps over each stream, the
+        episode counter (the done flags seen) carrying on.  A callable alpha is tabulated for the episodes passes sweeps can hold.
+        td_cap: TD errors of the first td_cap steps; snap_stride / snap_cap: Q after steps 0, stride, 2 stride, ....
+        No action is drawn in a replay, so the population's `behaviour` and `epsilon` are ignored.  mode "expsarsa" needs pi.
+        pi / Q_init are [nS,nA] or [L,nS,nA] tables by state (Q_init None: zeros).  Returns a TDReplayResult."""
+        from .replay import TDReplayResult, replay_td
+        if self.mode == L.TD_EXPSARSA and self.pi is None:
+            raise ValueError("TDPopulation.replay: mode 'expsarsa' needs pi")
+        for k, x in (("pi", self.pi), ("Q_init", self.Q_init)):
+            if x is not None and x.shape[-2:] != (log.nS, log.nA):
+                raise ValueError(f"TDPopulation.replay: {k} [nS,nA] = {(log.nS, log.nA)} expected, got {x.shape}")
+        S = 1 if orders is None else int(orders.shape[0])
+        M = log.N if orders is None else int(orders.shape[1])
+        a_const, a_tab = np.array([0.0 if callable(a) else float(a) for a in self.alpha]), None
+        if any(callable(a) for a in self.alpha):  # the episodes of the longest stream: its done flags, every sweep
+            flags = log.done.sum() if orders is None else log.done[orders.clamp(0, log.N - 1).to(torch.int64)].sum(dim=1).max()
+            n = int(flags.item()) * int(passes) + 1
+            a_tab = np.stack([_schedule(a, n) if callable(a) else np.full(n, float(a)) for a in self.alpha])
+        Q0 = np.zeros((log.nS, log.nA)) if self.Q_init is None else self.Q_init
+        q0 = torch.from_numpy(np.ascontiguousarray(Q0)).to(log.device)
+        q0 = (q0[:, None] if q0.dim() == 3 else q0[None, None]).expand(self.L, S, log.nS, log.nA)
+        o = replay_td(log, self.mode, a_const, self.gamma, q0, orders=orders, passes=passes, alpha_ep=a_tab,
+                      pi=self.pi if self.mode == L.TD_EXPSARSA else None, td_cap=td_cap, snap_stride=snap_stride, snap_cap=snap_cap)
+        td = o.get("td_err")
+        return TDReplayResult(Q=o["q"], n_ep=o["n_ep"], steps=o["steps"], status=o["status"], M=M, passes=int(passes),
+                              td_err=None if td is None else td.permute(2, 0, 1), q_snap=o.get("q_snap"), learners=self.learners)
 
     @staticmethod
     def _rows_into(Q0, q, dst_rows, src_rows, n_l, S):
