@@ -724,6 +724,33 @@ int offsim_encode_mlp(const void *x, int32_t x_dtype, int64_t N, int32_t dO, con
                       int32_t H, const float *W2, const float *b2, int32_t nZ, int32_t *out_z, float *out_logits,
                       void *stream);
 
+/* offsim_encode_mlp_pop: offsim_encode_mlp for L stacked encoders of one architecture in ONE launch (HOMERPopulation.encode).  Stacking as
+ * offsim_policy_mlp_pop's, which is how HOMERPopulation holds its weights: W1 [L, H, dO], b1 [L, H], W2 [L, nZ, H], b2 [L, nZ], contiguous;
+ * learner l's tensors are at W1 + l * H * dO and so on.  x [N, dO] is shared by all learners; out_z is [L, N] i32, out_logits [L, N, nZ]
+ * f32 or NULL (64-bit offsets throughout).  The learner is the grid's y of offsim_encode_mlp's four kernels, chosen by the same rule
+ * (the shape, 16-byte alignment of x, OFFSIM_ENCODER_F32): a workgroup serves one learner, loads that learner's weights into its
+ * registers or LDS and walks the rows as the single call's does, so learner l's out_z[l] and out_logits[l] equal offsim_encode_mlp with
+ * its tensors on the same x bit for bit (the order of a row's k summation does not depend on which wavefront takes the row).
+ * Grid: (g, L) with g = max(min(single, ceil(N / rows_per_wg)), ceil(single / L)), where `single` is the workgroup count
+ * offsim_encode_mlp starts for this N and rows_per_wg the rows a workgroup takes in one pass (4 wavefronts x 32 rows, x 2 on the
+ * register kernels at dO = 2 and 4; 256 on the VALU kernel): the single call's count, capped by what the learner's rows fill, but
+ * the L learners together never start fewer workgroups than the single call does.  L = 1 is the single call's grid.
+ * Limits as offsim_encode_mlp's (H <= 128, the LDS limit: OFFSIM_EUNSUPPORTED; f32 / f16 observations); L in 1..65535 (otherwise
+ * OFFSIM_EINVAL).  Argument validation happens before any HIP call; N = 0 launches nothing. */
+int offsim_encode_mlp_pop(const void *x, int32_t x_dtype, int64_t N, int32_t dO, const float *W1, const float *b1, int32_t H,
+                          const float *W2, const float *b2, int32_t nZ, int32_t L, int32_t *out_z, float *out_logits, void *stream);
+
+/* offsim_latent_counts: what L encoders make of a log (HOMERPopulation.latent_report).  z [L, N] i32 (offsim_encode_mlp_pop's out_z);
+ * labels [N] i32 or NULL, shared by all learners (the true state, for instance).  out_counts [L, nZ] i64: rows per latent state;
+ * out_joint [L, nZ, nY] i64 or NULL (it must be NULL when labels is): rows per (latent state, label); out_skipped [L] i64: the rows
+ * that are in neither, because their z is outside [0, nZ) or, with labels, their label is outside [0, nY).  The call zeroes its outputs
+ * itself (on `stream`).  Grid (min(ceil(N / 4096), 1024), L): a workgroup serves one learner with one LDS histogram of
+ * nZ * max(nY, 1) * 8 bytes (nY counts only with out_joint), flushed with one integer atomic add per non-empty bin, so the result is
+ * exact and the same on every call.  More than 64 KiB of histogram is OFFSIM_EUNSUPPORTED; L in 1..65535, nZ >= 1, nY >= 1 with
+ * labels (otherwise OFFSIM_EINVAL).  Argument validation happens before any HIP call; N = 0 zeroes the outputs and launches nothing. */
+int offsim_latent_counts(const int32_t *z, int32_t L, int64_t N, int32_t nZ, const int32_t *labels, int32_t nY, int64_t *out_counts,
+                         int64_t *out_joint, int64_t *out_skipped, void *stream);
+
 /* The policy network of a row-policy evaluation (offsim4rl/agents/ppo.py:18-27, spinup's MLPCategoricalActor: logits_net =
  * Linear -> act -> ... -> Linear, probs = Categorical(logits=...).probs, a max-subtracted softmax):
  *   out_probs[m] = softmax(L_n(act(... act(L_1(x[rows[m]])))))   m < M, f32 [M, nA] with nA = the last layer's `out`.

@@ -294,6 +294,8 @@ SIGNATURES = {
     "offsim_async_faults": (C.c_int, []),
     "offsim_encode_box": (C.c_int, [_vp, _i64, _vp, _vp]),
     "offsim_encode_mlp": (C.c_int, [_vp, _i32, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "offsim_encode_mlp_pop": (C.c_int, [_vp, _i32, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "offsim_latent_counts": (C.c_int, [_vp, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "offsim_eval_mc_rows_policy": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), _vp, _vp, _i32, _i32, C.c_double, _vp, _i64, _i64,
                                              C.POINTER(EvalMCOut), _vp, _vp]),
     "offsim_eval_mc_rows_policy_pop": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), _vp, _vp, _i32, _i32, _i32, _i32, C.c_double, _vp, _i64,

@@ -24,11 +24,23 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // MFMA 32x32 C/D: register g of lane l is matrix row (g&3) + 8*(g>>2) + 4*(l>>5), column l&31
 __device__ __forceinline__ int cd_row(int g, int hi) { return (g & 3) + 8 * (g >> 2) + 4 * hi; }
 
-template <typename XT, int HT /* hidden tiles of 32 */, int ZT /* latent tiles of 32 */>
+// POP (all four encoder kernels): a stacked population (offsim_encode_mlp_pop: W1 [L][H][dO], b1 [L][H], W2 [L][nZ][H], b2 [L][nZ], out_z
+// [L][N], out_logits [L][N][nZ]); the learner is blockIdx.y, a workgroup serves one learner and walks the rows as the single call's does.
+#define ENC_POP_LEARNER(DOv)                                       \
+    if constexpr (POP) {                                           \
+        const int64_t lrn = blockIdx.y;                            \
+        W1 += lrn * H * (DOv), b1 += lrn * H;                      \
+        W2 += lrn * nZ * H, b2 += lrn * nZ;                        \
+        out_z += lrn * N;                                          \
+        if (out_logits) out_logits += lrn * N * nZ;                \
+    }
+
+template <typename XT, int HT /* hidden tiles of 32 */, int ZT /* latent tiles of 32 */, bool POP = false>
 __global__ void __launch_bounds__(256) k_encode_mlp_mfma(const XT *__restrict__ x, int64_t N, int dO, const float *__restrict__ W1,
                                                          const float *__restrict__ b1, int H, const float *__restrict__ W2,
                                                          const float *__restrict__ b2, int nZ, int32_t *__restrict__ out_z,
                                                          float *__restrict__ out_logits) {
+    ENC_POP_LEARNER(dO)
     extern __shared__ __align__(16) float lds_w[];
     const int dOp = (dO + 1) & ~1;           // k extent of layer 1, padded to the MFMA's K = 2
     const int s1 = dOp + 1, s2 = HT * 32 + 1;  // padded LDS row strides (bank-conflict-free column reads)
@@ -139,11 +151,12 @@ __global__ void __launch_bounds__(256) k_encode_mlp_mfma(const XT *__restrict__ 
 // half): contiguous) arrives as a few 16-byte loads issued a tile ahead, and the loop is MFMAs with conversions in their shadow.
 // The order of the k summation is the kernel's above, but the accumulators start from the bias where the kernel above adds it last, so the
 // logits agree to rounding, not bit for bit (measured: most differ in the last bits, by at most 8e-8 of the sum of absolute terms).
-template <typename XT, int DO, int HT, int ZT, int WPE /* wavefronts per SIMD the registers are budgeted for */>
+template <typename XT, int DO, int HT, int ZT, int WPE /* wavefronts per SIMD the registers are budgeted for */, bool POP = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     k_encode_mlp_mfma_reg(const XT *__restrict__ x, int64_t N, const float *__restrict__ W1, const float *__restrict__ b1, int H,
                           const float *__restrict__ W2, const float *__restrict__ b2, int nZ, int32_t *__restrict__ out_z,
                           float *__restrict__ out_logits) {
+    ENC_POP_LEARNER(DO)
     constexpr int DOP = (DO + 1) & ~1, HALF = DOP / 2;
     constexpr int XB = HALF * (int)sizeof(XT);                  // bytes of an observation row one lane reads
     constexpr int XW = XB % 16 == 0 ? XB / 16 : 0;              // ... as 16-byte words (0: element by element)
@@ -328,11 +341,12 @@ __device__ __forceinline__ EncParts enc_split3(float a, float b) {
 #define ENC_SPLIT3(A, B, H, M, L) do { const EncParts _p = enc_split3(A, B); H = _p.h; M = _p.m; L = _p.l; } while (0)
 #define ENC_MFMA_BF16(A, B, C) __builtin_amdgcn_mfma_f32_32x32x16_bf16(enc_bf(A), enc_bf(B), C, 0, 0, 0)
 
-template <typename XT, int DO, int HT, int ZT, int WPE>
+template <typename XT, int DO, int HT, int ZT, int WPE, bool POP = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     k_encode_mlp_mfma_split(const XT *__restrict__ x, int64_t N, const float *__restrict__ W1, const float *__restrict__ b1, int H,
                             const float *__restrict__ W2, const float *__restrict__ b2, int nZ, int32_t *__restrict__ out_z,
                             float *__restrict__ out_logits) {
+    ENC_POP_LEARNER(DO)
     constexpr int DOP = (DO + 1) & ~1, HALF = DOP / 2;
     constexpr int XB = HALF * (int)sizeof(XT);
     constexpr int XW = XB % 16 == 0 ? XB / 16 : 0;

@@ -2267,12 +2267,15 @@ __device__ __forceinline__ float x_f32<float>(const float *x, int64_t i) { retur
 template <>
 __device__ __forceinline__ float x_f32<__half>(const __half *x, int64_t i) { return __half2float(x[i]); }
 
+#include "encode_mfma.hpp"
+
 #define MLP_MAX_H 128
-template <typename XT>
+template <typename XT, bool POP = false>
 __global__ void __launch_bounds__(256) k_encode_mlp(const XT *__restrict__ x, int64_t N, int dO, const float *__restrict__ W1,
                                                     const float *__restrict__ b1, int H, const float *__restrict__ W2,
                                                     const float *__restrict__ b2, int nZ, int32_t *__restrict__ out_z,
                                                     float *__restrict__ out_logits) {
+    ENC_POP_LEARNER(dO)
     extern __shared__ __align__(16) unsigned char lds_raw[];
     float *w1 = (float *)lds_raw;  // [H][dO]
     float *bb1 = w1 + H * dO;      // [H]
@@ -2308,11 +2311,21 @@ __global__ void __launch_bounds__(256) k_encode_mlp(const XT *__restrict__ x, in
         out_z[row] = best;
     }
 }
-#include "encode_mfma.hpp"
+#undef ENC_POP_LEARNER
 
+// Workgroups per learner of a population call (include/offsim.h, offsim_encode_mlp_pop): the single call's count `single`, capped by the
+// workgroups the learner's N rows fill (`rows_per_wg` rows a pass each), but never so few that the L learners together start fewer than
+// the single call does.  L = 1 gives the single call's grid.
+static unsigned enc_pop_grid(unsigned single, int64_t N, int64_t rows_per_wg, int32_t L) {
+    const int64_t need = (N + rows_per_wg - 1) / rows_per_wg, share = ((int64_t)single + L - 1) / L;
+    const int64_t capped = need < (int64_t)single ? need : (int64_t)single;
+    return (unsigned)(capped > share ? capped : share);
+}
+
+// n_pop: 0 = one network (offsim_encode_mlp); L = a stacked population (offsim_encode_mlp_pop), the learner is the grid's y
 template <typename XT>
-static int launch_mlp_mfma(const XT *x, int64_t N, int dO, const float *W1, const float *b1, int H, const float *W2, const float *b2,
-                           int nZ, int32_t *out_z, float *out_logits, hipStream_t st) {
+static int launch_mlp_mfma(const char *who, const XT *x, int64_t N, int dO, const float *W1, const float *b1, int H, const float *W2,
+                           const float *b2, int nZ, int32_t *out_z, float *out_logits, hipStream_t st, int32_t n_pop) {
     const int HT = (H + 31) / 32, ZT = (nZ + 31) / 32;
     const int dOp = (dO + 1) & ~1;
     {   // weights in registers (encode_mfma.hpp, second kernel): the observation widths of the reference's configurations, hidden layer
@@ -2324,14 +2337,20 @@ static int launch_mlp_mfma(const XT *x, int64_t N, int dO, const float *W1, cons
         if (nb < 1) nb = 1;
         // OFFSIM_ENCODER_F32=1: the exact-f32 products (round 3's kernel); default: the same kernel on bf16 x 3 (encode_mfma.hpp)
         static const bool f32_products = getenv("OFFSIM_ENCODER_F32") && atoi(getenv("OFFSIM_ENCODER_F32")) != 0;
+#define LAUNCH_REG_(KERNEL, DOc, HTc, ZTc, WPEc)                                                                                       \
+    do {                                                                                                                               \
+        if (n_pop) { /* a wavefront takes 32 PF rows a pass: PF = 1 where a lane's share of a row is >= 64 bytes, else 2 */            \
+            const int64_t pf = (((DOc + 1) & ~1) / 2) * (int64_t)sizeof(XT) >= 64 ? 1 : 2;                                             \
+            hipLaunchKernelGGL((KERNEL<XT, DOc, HTc, ZTc, WPEc, true>), dim3(enc_pop_grid(nb * WPEc, N, 4 * 32 * pf, n_pop), n_pop),    \
+                               dim3(256), 0, st, x, N, W1, b1, H, W2, b2, nZ, out_z, out_logits);                                      \
+        } else                                                                                                                         \
+            hipLaunchKernelGGL((KERNEL<XT, DOc, HTc, ZTc, WPEc>), dim3(nb * WPEc), dim3(256), 0, st, x, N, W1, b1, H, W2, b2, nZ,      \
+                               out_z, out_logits);                                                                                     \
+    } while (0)
 #define LAUNCH_REG(DOc, HTc, ZTc, WPEc)                                                                                                \
     do {                                                                                                                               \
-        if (f32_products)                                                                                                              \
-            hipLaunchKernelGGL((k_encode_mlp_mfma_reg<XT, DOc, HTc, ZTc, WPEc>), dim3(nb * WPEc), dim3(256), 0, st, x, N, W1, b1, H, W2, b2, nZ, \
-                               out_z, out_logits);                                                                                     \
-        else                                                                                                                           \
-            hipLaunchKernelGGL((k_encode_mlp_mfma_split<XT, DOc, HTc, ZTc, WPEc>), dim3(nb * WPEc), dim3(256), 0, st, x, N, W1, b1, H, W2, b2, nZ, \
-                               out_z, out_logits);                                                                                     \
+        if (f32_products) LAUNCH_REG_(k_encode_mlp_mfma_reg, DOc, HTc, ZTc, WPEc);                                                     \
+        else LAUNCH_REG_(k_encode_mlp_mfma_split, DOc, HTc, ZTc, WPEc);                                                                \
         LAUNCH_CHECK();                                                                                                                \
         return OFFSIM_OK;                                                                                                              \
     } while (0)
@@ -2344,18 +2363,25 @@ static int launch_mlp_mfma(const XT *x, int64_t N, int dO, const float *W1, cons
             if (dO == 4 && ZT == 2) LAUNCH_REG(4, 2, 2, 2);
         }
 #undef LAUNCH_REG
+#undef LAUNCH_REG_
     }
     size_t lds = sizeof(float) * ((size_t)HT * 32 * (dOp + 1) + (size_t)ZT * 32 * (HT * 32 + 1) + HT * 32 + ZT * 32);
-    if (lds > 160 * 1024) return fail(OFFSIM_EUNSUPPORTED, "encode_mlp: weights exceed LDS%s");
+    if (lds > 160 * 1024) return fail(OFFSIM_EUNSUPPORTED, "%s: weights exceed LDS", who);
     int64_t groups = (N + 31) / 32;
     unsigned nb = (unsigned)((groups + 3) / 4);
     if (nb > 1024) nb = 1024;
     if (nb < 1) nb = 1;
-#define LAUNCH_MFMA(HTc, ZTc)                                                                                              \
+#define LAUNCH_MFMA_(POPc, GRID)                                                                                           \
     do {                                                                                                                   \
         if (lds > 64 * 1024)                                                                                               \
-            HIP_TRY(allow_big_lds((k_encode_mlp_mfma<XT, HTc, ZTc>), (int)lds)); \
-        hipLaunchKernelGGL((k_encode_mlp_mfma<XT, HTc, ZTc>), dim3(nb), dim3(256), lds, st, x, N, dO, W1, b1, H, W2, b2, nZ, out_z, out_logits); \
+            HIP_TRY(allow_big_lds((k_encode_mlp_mfma<XT, HTc_, ZTc_, POPc>), (int)lds)); \
+        hipLaunchKernelGGL((k_encode_mlp_mfma<XT, HTc_, ZTc_, POPc>), GRID, dim3(256), lds, st, x, N, dO, W1, b1, H, W2, b2, nZ, out_z, out_logits); \
+    } while (0)
+#define LAUNCH_MFMA(HTc, ZTc)                                                                                              \
+    do {                                                                                                                   \
+        constexpr int HTc_ = HTc, ZTc_ = ZTc;                                                                              \
+        if (n_pop) LAUNCH_MFMA_(true, dim3(enc_pop_grid(nb, N, 4 * 32, n_pop), n_pop));                                    \
+        else LAUNCH_MFMA_(false, dim3(nb));                                                                                \
     } while (0)
     if (HT == 1 && ZT == 1) LAUNCH_MFMA(1, 1);
     else if (HT == 2 && ZT == 1) LAUNCH_MFMA(2, 1);
@@ -2365,6 +2391,41 @@ static int launch_mlp_mfma(const XT *x, int64_t N, int dO, const float *W1, cons
     else if (HT == 4 && ZT == 2) LAUNCH_MFMA(4, 2);
     else return 1;  // shape outside the MFMA instantiations: caller falls back to the VALU kernel
 #undef LAUNCH_MFMA
+#undef LAUNCH_MFMA_
+    LAUNCH_CHECK();
+    return OFFSIM_OK;
+}
+
+// offsim_encode_mlp (n_pop = 0) and offsim_encode_mlp_pop (n_pop = L): one dispatch rule, `who` names the entry point in the messages
+static int encode_mlp_any(const char *who, const void *x, int32_t x_dtype, int64_t N, int32_t dO, const float *W1, const float *b1, int32_t H,
+                          const float *W2, const float *b2, int32_t nZ, int32_t n_pop, int32_t *out_z, float *out_logits, void *stream) {
+    if (N < 0 || dO <= 0 || H <= 0 || nZ <= 0 || !W1 || !b1 || !W2 || !b2) return fail(OFFSIM_EINVAL, "%s: bad argument", who);
+    if (H > MLP_MAX_H) return fail(OFFSIM_EUNSUPPORTED, "%s: hidden size > 128", who);
+    if (N == 0) return OFFSIM_OK;
+    {   // matrix-core path for the shapes the reference uses (H <= 128, nZ <= 64); VALU kernel otherwise
+        int rc = 1;
+        if (x_dtype == OFFSIM_F32) rc = launch_mlp_mfma<float>(who, (const float *)x, N, dO, W1, b1, H, W2, b2, nZ, out_z, out_logits, (hipStream_t)stream, n_pop);
+        else if (x_dtype == OFFSIM_F16) rc = launch_mlp_mfma<__half>(who, (const __half *)x, N, dO, W1, b1, H, W2, b2, nZ, out_z, out_logits, (hipStream_t)stream, n_pop);
+        if (rc <= 0) return rc;
+    }
+    size_t lds = sizeof(float) * ((size_t)H * dO + H + (size_t)nZ * H + nZ);
+    if (lds > 160 * 1024) return fail(OFFSIM_EUNSUPPORTED, "%s: weights exceed LDS", who);
+    unsigned nb = (unsigned)((N + 255) / 256);
+    if (nb > 2048) nb = 2048;
+    hipStream_t st = (hipStream_t)stream;
+#define LAUNCH_VALU(XT, POPc, GRID)                                                                                                       \
+    do {                                                                                                                                  \
+        if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_encode_mlp<XT, POPc>), (int)lds));                                                  \
+        hipLaunchKernelGGL((k_encode_mlp<XT, POPc>), GRID, dim3(256), lds, st, (const XT *)x, N, dO, W1, b1, H, W2, b2, nZ, out_z, out_logits); \
+    } while (0)
+    if (x_dtype == OFFSIM_F32) {
+        if (n_pop) LAUNCH_VALU(float, true, dim3(enc_pop_grid(nb, N, 256, n_pop), n_pop));
+        else LAUNCH_VALU(float, false, dim3(nb));
+    } else if (x_dtype == OFFSIM_F16) {
+        if (n_pop) LAUNCH_VALU(__half, true, dim3(enc_pop_grid(nb, N, 256, n_pop), n_pop));
+        else LAUNCH_VALU(__half, false, dim3(nb));
+    } else return fail(OFFSIM_EINVAL, "%s: x_dtype must be OFFSIM_F32 or OFFSIM_F16", who);
+#undef LAUNCH_VALU
     LAUNCH_CHECK();
     return OFFSIM_OK;
 }
@@ -2372,27 +2433,71 @@ static int launch_mlp_mfma(const XT *x, int64_t N, int dO, const float *W1, cons
 extern "C" int offsim_encode_mlp(const void *x, int32_t x_dtype, int64_t N, int32_t dO, const float *W1, const float *b1,
                                  int32_t H, const float *W2, const float *b2, int32_t nZ, int32_t *out_z, float *out_logits,
                                  void *stream) {
-    if (N < 0 || dO <= 0 || H <= 0 || nZ <= 0 || !W1 || !b1 || !W2 || !b2) return fail(OFFSIM_EINVAL, "encode_mlp: bad argument%s");
-    if (H > MLP_MAX_H) return fail(OFFSIM_EUNSUPPORTED, "encode_mlp: hidden size > 128%s");
-    if (N == 0) return OFFSIM_OK;
-    {   // matrix-core path for the shapes the reference uses (H <= 128, nZ <= 64); VALU kernel otherwise
-        int rc = 1;
-        if (x_dtype == OFFSIM_F32) rc = launch_mlp_mfma<float>((const float *)x, N, dO, W1, b1, H, W2, b2, nZ, out_z, out_logits, (hipStream_t)stream);
-        else if (x_dtype == OFFSIM_F16) rc = launch_mlp_mfma<__half>((const __half *)x, N, dO, W1, b1, H, W2, b2, nZ, out_z, out_logits, (hipStream_t)stream);
-        if (rc <= 0) return rc;
+    return encode_mlp_any("encode_mlp", x, x_dtype, N, dO, W1, b1, H, W2, b2, nZ, 0, out_z, out_logits, stream);
+}
+
+extern "C" int offsim_encode_mlp_pop(const void *x, int32_t x_dtype, int64_t N, int32_t dO, const float *W1, const float *b1,
+                                     int32_t H, const float *W2, const float *b2, int32_t nZ, int32_t L, int32_t *out_z,
+                                     float *out_logits, void *stream) {
+    if (L < 1 || L > 65535) return fail(OFFSIM_EINVAL, "encode_mlp_pop: L must be in 1..65535%s");
+    if (N > 0 && (!x || !out_z)) return fail(OFFSIM_EINVAL, "encode_mlp_pop: x or out_z is NULL%s");
+    return encode_mlp_any("encode_mlp_pop", x, x_dtype, N, dO, W1, b1, H, W2, b2, nZ, L, out_z, out_logits, stream);
+}
+
+// ---- how the learners of a population use their latent states: per learner a histogram of z [L, N], and of (z, label) ----
+// One LDS histogram per workgroup (nZ * max(nY, 1) 64-bit bins), which serves one learner (blockIdx.y) and 4096 rows a pass; flushed with
+// one atomic add per non-empty bin.  Integer sums: the result does not depend on the order.  A row whose z or label is outside its range
+// is counted in `skipped` only.
+#define LATENT_ROWS_PER_WG 4096
+__global__ void __launch_bounds__(256) k_latent_counts(const int32_t *__restrict__ z, int64_t N, int nZ, const int32_t *__restrict__ labels, int nY,
+                                                       unsigned long long *__restrict__ counts, unsigned long long *__restrict__ joint,
+                                                       unsigned long long *__restrict__ skipped) {
+    extern __shared__ __align__(16) unsigned long long lds_bins[];  // [nZ][nYb]
+    const int nYb = joint ? nY : 1, n_bins = nZ * nYb;
+    const int64_t lrn = blockIdx.y;
+    z += lrn * N;
+    for (int i = threadIdx.x; i < n_bins; i += blockDim.x) lds_bins[i] = 0ull;
+    __syncthreads();
+    unsigned long long skip = 0ull;
+    for (int64_t base = (int64_t)blockIdx.x * LATENT_ROWS_PER_WG; base < N; base += (int64_t)gridDim.x * LATENT_ROWS_PER_WG) {
+        const int64_t end = base + LATENT_ROWS_PER_WG < N ? base + LATENT_ROWS_PER_WG : N;
+        for (int64_t row = base + threadIdx.x; row < end; row += blockDim.x) {
+            const int zv = z[row], yv = labels ? labels[row] : 0;
+            if (zv < 0 || zv >= nZ || (labels && (yv < 0 || yv >= nY))) skip++;
+            else atomicAdd(&lds_bins[zv * nYb + (joint ? yv : 0)], 1ull);
+        }
     }
-    size_t lds = sizeof(float) * ((size_t)H * dO + H + (size_t)nZ * H + nZ);
-    if (lds > 160 * 1024) return fail(OFFSIM_EUNSUPPORTED, "encode_mlp: weights exceed LDS%s");
-    unsigned nb = (unsigned)((N + 255) / 256);
-    if (nb > 2048) nb = 2048;
+    __syncthreads();
+    for (int i = threadIdx.x; i < n_bins; i += blockDim.x) {
+        const unsigned long long c = lds_bins[i];
+        if (c && joint) atomicAdd(&joint[lrn * n_bins + i], c);
+    }
+    for (int zc = threadIdx.x; zc < nZ; zc += blockDim.x) {
+        unsigned long long c = 0ull;
+        for (int y = 0; y < nYb; y++) c += lds_bins[zc * nYb + y];
+        if (c) atomicAdd(&counts[lrn * nZ + zc], c);
+    }
+    for (int off = 32; off > 0; off >>= 1) skip += __shfl_down(skip, off);
+    if ((threadIdx.x & 63) == 0 && skip) atomicAdd(&skipped[lrn], skip);
+}
+
+extern "C" int offsim_latent_counts(const int32_t *z, int32_t L, int64_t N, int32_t nZ, const int32_t *labels, int32_t nY, int64_t *out_counts,
+                                    int64_t *out_joint, int64_t *out_skipped, void *stream) {
+    if (L < 1 || L > 65535) return fail(OFFSIM_EINVAL, "latent_counts: L must be in 1..65535%s");
+    if (N < 0 || nZ <= 0 || !out_counts || !out_skipped || (N > 0 && !z)) return fail(OFFSIM_EINVAL, "latent_counts: bad argument%s");
+    if (!labels && out_joint) return fail(OFFSIM_EINVAL, "latent_counts: out_joint without labels%s");
+    if (labels && nY <= 0) return fail(OFFSIM_EINVAL, "latent_counts: labels need nY >= 1%s");
+    const int64_t image = (int64_t)nZ * (out_joint ? nY : 1) * 8;
+    if (image > 64 * 1024) return fail(OFFSIM_EUNSUPPORTED, "latent_counts: nZ * max(nY, 1) * 8 bytes exceed 64 KiB of LDS%s");
     hipStream_t st = (hipStream_t)stream;
-    if (x_dtype == OFFSIM_F32) {
-        if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_encode_mlp<float>), (int)lds));
-        hipLaunchKernelGGL(k_encode_mlp<float>, dim3(nb), dim3(256), lds, st, (const float *)x, N, dO, W1, b1, H, W2, b2, nZ, out_z, out_logits);
-    } else if (x_dtype == OFFSIM_F16) {
-        if (lds > 64 * 1024) HIP_TRY(allow_big_lds((k_encode_mlp<__half>), (int)lds));
-        hipLaunchKernelGGL(k_encode_mlp<__half>, dim3(nb), dim3(256), lds, st, (const __half *)x, N, dO, W1, b1, H, W2, b2, nZ, out_z, out_logits);
-    } else return fail(OFFSIM_EINVAL, "encode_mlp: x_dtype must be OFFSIM_F32 or OFFSIM_F16%s");
+    HIP_TRY(hipMemsetAsync(out_counts, 0, sizeof(int64_t) * (size_t)L * nZ, st));
+    HIP_TRY(hipMemsetAsync(out_skipped, 0, sizeof(int64_t) * (size_t)L, st));
+    if (out_joint) HIP_TRY(hipMemsetAsync(out_joint, 0, sizeof(int64_t) * (size_t)L * nZ * nY, st));
+    if (N == 0) return OFFSIM_OK;
+    int64_t nb = (N + LATENT_ROWS_PER_WG - 1) / LATENT_ROWS_PER_WG;  // workgroups per learner: ceil(N / 4096), at most 1024
+    if (nb > 1024) nb = 1024;
+    hipLaunchKernelGGL(k_latent_counts, dim3((unsigned)nb, (unsigned)L), dim3(256), (size_t)image, st, z, N, nZ, labels, nY,
+                       (unsigned long long *)out_counts, (unsigned long long *)out_joint, (unsigned long long *)out_skipped);
     LAUNCH_CHECK();
     return OFFSIM_OK;
 }

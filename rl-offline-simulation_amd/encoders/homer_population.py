@@ -7,9 +7,14 @@ has its own weights, Adam state, hyperparameters, batch indices, Gumbel noise an
 numbers are, bit for bit, those of a HOMEREncoder fed learner l's indices and noise.
 
 The population owns the stacked device weights (every tensor of the state_dict with a leading learner axis) and steps them in place;
-encoder(l) / state_dict(l) / best_state_dict(l) export one learner."""
+encoder(l) / state_dict(l) / best_state_dict(l) export one learner.
+
+The population is also used as one: encode / encode_device run every learner over the same observations in one launch
+(offsim_encode_mlp_pop, the learner as a grid dimension of the encoder's kernels), latent_report counts what each learner makes of a log
+(offsim_latent_counts), and evaluators builds each learner's PerStateRejectionSampling from two such launches."""
 import math
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -40,6 +45,19 @@ def epoch_draws(generator, L, n, nZ):
     idx_real, idx_impo = perms(), perms()
     noise = -torch.empty((L, n, 4, nZ), dtype=torch.float32, device=dev).exponential_(generator=generator).log()
     return idx_real, idx_impo, noise
+
+
+LatentReport = namedtuple("LatentReport", "z counts used joint purity skipped")
+
+
+def latent_stats(counts, joint, n_rows):
+    """(used [L] i64, purity [L] f64 or None) of counts [L, nZ] and joint [L, nZ, nY] (or None), exact integers: used = the non-empty
+    latent states, purity = sum_z max_y joint[l, z, y] / n_rows in f64 (0 rows: 0).  torch on the tensors' device, nothing read back."""
+    used = (counts > 0).sum(dim=1)
+    if joint is None:
+        return used, None
+    hits = joint.max(dim=2).values.sum(dim=1).to(torch.float64)
+    return used, hits / torch.full_like(hits, max(int(n_rows), 1))  # (tensor by tensor: a scalar divisor is multiplied by as its reciprocal on the device)
 
 
 class HOMERPopulation:
@@ -318,6 +336,97 @@ class HOMERPopulation:
         return HOMEREncoder(self.obs_dim, self.action_dim, self.latent_size, self.hidden_size,
                             state_dict=self.best_state_dict(l) if best else self.state_dict(l), device=self.device)
 
+    # ---- the population in use: all learners over a set of observations per launch ----
+    def _enc_weights(self, best):
+        """(W1 [L, H, dO], b1 [L, H], W2 [L, nZ, H], b2 [L, nZ]) on the device: the current weights, or with `best` those of the best
+        validation epoch of the last train() (before train(), the current ones: best_state_dict's rule)"""
+        if self._host is None and self._p is None:  # homer.py:160-161 (a population is constructed with weights, so this never fires)
+            raise ValueError("Model not initialized. Either train a new model for the encoder or load an existing one.")
+        return (self._best if best and self._best is not None else self._params())[:4]
+
+    def encode_device(self, x, return_logits=False, best=False):
+        """x [N, dO] f32 / f16 on the device -> z [L, N] i32, with return_logits also the logits [L, N, nZ] f32, in ONE launch
+        (offsim_encode_mlp_pop).  z[l] and logits[l] are encoder(l, best).encode_device(x)'s bit for bit."""
+        W1, b1, W2, b2 = self._enc_weights(best)
+        if x.dtype not in (torch.float32, torch.float16):
+            x = x.to(torch.float32)
+        x = x.contiguous()
+        if x.dim() != 2 or x.shape[1] != self.obs_dim:
+            raise ValueError(f"HOMERPopulation.encode_device: x must be [N, {self.obs_dim}], got {tuple(x.shape)}")
+        N = x.shape[0]
+        z = torch.empty((self.L, N), dtype=torch.int32, device=x.device)
+        logits = torch.empty((self.L, N, self.latent_size), dtype=torch.float32, device=x.device) if return_logits else None
+        L.check(L.load().offsim_encode_mlp_pop(L.ptr(x), L.F16 if x.dtype == torch.float16 else L.F32, N, self.obs_dim, L.ptr(W1), L.ptr(b1),
+                                               self.hidden_size, L.ptr(W2), L.ptr(b2), self.latent_size, self.L, L.ptr(z), L.ptr(logits),
+                                               L.stream_ptr()))
+        return (z, logits) if return_logits else z
+
+    def _observations_on_device(self, observations):
+        """HOMEREncoder.encode's rule: float16 observations stay float16, everything else goes to float32; [N, dO], uploaded once"""
+        dev = self._params()[0].device
+        obs = observations if isinstance(observations, torch.Tensor) else np.asarray(observations)
+        half = obs.dtype in (np.float16, torch.float16)
+        if isinstance(obs, torch.Tensor):
+            x = obs.to(device=dev, dtype=torch.float16 if half else torch.float32)
+        else:
+            x = torch.from_numpy(np.ascontiguousarray(obs, dtype=np.float16 if half else np.float32)).to(dev)
+        self.last_input_dtype = x.dtype
+        return x.reshape(x.shape[0], -1)
+
+    def encode(self, observations, best=False):
+        """every learner's HOMEREncoder.encode of the same observations: np.int64 [L, N], one upload and one launch"""
+        return self.encode_device(self._observations_on_device(observations), best=best).cpu().numpy().astype(np.int64)
+
+    def latent_counts(self, z, labels=None, n_labels=None):
+        """offsim_latent_counts of z [L, N] i32 on the device (and labels [N] i32 in [0, n_labels)): (counts [L, nZ], joint [L, nZ, nY] or
+        None, skipped [L]), i64 device tensors"""
+        z = z.to(torch.int32).contiguous()
+        n, N = z.shape
+        if (labels is None) != (n_labels is None):
+            raise ValueError("HOMERPopulation.latent_counts: labels and n_labels go together")
+        nZ, nY = self.latent_size, 0 if labels is None else int(n_labels)
+        if labels is not None:
+            labels = labels.to(z.device, torch.int32).contiguous()
+            if labels.shape != (N,) or nY < 1:
+                raise ValueError(f"HOMERPopulation.latent_counts: labels must be [{N}] with n_labels >= 1, got {tuple(labels.shape)}, {nY}")
+        counts = torch.empty((n, nZ), dtype=torch.int64, device=z.device)
+        joint = None if labels is None else torch.empty((n, nZ, nY), dtype=torch.int64, device=z.device)
+        skipped = torch.empty(n, dtype=torch.int64, device=z.device)
+        L.check(L.load().offsim_latent_counts(L.ptr(z), n, N, nZ, L.ptr(labels), nY, L.ptr(counts), L.ptr(joint), L.ptr(skipped), L.stream_ptr()))
+        return counts, joint, skipped
+
+    def latent_report(self, observations, labels=None, n_labels=None, best=False):
+        """What the L encoders make of a log (the reference looks at this with _visualize): LatentReport of device tensors, nothing read
+        back.  z [L, N] i32; counts [L, nZ] i64 rows per latent state; used [L] the number of non-empty latent states; skipped [L] rows
+        counted nowhere (a label outside [0, n_labels)); with labels [N] (the true state, say; n_labels = their number, by default
+        max + 1 of labels given on the host) also joint [L, nZ, nY] and purity [L] f64 = sum_z max_y joint[l, z, y] / N, the share of rows
+        whose label is the most frequent one of their latent state (1.0: every latent state holds one true state)."""
+        z = self.encode_device(self._observations_on_device(observations), best=best)
+        if labels is not None:
+            if n_labels is None:
+                if isinstance(labels, torch.Tensor) and labels.device.type != "cpu":
+                    raise ValueError("HOMERPopulation.latent_report: give n_labels with labels on the device (no host read in here)")
+                n_labels = int(np.asarray(labels).max()) + 1 if len(labels) else 1
+            labels = labels if isinstance(labels, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(labels))
+            labels = labels.reshape(-1)
+        counts, joint, skipped = self.latent_counts(z, labels, n_labels if labels is not None else None)
+        used, purity = latent_stats(counts, joint, z.shape[1])
+        return LatentReport(z, counts, used, joint, purity, skipped)
+
+    def evaluators(self, dataset, learners=None, best=False, cls=None):
+        """[cls.from_latents(dataset, ...) for the chosen learners (default: all)], cls = PerStateRejectionSampling or a subclass:
+        observations and next_observations are each uploaded once and encoded by all learners in one launch, where building
+        cls(dataset, num_states, encoder=population.encoder(l)) per learner uploads and encodes both 2 L times."""
+        if cls is None:
+            from ..evaluators.per_state_rejection import PerStateRejectionSampling as cls
+        learners = list(range(self.L)) if learners is None else [int(l) for l in learners]
+        for l in learners:
+            if not 0 <= l < self.L:
+                raise IndexError(f"HOMERPopulation: learner {l} of {self.L}")
+        e = dataset.experience
+        zs, next_zs = self.encode(e["observations"], best=best), self.encode(e["next_observations"], best=best)
+        return [cls.from_latents(dataset, zs[l], next_zs[l], self.latent_size) for l in learners]
+
     def best(self):
         """the learner with the lowest best_val_loss of the last train()"""
         if self.result is None:
@@ -325,4 +434,4 @@ class HOMERPopulation:
         return int(np.argmin(self.result.best_val_loss))
 
 
-__all__ = ["HOMERPopulation", "HomerTrainResult", "epoch_draws"]
+__all__ = ["HOMERPopulation", "HomerTrainResult", "LatentReport", "epoch_draws", "latent_stats"]

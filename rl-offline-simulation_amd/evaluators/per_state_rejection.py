@@ -48,6 +48,37 @@ class PerStateRejectionSampling(RevealedRandomnessEnv):
             obs=e["observations"], next_obs=e["next_observations"], reject_mode=rule)
         self.new_step_api = new_step_api
 
+    @classmethod
+    def from_latents(cls, dataset, zs, next_zs, num_states, new_step_api=False):
+        """The evaluator of `dataset` over latent states already computed (HOMERPopulation.evaluators: every learner's zs from one
+        launch): the constructor's PSRS.from_arrays call with zs / next_zs [n] handed in where the constructor asks encoder.encode for
+        them.  Same errors, same rejection rule of the subclass, same table as cls(dataset, num_states, encoder) whose encoder gives
+        these latents."""
+        if num_states is None:
+            raise ValueError("PerStateRejectionSampling.from_latents: num_states must be given with the latent states")
+        if not is_discrete(dataset.action_space):
+            raise ValueError("PerStateRejectionSampling currently only supports discrete action spaces")
+        e = dataset.experience
+        zs, next_zs = np.asarray(zs), np.asarray(next_zs)
+        n = len(zs)
+        if zs.ndim != 1 or next_zs.shape != zs.shape or n != len(e["actions"]):
+            raise ValueError(f"PerStateRejectionSampling.from_latents: zs and next_zs must be one latent state per transition "
+                             f"({len(e['actions'])}), got {zs.shape} and {next_zs.shape}")
+        if "action_distributions" not in e:
+            raise ValueError("PerStateRejectionSampling needs action_distributions (the logging policy's probabilities)")
+        self = cls.__new__(cls)
+        self._dataset = dataset
+        t0 = (np.asarray(e["steps"]) == 0) if "steps" in e else None
+        rule = getattr(cls, "_device_reject_mode", None)
+        overridden = cls._reject is not PerStateRejectionSampling._reject
+        self._impl = PSRS.from_arrays(
+            zs, e["actions"], e["rewards"], next_zs, e["terminals"], np.asarray(e["action_distributions"]).reshape(n, -1),
+            t0=t0, nS=num_states, nA=dataset.action_space.n,
+            reject_func=(self._reject if (overridden and rule is None) else None),
+            obs=e["observations"], next_obs=e["next_observations"], reject_mode=rule)
+        self.new_step_api = new_step_api
+        return self
+
     @property
     def observation_space(self):
         return self._dataset.observation_space

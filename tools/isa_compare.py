@@ -6,7 +6,8 @@ a line-by-line comparison.  Normalised: addresses, the <symbol+offset> comments 
 s_addc_u32 pair after an s_getpc_b64 (the pc-relative distance to a global, which moves with the size of the code around it).  Nothing
 else: register numbers and kernel-argument offsets count as differences.  Prints the counts, the identical instances by kernel, and for
 every differing or one-sided instance the figures of the code object's notes, in the format of the reports under profiles/.  Needs no
-GPU.  Exit status 0 whatever the outcome: the report is the result.
+GPU.  Exit status 0 whatever the outcome: the report is the result.  --defaulted-false: an instance of the new build whose template
+argument list ends in `, false` is compared with the parent's instance without it (a kernel that gained a defaulted trailing parameter).
 """
 import collections
 import difflib
@@ -101,7 +102,8 @@ def worse(p, b):
     return any(b.get(k, 0) > p.get(k, 0) for k in ("vgpr_count", "private_segment_fixed_size", "vgpr_spill_count")) or w(b) < w(p)
 
 
-def main(parent_so, new_so):
+def main(parent_so, new_so, defaulted=False):
+    renamed = []
     with tempfile.TemporaryDirectory() as tmp:
         cos = []
         for tag, so in (("parent", parent_so), ("branch", new_so)):
@@ -111,6 +113,15 @@ def main(parent_so, new_so):
         fp, fb = functions(cos[0]), functions(cos[1])
         np_, nb = notes(cos[0]), notes(cos[1])
     pretty = demangle(set(fp) | set(fb))
+    if defaulted:  # a kernel that gained a defaulted trailing template parameter: its instance `..., false>(` is the parent's `...>(`
+        by_pretty = {pretty[n]: n for n in fp if n not in fb}
+        for n in [n for n in fb if n not in fp]:
+            old = by_pretty.get(pretty[n].replace(", false>(", ">(", 1))
+            if old is not None and ", false>(" in pretty[n]:
+                fb = collections.OrderedDict((old if k == n else k, v) for k, v in fb.items())
+                if n in nb:
+                    nb[old] = nb.pop(n)
+                renamed.append(pretty[n])
     both = [n for n in fp if n in fb]
     same = [n for n in both if fp[n] == fb[n]]
     diff = [n for n in both if fp[n] != fb[n]]
@@ -118,6 +129,10 @@ def main(parent_so, new_so):
     w = sys.stdout.write
     w(f"functions in .text: parent {len(fp)}, branch {len(fb)}; identical line for line {len(same)}, different {len(diff)}, "
       f"in the parent only {len(only_p)}, in the branch only {len(only_b)}\n\n")
+    if renamed:
+        c = collections.Counter(kernel_of(p) for p in renamed)
+        w("matched to the parent's instance by dropping a trailing defaulted `, false` template argument (instances): "
+          + ", ".join(f"{k} {c[k]}" for k in sorted(c)) + "\n\n")
     w("identical line for line, by kernel (instances):\n" + by_kernel(same, pretty))
     w("\ndifferent (figures from the code object's notes; waves = waves per SIMD the VGPR count allows):\n")
     n_worse = 0
@@ -138,6 +153,7 @@ def main(parent_so, new_so):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) != 3:
+    args = [a for a in sys.argv[1:] if a != "--defaulted-false"]
+    if len(args) != 2:
         sys.exit(__doc__)
-    main(sys.argv[1], sys.argv[2])
+    main(args[0], args[1], defaulted=len(args) != len(sys.argv) - 1)
