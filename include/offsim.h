@@ -971,6 +971,85 @@ int offsim_queue_collect_ppo_pop(const offsim_table *t, offsim_rollouts *ro, int
                                  const offsim_collect_state *st, const offsim_collect_out *out, int32_t *out_action,
                                  const offsim_collect_ppo_out *ppo, void *stream);
 
+/* ---- the same collection in the environments that produced the logs (VectorGridNavi / VectorCartPole) ---------------------------------
+ * The other half of the reference's experiments: the learner's loop in the real environment, to set beside its loop inside a simulator
+ * built from a log.  offsim_env_collect is offsim_queue_collect with the environment's dynamics in the place of the queue pop -- there is
+ * no table, nothing is popped, and an environment never runs dry; offsim_env_collect_ppo and offsim_env_collect_ppo_pop add what
+ * offsim_vector_collect_ppo and offsim_vector_collect_ppo_pop add.  The policy, critic and PPO record structs are theirs.
+ * Environments (env->kind), R of them, every one with two PCG64 streams ([R,4] words as offsim_seed_streams writes them): rng_act, from
+ * which its actions are drawn, and rng_env, from which the environment draws its own noise and resets:
+ *   OFFSIM_ENV_GRID         the reference's MyGridNavi (offsim4rl/envs/gridworld.py:14-124) with discrete observations: nA = 5 (noop, up,
+ *                           right, down, left), the observation is the cell id x + num_cells * y (i32; a network reads it as one f32);
+ *   OFFSIM_ENV_GRID_COORDS  MyGridNaviCoords (:187-211): observation (x / 5 + 0.1 + d0, y / 5 + 0.1 + d1) computed in f64 and rounded once
+ *                           to f32, d = -0.1 + 0.2 * next_double drawn twice at every step and twice at every reset -- default_rng(seed)
+ *                           .uniform(-0.1, 0.1, 2), continuing across resets as reset() without a seed does.  The divisor is the literal 5;
+ *   OFFSIM_ENV_CARTPOLE     CartPole-v1: nA = 2, Euler steps of tau = 0.02 in f64 with the operation order of the package's host generator
+ *                           (synth.cartpole_log), terminated at |x| > 2.4 or |theta| > 12 degrees, reward 1, a reset draws
+ *                           uniform(-0.05, 0.05, 4) = -0.05 + 0.1 * next_double; the f32 observation is the f64 state rounded once.
+ * Grid step, MyGridNavi.step to the letter: done if the agent stands on the goal before it moves; the move, clamped at the walls;
+ * step_count += 1 and done at step_count >= num_steps; reward 0 if done, else 1 (and done) on reaching the goal, else -0.1.  The old
+ * API's `done` is recorded as terminated.  goal_x / goal_y, num_cells (1..1024) and num_steps (>= 1) are parameters.
+ * State carried between calls, all in/out: state [R,4] f64 -- CartPole (x, x_dot, theta, theta_dot); the grids (x, y, obs_0, obs_1) with
+ * the f64 observation of GRID_COORDS (zeros for GRID) -- step_count [R] (the grids'), ep_t [R] (steps of the open episode), and the
+ * two streams' positions.  offsim_env_collect_reset is reset() for the environments in mask (NULL: all): the start state, step_count =
+ * ep_t = 0, the reset's draws taken from rng_env.  It does not touch rng_act.
+ * Per step: the critic, then the policy at the current observation -- OFFSIM_COLLECT_MLP (offsim_policy_mlp's bits; x_dtype must be
+ * OFFSIM_F32 and dO the observation's width 1 / 2 / 4; x_start / x_next / x_init are not read) or, on the grids, OFFSIM_COLLECT_TABULAR
+ * (pi [num_cells^2, 5] by cell id, x_dtype its element type OFFSIM_F32 | OFFSIM_F64, widened exactly to f64); there are no logged rows and
+ * so no ROWS form (OFFSIM_EUNSUPPORTED, as TABULAR on CartPole) -- then A drawn as offsim_queue_collect draws it, one draw of rng_act per
+ * asked step; the dynamics; ep_t += 1, truncated = max_episode_steps > 0 && ep_t >= max_episode_steps; on terminated or truncated the
+ * reset and ep_t = 0.  No A (a row of NaN or zeros): the environment stops for the rest of the launch with OFFSIM_ST_KEYERROR, state as
+ * it was, the draw consumed; otherwise every asked step is served and status stays OFFSIM_ST_OK.
+ * Records, step-major [T,R]; obs / next_obs / state / next_state / probs / status may be NULL:
+ *   obs, next_obs      rows of the observation's width, f32 (GRID: one i32, the cell id); next_obs is the true next observation, not the
+ *                      one a reset puts in its place;
+ *   state, next_state  CartPole: [T,R,4] f64; the grids: [T,R] i32 cell ids z / z_next;
+ *   probs [T,R,nA] f32, action [T,R] i32 (nA where none could be drawn, -1 where nothing was asked), reward [T,R] f32, flags [T,R]
+ *   OFFSIM_COLLECT_* bits (SERVED and ALIVE at every served step), ep_step [T,R] i32 (the step's index in its episode);
+ *   value / logp / final_value / v_trunc as offsim_vector_collect_ppo's, the critic OFFSIM_VALUE_MLP only.
+ * Limits: the networks' floats as offsim_vector_collect[_ppo]'s; the workgroup's LDS -- [actor | pi as f64][critic][16 f64 + 16 f32 + 2
+ * activation rows + 8 f32 per environment], 8 environments -- at most 160 KiB (OFFSIM_EUNSUPPORTED beyond).
+ * offsim_env_collect_ppo_pop: L learners of E environments each, learner-major, grid (ceil(E / 8), L), stacked networks, MLP actors with
+ * MLP critics only, L in 1..65535, env->R = L * E -- offsim_vector_collect_ppo_pop's rules, and every environment equals
+ * offsim_env_collect_ppo with its learner's networks bit for bit.
+ * Argument validation happens before any HIP call; T = 0 or R = 0 launches nothing (the record pointers may then be NULL). */
+#define OFFSIM_ENV_GRID 0
+#define OFFSIM_ENV_GRID_COORDS 1
+#define OFFSIM_ENV_CARTPOLE 2
+typedef struct offsim_env {
+    int32_t kind;                      /* OFFSIM_ENV_*                                              */
+    int32_t R;                         /* environments                                              */
+    int32_t num_cells;                 /* grids                                                     */
+    int32_t num_steps;                 /* grids: MyGridNavi._max_episode_steps                      */
+    int32_t goal_x;
+    int32_t goal_y;
+    uint64_t *rng_env;                 /* [R,4] in/out                                              */
+    uint64_t *rng_act;                 /* [R,4] in/out                                              */
+    double *state;                     /* [R,4] in/out                                              */
+    int32_t *step_count;               /* [R] in/out                                                */
+    int32_t *ep_t;                     /* [R] in/out                                                */
+} offsim_env;
+typedef struct offsim_env_out {
+    void *obs;                         /* [T,R] rows, or NULL                                       */
+    void *next_obs;                    /* [T,R] rows, or NULL                                       */
+    void *state;                       /* [T,R,4] f64 | [T,R] i32, or NULL                          */
+    void *next_state;                  /* likewise                                                  */
+    float *probs;                      /* [T,R,nA], or NULL                                         */
+    int32_t *action;                   /* [T,R]                                                     */
+    float *reward;                     /* [T,R]                                                     */
+    uint8_t *flags;                    /* [T,R]                                                     */
+    int32_t *ep_step;                  /* [T,R]                                                     */
+    int32_t *status;                   /* [R], or NULL                                              */
+} offsim_env_out;
+int offsim_env_collect_reset(const offsim_env *env, const uint8_t *mask, void *stream);
+int offsim_env_collect(const offsim_env *env, const offsim_collect_policy *pol, int64_t T, int32_t max_episode_steps,
+                       const offsim_env_out *out, void *stream);
+int offsim_env_collect_ppo(const offsim_env *env, const offsim_collect_policy *pol, const offsim_collect_value *val, int64_t T,
+                           int32_t max_episode_steps, const offsim_env_out *out, const offsim_collect_ppo_out *ppo, void *stream);
+int offsim_env_collect_ppo_pop(const offsim_env *env, const offsim_collect_policy *pol, const offsim_collect_value *val, int32_t L, int32_t E,
+                               int64_t T, int32_t max_episode_steps, const offsim_env_out *out, const offsim_collect_ppo_out *ppo,
+                               void *stream);
+
 /* offsim_ppo_advantages: GAE-lambda advantages and rewards-to-go over step-major [T,E] records, with the path rules of the reference's
  * agent, and spinup's advantage normalisation (spinup PPOBuffer.finish_path / get, driven by offsim4rl/agents/ppo.py:106-158; E
  * environments = E MPI processes of local_steps_per_epoch = T).  Per environment e, over its valid steps t (flags & OFFSIM_COLLECT_SERVED):

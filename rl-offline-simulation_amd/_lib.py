@@ -120,6 +120,21 @@ class CollectPPOOut(C.Structure):
     _fields_ = [("value", _vp), ("logp", _vp), ("final_value", _vp), ("v_trunc", _vp)]
 
 
+ENV_GRID, ENV_GRID_COORDS, ENV_CARTPOLE = 0, 1, 2
+
+
+class Env(C.Structure):
+    """struct offsim_env"""
+    _fields_ = [("kind", _i32), ("R", _i32), ("num_cells", _i32), ("num_steps", _i32), ("goal_x", _i32), ("goal_y", _i32), ("rng_env", _vp),
+                ("rng_act", _vp), ("state", _vp), ("step_count", _vp), ("ep_t", _vp)]
+
+
+class EnvOut(C.Structure):
+    """struct offsim_env_out"""
+    _fields_ = [("obs", _vp), ("next_obs", _vp), ("state", _vp), ("next_state", _vp), ("probs", _vp), ("action", _vp), ("reward", _vp),
+                ("flags", _vp), ("ep_step", _vp), ("status", _vp)]
+
+
 PPO_ACTOR, PPO_CRITIC = 0, 1
 PPO_MAX_BLOCKS = 256
 
@@ -320,6 +335,12 @@ SIGNATURES = {
                                            C.POINTER(CollectState), C.POINTER(CollectOut), _vp, C.POINTER(CollectPPOOut), _vp]),
     "offsim_queue_collect_ppo_pop": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), _i32, C.POINTER(CollectPolicy), C.POINTER(CollectValue), _i32,
                                                _i32, _i64, _i32, C.POINTER(CollectState), C.POINTER(CollectOut), _vp, C.POINTER(CollectPPOOut), _vp]),
+    "offsim_env_collect_reset": (C.c_int, [C.POINTER(Env), _vp, _vp]),
+    "offsim_env_collect": (C.c_int, [C.POINTER(Env), C.POINTER(CollectPolicy), _i64, _i32, C.POINTER(EnvOut), _vp]),
+    "offsim_env_collect_ppo": (C.c_int, [C.POINTER(Env), C.POINTER(CollectPolicy), C.POINTER(CollectValue), _i64, _i32, C.POINTER(EnvOut),
+                                         C.POINTER(CollectPPOOut), _vp]),
+    "offsim_env_collect_ppo_pop": (C.c_int, [C.POINTER(Env), C.POINTER(CollectPolicy), C.POINTER(CollectValue), _i32, _i32, _i64, _i32,
+                                             C.POINTER(EnvOut), C.POINTER(CollectPPOOut), _vp]),
     "offsim_ppo_advantages_pop": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, C.c_double, C.c_double, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "offsim_ppo_epoch_log": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "offsim_ppo_epoch_log_pop": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),

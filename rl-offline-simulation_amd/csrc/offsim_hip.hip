@@ -2573,6 +2573,9 @@ extern "C" int offsim_value_mlp(const void *x, int32_t x_dtype, int64_t n_x, int
 // ---- the same collection on QueueEvaluator: the agent draws its action, the simulator pops queue (z, a) (csrc/collect_queue.hpp) ----
 #include "collect_queue.hpp"
 
+// ---- the same collection in the environments that produced the logs: grid worlds and CartPole, dynamics in the kernel (csrc/collect_env.hpp) ----
+#include "collect_env.hpp"
+
 // ---- the PPO buffer: GAE-lambda, rewards-to-go and spinup's normalisation over [T, E] records (csrc/ppo_buffer.hpp) ----
 #include "ppo_buffer.hpp"
 
