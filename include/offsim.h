@@ -613,6 +613,83 @@ int offsim_eval_queue_rows_policy_pop(const offsim_table *t, offsim_rollouts *ro
                                       int32_t p_dtype, int32_t L, int32_t S, double gamma, const double *gamma_pow, int64_t n_gamma_pow,
                                       int64_t max_episodes, const offsim_evalmc_out *out, int32_t *cur_row, int32_t *out_obs_row, void *stream);
 
+/* offsim_eval_env: the reference's tabular drivers -- evalMC (td = NULL; offsim4rl/agents/tabular.py:247-270), qlearn (:71-139) and expSARSA
+ * (:141-191) by td->mode -- on its own GRID WORLDS, all rollouts in ONE launch (csrc/eval_env.hpp): the ground truth that offsim_eval_mc /
+ * offsim_eval_mc_exo (PSRS, PSRS_Exo) and offsim_eval_queue (the (z, a) queue baseline) are judged against.  There is no table: nothing is
+ * popped, an environment never runs dry, and every episode begins with env.reset(seed=episode).
+ *   env  the world (struct offsim_grid_env), nA = 5 (noop, up, right, down, left), start (0, 0), the goal an argument:
+ *          OFFSIM_GRID_PLAIN    MyGridNavi with discrete observations (offsim4rl/envs/gridworld.py:14-124); factor = 1.
+ *          OFFSIM_GRID_NOISE    MyGridNaviNoise (:127-155) with factor = int(augmented_state) >= 1: extra = Generator.integers(factor) at the
+ *                               reset and before the move of every step.
+ *          OFFSIM_GRID_COUNTER  MyGridNaviModuloCounter (:158-184) with factor = counter_limit >= 1: extra = Generator.integers(factor) at
+ *                               the reset, then (extra + 1) % factor before the move of every step.
+ *        The observation is o = x + num_cells * y + num_cells^2 * extra, nS = num_cells^2 * factor; pi and Q are [nS, 5] f64 by observation.
+ *        The exogenous stream is np.random.default_rng(episode0 + e), created again on the device at the reset of episode e of this call.
+ *        integers(n) is NumPy's scalar path: nothing is drawn for n = 1, otherwise Lemire's bounded draw on 32-bit words, which are the low
+ *        and then the high half of each 64-bit output (PCG64's buffered next_uint32): m = word * n, and while the low half of m is below
+ *        (2^32 - n) % n another word is drawn; the result is m >> 32.
+ *   ro   struct offsim_env_rollouts: R rollouts and their ACTION streams, PCG64 rows [R, 4] as offsim_seed_streams writes them (tabular.py:75:
+ *        one default_rng(seed) per rollout that runs on across episodes).  OFFSIM_STREAM_PHILOX is refused with OFFSIM_EUNSUPPORTED (its
+ *        double lies in (0, 1]: u = 1.0 would select action 5).
+ * Per step: p = pi[o], or the behaviour policy on Q[o] (offsim_eval_td's rules, one definition on the device); A = Generator.choice(5, p=p)
+ *   as offsim_eval_queue draws it (c_k = c_{k-1} + p_k in f64 from 0, cdf_k = c_k / c_4, u = (next64 >> 11) * 2^-53, the first k with
+ *   cdf_k > u), one draw per step; extra is updated; then MyGridNavi.step: done if the agent already stands on the goal, the move clamped to
+ *   the grid, step_count += 1 and done at num_steps, reward 0 if done, else 1 and done on reaching the goal, else -0.1 (f64).  A row p without
+ *   a cdf entry above u (NaN, all zeros): OFFSIM_ST_KEYERROR, the draw consumed, the environment not stepped.
+ * td: the update of offsim_eval_td on Q[o, A] with Q[o'] (tabular.py:123-126 / :175-178, the same arithmetic and order); q [R, nS, 5], td_err,
+ *   alpha_ep / epsilon_ep, q_snap [R, snap_cap, nS, 5] / snap_stride / snap_cap, beh_arg, tie_mt, tie_reseed_episode (needs td->tie_mt): all
+ *   offsim_eval_queue's, word for word.  The tie stream of episode e restarts as np.random.seed((episode0 + e) mod 2^32).
+ * out: offsim_eval_mc's (sum_g, n_ep, steps, cand = steps, n_len, status; ep_g, ep_len); trace_pop [R, trace_cap] holds the ACTION drawn at
+ *   every step, the undrawable one (5) of a rollout that stopped with OFFSIM_ST_KEYERROR included (at index steps); trace_row is not written.
+ * On exit the action stream (the state after the last draw), q and tie_mt are written back; every episode begins with a reset, so a second
+ *   call with episode0 moved on by the episodes of the first continues it.
+ * Launch shapes.  Learners: one wavefront per rollout; LDS per workgroup: per rollout Q (nS * 40 bytes), the behaviour row (40) and the tie
+ *   stream (2496), and the shared pi (nS * 40, when given); 4 rollouts per workgroup, then 2, then 1 while the carve exceeds 64 KiB, one rollout
+ *   up to 160 KiB, beyond that -- or num_cells^2 > 40960 -- OFFSIM_EUNSUPPORTED.  evalMC: one LANE per rollout, 256 rollouts per workgroup, pi in
+ *   LDS when its nS * 40 bytes (for a stack: L * nS * 40) are at most 64 KiB and read from global memory otherwise; nS * 5 > 2^24:
+ *   OFFSIM_EUNSUPPORTED.
+ * OFFSIM_EINVAL: NULL env / ro / out / required outputs / q / ro->rng with R > 0, a kind outside OFFSIM_GRID_*, num_cells < 1, num_steps < 1,
+ *   a goal off the grid, factor < 1 (or != 1 for PLAIN), max_episodes <= 0, episode0 < 0, pi = NULL where a policy is read, a bad mode /
+ *   behaviour / snapshot stride / tie_reseed_episode, schedules without n_sched, negative capacities.
+ * Argument validation happens before any HIP call; ro->R = 0 launches nothing. */
+#define OFFSIM_GRID_PLAIN 0
+#define OFFSIM_GRID_NOISE 1
+#define OFFSIM_GRID_COUNTER 2
+typedef struct offsim_grid_env {
+    int32_t kind;      /* OFFSIM_GRID_* */
+    int32_t num_cells; /* the grid is num_cells x num_cells */
+    int32_t num_steps; /* _max_episode_steps */
+    int32_t goal_x;
+    int32_t goal_y;
+    int32_t factor;    /* NOISE: int(augmented_state); COUNTER: counter_limit; PLAIN: 1 */
+} offsim_grid_env;
+typedef struct offsim_env_rollouts {
+    int32_t R;
+    int32_t rng_kind; /* OFFSIM_STREAM_PCG64 */
+    uint64_t *rng;    /* [R, 4] action streams */
+} offsim_env_rollouts;
+int offsim_eval_env(const offsim_grid_env *env, offsim_env_rollouts *ro, const double *pi /* [nS,5] or NULL with a Q-dependent behaviour */,
+                    double gamma, const double *gamma_pow, int64_t n_gamma_pow, int64_t max_episodes, const offsim_evalmc_out *out,
+                    const offsim_td *td /* NULL: evalMC */, int32_t tie_reseed_episode, int64_t episode0, void *stream);
+
+/* offsim_eval_env_pop: offsim_eval_env for L policies or L learners on the same S action-stream seeds in ONE launch.  ro->R = L * S,
+ * member-major: rollout r = l * S + j is member l on seed j; ro->rng holds [L * S, 4] rows (the caller's S rows replicated L times), advanced
+ * per rollout.  All members of a seed start from the same action stream and see the same exogenous draws (default_rng(episode0 + e) depends
+ * on the episode alone), so differences between members are paired.
+ *   pop != NULL  a population of learners: struct offsim_td_pop as offsim_eval_queue_pop takes it with nS * 5 in the place of nZ * nA;
+ *                pi_stack, gamma, gamma_pow and n_gamma_pow are ignored (pop's are read).  A workgroup holds rollouts of one learner
+ *                (grid = L * ceil(S / rollouts per workgroup)); the carve and its 4 / 2 / 1 rule are offsim_eval_env's learner shape.
+ *                Rollout l * S + j equals, in every output bit and in the state it leaves, offsim_eval_env's learner driver run alone with
+ *                learner l's setting from seed j's stream, for every behaviour.
+ *   pop == NULL  evalMC of the stack pi_stack [L, nS, 5] f64 with one gamma / gamma_pow: the lane-per-rollout shape, rollout r reads stack
+ *                row r / S; tie_reseed_episode must be 0.  Rollout l * S + j equals offsim_eval_env's evalMC of pi_stack[l] from seed j.
+ * OFFSIM_EINVAL as offsim_eval_env, and L outside 1..65535, S < 1, ro->R != L * S, pi_stack = NULL without pop, and everything
+ * offsim_eval_td_pop checks about the per-learner arrays, behaviour_host, the schedules and the snapshot stride; OFFSIM_EUNSUPPORTED as
+ * offsim_eval_env.  Argument validation happens before any HIP call; ro->R = 0 launches nothing. */
+int offsim_eval_env_pop(const offsim_grid_env *env, offsim_env_rollouts *ro, int32_t L, int32_t S, const offsim_td_pop *pop,
+                        const double *pi_stack, double gamma, const double *gamma_pow, int64_t n_gamma_pow, int64_t max_episodes,
+                        const offsim_evalmc_out *out, int32_t tie_reseed_episode, int64_t episode0, void *stream);
+
 /* Fast path of evalMC_psrs for a fixed tabular policy (the headline scan).
  * offsim_compile_policy folds psrs.py:53-57 for policy pi [n_slots,nA] f64 into one 64-bit key per grouped row:
  *   key = T << 11 | done << 10 | z_next_slot,  T = floor(2^53 * pi[z][a]/p_log[a]/max_a'(pi[z][a']/p_log[a'])),

@@ -135,6 +135,19 @@ class EnvOut(C.Structure):
                 ("flags", _vp), ("ep_step", _vp), ("status", _vp)]
 
 
+GRID_PLAIN, GRID_NOISE, GRID_COUNTER = 0, 1, 2
+
+
+class GridEnv(C.Structure):
+    """struct offsim_grid_env"""
+    _fields_ = [("kind", _i32), ("num_cells", _i32), ("num_steps", _i32), ("goal_x", _i32), ("goal_y", _i32), ("factor", _i32)]
+
+
+class EnvRollouts(C.Structure):
+    """struct offsim_env_rollouts"""
+    _fields_ = [("R", _i32), ("rng_kind", _i32), ("rng", _vp)]
+
+
 PPO_ACTOR, PPO_CRITIC = 0, 1
 PPO_MAX_BLOCKS = 256
 
@@ -289,6 +302,10 @@ SIGNATURES = {
                                                 C.POINTER(EvalMCOut), _vp, _vp, _vp]),
     "offsim_eval_queue_rows_policy_pop": (C.c_int, [C.POINTER(Table), C.POINTER(Rollouts), _i32, _vp, _vp, _i32, _i32, _i32, C.c_double, _vp, _i64,
                                                     _i64, C.POINTER(EvalMCOut), _vp, _vp, _vp]),
+    "offsim_eval_env": (C.c_int, [C.POINTER(GridEnv), C.POINTER(EnvRollouts), _vp, C.c_double, _vp, _i64, _i64, C.POINTER(EvalMCOut), C.POINTER(TD),
+                                  _i32, _i64, _vp]),
+    "offsim_eval_env_pop": (C.c_int, [C.POINTER(GridEnv), C.POINTER(EnvRollouts), _i32, _i32, C.POINTER(TDPop), _vp, C.c_double, _vp, _i64, _i64,
+                                      C.POINTER(EvalMCOut), _i32, _i64, _vp]),
     "offsim_compile_policy": (C.c_int, [C.POINTER(Table), _vp, _vp, _vp]),
     "offsim_eval_mc_keys_kernel": (C.c_char_p, [_i32, _i32]),
     "offsim_compile_digests": (C.c_int, [C.POINTER(Table), _vp, _i32, _vp, _vp]),

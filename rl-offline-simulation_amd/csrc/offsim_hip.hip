@@ -1892,6 +1892,9 @@ extern "C" int offsim_td_curves(const double *ep_g, const int64_t *n_ep, int32_t
 // ---- evalMC on QueueEvaluator for policies over observations, one or a population (csrc/eval_queue_rows.hpp) ----
 #include "eval_queue_rows.hpp"
 
+// ---- the tabular drivers on the true grid worlds, the ground truth of the two above: evalMC / qlearn / expSARSA (csrc/eval_env.hpp) ----
+#include "eval_env.hpp"
+
 // ------------------------------------------------------------------------------------------------
 // Fast evalMC scan: compiled-policy keys + LDS candidate windows (scan_win.hpp)
 // ------------------------------------------------------------------------------------------------

@@ -11,6 +11,7 @@ per learner on the device.  Learners never interact: learner l on seed j is, bit
   population.run(table, seeds, ...)                                  -> TDPopulationResult of device tensors
   population.run_exo(env_or_tables, seeds, ...)                      the same on an exogenous-state log (PSRS_Exo), tables by observation
   population.run_queue(env_or_arrays, seeds, ...)                    the same on the queue simulator (QueueEvaluator), tables by state
+  population.run_env(grid_world, seeds, n_episodes, ...)             the same in the true grid world: the ground truth of the three above
   population.replay(log, orders, passes, ...)                        no simulator: the logged memory itself replayed through every learner
 """
 import itertools
@@ -314,6 +315,38 @@ class TDPopulation:
                                lambda n: BatchedQueueEvaluator(*arrays, R=n), launch,
                                lambda q: self._rows_into(Q0, q, range(probe.z_lo, probe.z_lo + nZ), range(nZ), self.L, S), tie=tie,
                                tie_out=not (isinstance(tie, str) and tie == "first"), trace_cap=trace_cap)
+
+    def run_env(self, env, seeds, n_episodes, tie="episode", episode0=0, tile=None, trace_cap=0):
+        """Every learner on every seed in the TRUE grid world (a GridWorld of evaluators/true_env_drivers.py; qlearn / expSARSA of
+        offsim4rl/agents/tabular.py:71-191 on the reference's own environment): the ground truth run(), run_exo() and run_queue() are
+        judged against.  pi / Q_init are [nS,5] or [L,nS,5] tables by observation (pi None: uniform).  Rollout (l, j) draws its actions
+        from default_rng(seeds[j]) and runs n_episodes episodes, episode e reset with seed episode0 + e: all learners of a seed start from
+        the same action stream and see the same exogenous draws, so comparisons are paired.  One launch per tile of seeds (default: all;
+        BatchedGridWorld.eval_td_population), then offsim_td_curves over all seeds.  tie: "episode" (the reference: ties between maximal Q
+        values are broken with a stream restarted as np.random.seed(episode0 + e) at every episode e), "first" (the first maximum), or
+        NumPy MT19937 states [625] (every rollout starts from it) / [L,S,625].  Returns a TDPopulationResult with Q [L,S,nS,5], tie_mt
+        [L,S,625] whenever a stream ran, td_err with trace_cap.  OFFSIM_ST_KEYERROR does not raise: it is in result.status."""
+        from .true_env_drivers import BatchedGridWorld, GridWorld
+        if not isinstance(env, GridWorld):
+            raise TypeError(f"TDPopulation.run_env: `env` must be a GridWorld, got {type(env).__name__}")
+        seeds, S = self._seeds("run_env", seeds)
+        n_episodes = int(n_episodes)
+        if n_episodes < 1:
+            raise ValueError("TDPopulation.run_env: n_episodes must be positive (an environment never runs dry)")
+        for k, x in (("pi", self.pi), ("Q_init", self.Q_init)):
+            if x is not None and x.shape[-2:] != (env.nS, env.nA):
+                raise ValueError(f"TDPopulation.run_env: {k} [nS,nA] = {(env.nS, env.nA)} expected, got {x.shape}")
+        if isinstance(tie, str) and tie not in ("episode", "first"):
+            raise ValueError(f"TDPopulation.run_env: tie must be 'episode', 'first' or MT19937 states, got {tie!r}")
+        Q0 = np.zeros((env.nS, env.nA)) if self.Q_init is None else self.Q_init
+
+        def launch(b, lo, sd, tie, hp):
+            b.set_action_seeds(sd)
+            return b.eval_td_population(pi=self.pi, q=Q0, tie=tie, episode0=episode0, **hp)
+
+        # (_run_tiles bounds the episodes by a log's initial rows: none here, so N0 = n_episodes leaves n_episodes as it is)
+        return self._run_tiles("run_env", seeds, n_episodes, n_episodes, S if tile is None else tile, lambda n: BatchedGridWorld(env, n), launch,
+                               lambda q: q, tie=tie, tie_out=tie is not None and not (isinstance(tie, str) and tie == "first"), trace_cap=trace_cap)
 
     def replay(self, log, orders=None, passes=1, td_cap=0, snap_stride=0, snap_cap=0):
         """Every learner on the logged memory itself, no simulator: qlearn(..., memory=...) of offsim4rl/agents/tabular.py:90-104 (and the
