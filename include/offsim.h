@@ -1127,6 +1127,61 @@ int offsim_env_collect_ppo_pop(const offsim_env *env, const offsim_collect_polic
                                int64_t T, int32_t max_episode_steps, const offsim_env_out *out, const offsim_collect_ppo_out *ppo,
                                void *stream);
 
+/* ---- evalMC of policies over observations in those environments: L actors on S paired seeds per launch ------------------------------------
+ * The value of MLP actors in the true dynamics, beside their value inside PSRS (offsim_eval_mc_rows_policy_pop) and inside the (z, a)
+ * queues (offsim_eval_queue_rows_policy_pop).  offsim_eval_env_obs runs L * S rollouts in ONE launch, one wavefront each, grid (ceil(S / 8),
+ * L): rollout (l, j) runs policy l for n_episodes episodes on seed j.  It is a query: there is no carried state, and the streams are read
+ * only -- rollout (l, j) starts from row j of rng_env / rng_act ([S,4] words as offsim_seed_streams writes them), whatever l, so every policy
+ * of a seed sees the same resets, the same noise and the same action uniforms, and differences between policies are paired.
+ * The environments (env->kind) and their rules are offsim_env_collect's.  Per episode: reset() (its draws from the env stream); per step the
+ * policy at the current observation (offsim_policy_mlp's bits, widened to f64), A drawn as offsim_env_collect draws it with one draw of the
+ * action stream, the dynamics, G = G + gamma_pow[t] * (double)reward in f64 in step order, t += 1; the episode ends at terminated, or
+ * truncated at max_episode_steps > 0 && t >= max_episode_steps (both bits may be set).  max_episode_steps is required for CartPole (> 0;
+ * CartPole-v1's is 500) and optional on the grids, whose num_steps already bounds an episode.  gamma_pow [n_gamma_pow]: gamma**t as the
+ * host computes it, at least as long as the longest episode (the cap; on the grids min(cap, num_steps) or num_steps).  A rollout equals,
+ * bit for bit, what offsim_env_collect records for one environment on the same streams, cut into its first n_episodes episodes.
+ * No A (a row of NaN or zeros): the rollout stops with OFFSIM_ST_KEYERROR, the draw consumed, the open episode dropped.
+ * pol: OFFSIM_COLLECT_MLP only -- one network (L = 1) or stacked ones (W [L][out][in], b [L][out], the descriptor learner 0's, as
+ * offsim_policy_mlp_pop); x_dtype OFFSIM_F32, dO the observation's width 1 / 2 / 4, the last layer nA = 5 / 5 / 2 units; x_start / x_next /
+ * x_init are not read.  The ROWS and TABULAR forms are refused with OFFSIM_EUNSUPPORTED (there are no logged rows; tabular policies on the
+ * grids are offsim_eval_env's).  L in 1..65535.
+ * Outputs, all written by the kernel, policy-major:
+ *   Gs [L,S,n_episodes] f64, lengths [L,S,n_episodes] i32, ended [L,S,n_episodes] u8 (OFFSIM_COLLECT_TERMINATED | OFFSIM_COLLECT_TRUNCATED)
+ *   per completed episode, zeros for the episodes a stopped rollout did not complete;
+ *   n_ep [L,S] episodes completed, steps [L,S] steps taken, status [L,S] OFFSIM_ST_OK | OFFSIM_ST_KEYERROR;
+ *   value [L,S] f64: the sum of the completed episodes' G in episode order, divided by n_ep (NaN for n_ep = 0).
+ * Trace (optional, for tests; any pointer may be NULL) of a rollout's first trace_cap steps, across episode boundaries: trace_action
+ *   [L,S,trace_cap] i32 (nA at the undrawable step); trace_state / trace_next_state [L,S,trace_cap,4] f64: offsim_env's state row before
+ *   the step, and after it before any reset.  The caller fills them; steps not taken are left as they were.
+ * Limits: the workgroup's LDS -- [W^T / b][16 f64 + 16 f32 + 2 activation rows + 8 f32 per rollout], 8 rollouts -- at most 160 KiB
+ * (OFFSIM_EUNSUPPORTED beyond); no other cap on the weights.
+ * Argument validation happens before any HIP call; S = 0 or n_episodes = 0 launches nothing (the output pointers may then be NULL). */
+typedef struct offsim_env_eval {
+    int32_t kind;                      /* OFFSIM_ENV_*                                              */
+    int32_t S;                         /* seeds                                                     */
+    int32_t num_cells;                 /* grids                                                     */
+    int32_t num_steps;                 /* grids: MyGridNavi._max_episode_steps                      */
+    int32_t goal_x;
+    int32_t goal_y;
+    const uint64_t *rng_env;           /* [S,4] read only                                           */
+    const uint64_t *rng_act;           /* [S,4] read only                                           */
+} offsim_env_eval;
+typedef struct offsim_env_eval_out {
+    double *Gs;                        /* [L,S,n_episodes]                                          */
+    int32_t *lengths;                  /* [L,S,n_episodes]                                          */
+    uint8_t *ended;                    /* [L,S,n_episodes]                                          */
+    int64_t *n_ep;                     /* [L,S]                                                     */
+    int64_t *steps;                    /* [L,S]                                                     */
+    int32_t *status;                   /* [L,S]                                                     */
+    double *value;                     /* [L,S]                                                     */
+    int64_t trace_cap;
+    int32_t *trace_action;             /* [L,S,trace_cap], or NULL                                  */
+    double *trace_state;               /* [L,S,trace_cap,4], or NULL                                */
+    double *trace_next_state;          /* likewise                                                  */
+} offsim_env_eval_out;
+int offsim_eval_env_obs(const offsim_env_eval *env, const offsim_collect_policy *pol, int32_t L, int64_t n_episodes, int32_t max_episode_steps,
+                        const double *gamma_pow, int64_t n_gamma_pow, const offsim_env_eval_out *out, void *stream);
+
 /* offsim_ppo_advantages: GAE-lambda advantages and rewards-to-go over step-major [T,E] records, with the path rules of the reference's
  * agent, and spinup's advantage normalisation (spinup PPOBuffer.finish_path / get, driven by offsim4rl/agents/ppo.py:106-158; E
  * environments = E MPI processes of local_steps_per_epoch = T).  Per environment e, over its valid steps t (flags & OFFSIM_COLLECT_SERVED):

@@ -135,6 +135,18 @@ class EnvOut(C.Structure):
                 ("flags", _vp), ("ep_step", _vp), ("status", _vp)]
 
 
+class EnvEval(C.Structure):
+    """struct offsim_env_eval"""
+    _fields_ = [("kind", _i32), ("S", _i32), ("num_cells", _i32), ("num_steps", _i32), ("goal_x", _i32), ("goal_y", _i32), ("rng_env", _vp),
+                ("rng_act", _vp)]
+
+
+class EnvEvalOut(C.Structure):
+    """struct offsim_env_eval_out"""
+    _fields_ = [("Gs", _vp), ("lengths", _vp), ("ended", _vp), ("n_ep", _vp), ("steps", _vp), ("status", _vp), ("value", _vp), ("trace_cap", _i64),
+                ("trace_action", _vp), ("trace_state", _vp), ("trace_next_state", _vp)]
+
+
 GRID_PLAIN, GRID_NOISE, GRID_COUNTER = 0, 1, 2
 
 
@@ -358,6 +370,7 @@ SIGNATURES = {
                                          C.POINTER(CollectPPOOut), _vp]),
     "offsim_env_collect_ppo_pop": (C.c_int, [C.POINTER(Env), C.POINTER(CollectPolicy), C.POINTER(CollectValue), _i32, _i32, _i64, _i32,
                                              C.POINTER(EnvOut), C.POINTER(CollectPPOOut), _vp]),
+    "offsim_eval_env_obs": (C.c_int, [C.POINTER(EnvEval), C.POINTER(CollectPolicy), _i32, _i64, _i32, _vp, _i64, C.POINTER(EnvEvalOut), _vp]),
     "offsim_ppo_advantages_pop": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, C.c_double, C.c_double, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "offsim_ppo_epoch_log": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "offsim_ppo_epoch_log_pop": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),

@@ -2579,6 +2579,9 @@ extern "C" int offsim_value_mlp(const void *x, int32_t x_dtype, int64_t n_x, int
 // ---- the same collection in the environments that produced the logs: grid worlds and CartPole, dynamics in the kernel (csrc/collect_env.hpp) ----
 #include "collect_env.hpp"
 
+// ---- evalMC of MLP policies in those environments: L actors on S paired seeds, whole rollouts per launch (csrc/eval_env_obs.hpp) ----
+#include "eval_env_obs.hpp"
+
 // ---- the PPO buffer: GAE-lambda, rewards-to-go and spinup's normalisation over [T, E] records (csrc/ppo_buffer.hpp) ----
 #include "ppo_buffer.hpp"
 

@@ -8,6 +8,7 @@ from .psrs_exo import PSRS_Exo, BatchedPSRSExo, evalmc_rollouts_exo, tabulate_ob
 from .vector_env import VectorPSRS  # noqa: F401
 from .vector_queue import VectorQueueEvaluator  # noqa: F401
 from .vector_true_env import VectorGridNavi, VectorCartPole  # noqa: F401
+from .true_env_population import evalmc_rollouts_true_env  # noqa: F401
 from .obs_policy import MLPPolicy, RowPolicy, CallablePolicy, MLPValue, RowValue, PolicyPopulation  # noqa: F401
 from .batched import evalmc_rollouts_population  # noqa: F401
 from .ppo_buffer import PPOBatch, ppo_advantages  # noqa: F401

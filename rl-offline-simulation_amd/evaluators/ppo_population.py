@@ -188,6 +188,14 @@ class PPOPopulation:
         from .queue_evaluator import evalmc_rollouts_queue_population
         return evalmc_rollouts_queue_population(env_or_arrays, seeds, PolicyPopulation.from_ppo(self), gamma, obs=obs, next_obs=next_obs, **kw)
 
+    def evaluate_env(self, kind_or_env, seeds, gamma, n_episodes, **kw):
+        """evalMC in the TRUE environment of every learner's actor, with its current weights, on the same seeds (the same resets, noise and
+        action uniforms): evalmc_rollouts_true_env (true_env_population.py) over PolicyPopulation.from_ppo(self); `kind_or_env`, `kw` and
+        the result are its."""
+        from .obs_policy import PolicyPopulation
+        from .true_env_population import evalmc_rollouts_true_env
+        return evalmc_rollouts_true_env(kind_or_env, seeds, PolicyPopulation.from_ppo(self), gamma, n_episodes, **kw)
+
     # ---- one learner, exported ----
     def actor(self, l):
         """learner l's actor as an MLPPolicy of its current weights (a copy)"""
