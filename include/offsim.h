@@ -1182,6 +1182,95 @@ typedef struct offsim_env_eval_out {
 int offsim_eval_env_obs(const offsim_env_eval *env, const offsim_collect_policy *pol, int32_t L, int64_t n_episodes, int32_t max_episode_steps,
                         const double *gamma_pow, int64_t n_gamma_pow, const offsim_env_eval_out *out, void *stream);
 
+/* ---- tabular policies and TD learners on the LATENT STATES of those environments: the tabular drivers behind an encoder ---------------------
+ * offsim_eval_env_latent: the reference's tabular drivers -- evalMC (td = NULL; offsim4rl/agents/tabular.py:247-270), qlearn (:71-139),
+ * expSARSA (:141-191) and z_expSARSA (:193-245, run->rec_max) by td->mode -- on CartPole-v1 (OFFSIM_ENV_CARTPOLE) and MyGridNaviCoords
+ * (OFFSIM_ENV_GRID_COORDS, offsim4rl/envs/gridworld.py:187-211), whose observations are continuous, with pi and Q [nS, nA] indexed by
+ * z = enc(observation): all rollouts in ONE launch (csrc/eval_env_latent.hpp), one wavefront each.  The ground truth that offsim_eval_td /
+ * offsim_eval_mc (PSRS) and offsim_eval_queue (the (z, a) queues) on a log encoded by the same encoder are judged against.
+ *   env  struct offsim_env_eval: the world and its rules as offsim_env_collect's (nA = 2 / 5); S is the number of ROLLOUTS R, and rng_act /
+ *        rng_env hold [R, 4] PCG64 rows as offsim_seed_streams writes them, READ ONLY: the call is a query, and where the streams stand
+ *        afterwards comes back in run->rng_act_end / rng_env_end.  OFFSIM_ENV_GRID is refused with OFFSIM_EUNSUPPORTED (offsim_eval_env's).
+ *   enc  struct offsim_latent_encoder, run in the kernel at every observation the loop visits (the f32 observation offsim_env_collect records):
+ *          OFFSIM_LATENT_BOX  CartpoleBoxEncoder.get_box with offsim_encode_box's f32 literals and comparisons: -1 (out of bounds) .. 161;
+ *                             OFFSIM_ENV_CARTPOLE only (OFFSIM_EUNSUPPORTED otherwise), nS >= 162.
+ *          OFFSIM_LATENT_MLP  the HOMER obs_encoder Linear(dO, H) -> LeakyReLU(0.01) -> Linear(H, nZ) -> first arg max, offsim_encode_mlp's
+ *                             arithmetic (per unit one k-ordered fmaf chain from 0, then the bias; a row that is all NaN gives 0); W1 [H, dO],
+ *                             b1 [H], W2 [nZ, H], b2 [nZ] f32 device pointers, dO the observation's width (2 / 4), nZ <= nS.  Limits: H and nZ
+ *                             at most 4096 each, and the weights (H * dO + H + nZ * H + nZ floats, staged once per workgroup) with 4 + H + nZ
+ *                             floats per rollout must fit the LDS carve below: OFFSIM_EUNSUPPORTED beyond.
+ *        nS: the rows of pi and Q.  The row of z is z for 0 <= z < nS and z + nS for -nS <= z < 0 -- NumPy's index wrap: the reference's Q[-1]
+ *        is the last row -- the rule TransitionTable's slots follow on the PSRS side, so Q compares entry for entry.
+ * Per step: z = enc(obs); p = pi[row], or the behaviour policy on Q[row] (offsim_eval_td's rules); A = Generator.choice(nA, p=p) as
+ *   offsim_eval_env draws it, one draw of the action stream per step; the dynamics (offsim_env_collect's, their draws from the environment
+ *   stream); z' = enc(obs'); the update of offsim_eval_td on Q[row, A] with Q[row'] (the same arithmetic and order; done is not masked, as in
+ *   the reference); G = G + gamma_pow[t] * (double)reward, where the grid's -0.1f is widened to the f64 literal -0.1, the reference's
+ *   Python float.  A row p without a cdf entry above u (NaN, all zeros): OFFSIM_ST_KEYERROR, the draw consumed, the environment not stepped.
+ *   An episode ends at done or at run->max_episode_steps (required > 0 for CartPole, CartPole-v1's is 500; 0 on the grid: num_steps alone).
+ * run  struct offsim_latent_run:
+ *        reseed = 1  the reference's protocol: episode e of the call restarts the environment stream as np.random.default_rng(episode0 + e),
+ *                    seeded on the device, and draws the reset from it (env.reset(seed=episode)); env->rng_env is not read;
+ *        reseed = 0  the rollout's own environment stream (row r of env->rng_env) runs on across episodes;
+ *        rec_max = 1 (z_expSARSA, OFFSIM_TD_EXPSARSA only) td_err records R + gamma * max_a Q[row', a] - Q[row, A] while the update stays
+ *                    expected SARSA (tabular.py:229 / :232);
+ *        tie_reseed_episode (needs tie_mt): the tie stream of episode e restarts as np.random.seed((episode0 + e) mod 2^32);
+ *        rng_act_end / rng_env_end [R, 4] or NULL: the rows a later call continues from (with episode0 moved on by the episodes run);
+ *        the trace (optional, for tests; any pointer NULL) of a rollout's first trace_cap steps: trace_z / trace_z_next [R, trace_cap] i32 as
+ *        the encoder gave them (before the wrap), trace_reward [R, trace_cap] f64, trace_done [R, trace_cap] u8, trace_state /
+ *        trace_next_state [R, trace_cap, 4] f64 (offsim_env's state row before and after the step).  Steps not taken are left as they were.
+ * td, out, gamma_pow: offsim_eval_env's, word for word, with q [R, nS, nA]; trace_pop holds the ACTION drawn at every step (nA at the
+ *   undrawable one).  On exit q and tie_mt are written back.
+ * Launch shape: one wavefront per rollout; LDS per workgroup: per rollout Q (nS * nA * 8 bytes), the behaviour row and the tie stream (2496)
+ *   for a learner, the shared pi when given, the encoder's weights and 4 * (4 + H + nZ) bytes per rollout; 4 rollouts per workgroup, then 2,
+ *   then 1 while the carve exceeds 64 KiB, one rollout up to 160 KiB, beyond that -- or nS * nA > 40960 -- OFFSIM_EUNSUPPORTED.
+ * OFFSIM_EINVAL: NULL env / enc / run / out / required outputs / q / weights / streams with S > 0, unknown kinds, a goal off the grid, nS < 1,
+ *   nZ > nS, an input width that is not the observation's, CartPole without a cap, n_episodes <= 0, episode0 < 0, pi = NULL where a policy is
+ *   read, flags outside 0 / 1, rec_max without OFFSIM_TD_EXPSARSA, and everything offsim_eval_env checks about td and out.
+ * Argument validation happens before any HIP call; env->S = 0 launches nothing.
+ *
+ * offsim_eval_env_latent_pop: offsim_eval_env_latent for L policies or L learners on the same S seeds in ONE launch, behind ONE encoder.
+ * env->S = L * S rollouts, member-major: rollout r = l * S + j is member l on seed j; the stream tables hold [L * S, 4] rows (the caller's S
+ * rows replicated L times), so all members of a seed see the same resets, the same noise and the same action uniforms.
+ *   pop != NULL  a population of learners: struct offsim_td_pop as offsim_eval_env_pop takes it with nS * nA entries per table; pi_stack,
+ *                gamma, gamma_pow and n_gamma_pow are ignored (pop's are read).  A workgroup holds rollouts of one learner (grid = L *
+ *                ceil(S / rollouts per workgroup)).  Rollout l * S + j equals, in every output bit, offsim_eval_env_latent run alone with
+ *                learner l's setting on seed j's streams.
+ *   pop == NULL  evalMC of the stack pi_stack [L, nS, nA] f64 with one gamma / gamma_pow, the same launch shape (a workgroup stages its
+ *                policy); run->tie_reseed_episode and rec_max must be 0.
+ * OFFSIM_EINVAL as offsim_eval_env_latent, and L outside 1..65535, S < 1, env->S != L * S, pi_stack = NULL without pop, and everything
+ * offsim_eval_td_pop checks about the per-learner arrays; OFFSIM_EUNSUPPORTED as offsim_eval_env_latent.  Argument validation happens
+ * before any HIP call; env->S = 0 launches nothing. */
+#define OFFSIM_LATENT_BOX 0
+#define OFFSIM_LATENT_MLP 1
+typedef struct offsim_latent_encoder {
+    int32_t kind;                      /* OFFSIM_LATENT_*                                           */
+    int32_t nS;                        /* rows of pi and Q                                          */
+    int32_t dO, H, nZ;                 /* MLP                                                       */
+    const float *W1, *b1, *W2, *b2;    /* MLP: state_dict layout, device pointers                   */
+} offsim_latent_encoder;
+typedef struct offsim_latent_run {
+    int32_t reseed;                    /* 1: default_rng(episode0 + e) per episode; 0: env->rng_env */
+    int32_t max_episode_steps;         /* 0: none (the grid)                                        */
+    int32_t rec_max;                   /* z_expSARSA's recorded TD error                            */
+    int32_t tie_reseed_episode;
+    int64_t episode0;
+    uint64_t *rng_act_end;             /* [R,4], or NULL                                            */
+    uint64_t *rng_env_end;             /* [R,4], or NULL                                            */
+    int64_t trace_cap;
+    int32_t *trace_z;                  /* [R,trace_cap], or NULL                                    */
+    int32_t *trace_z_next;             /* likewise                                                  */
+    double *trace_reward;              /* likewise                                                  */
+    uint8_t *trace_done;               /* likewise                                                  */
+    double *trace_state;               /* [R,trace_cap,4], or NULL                                  */
+    double *trace_next_state;          /* likewise                                                  */
+} offsim_latent_run;
+int offsim_eval_env_latent(const offsim_env_eval *env, const offsim_latent_encoder *enc, const double *pi /* [nS,nA] or NULL */, double gamma,
+                           const double *gamma_pow, int64_t n_gamma_pow, int64_t n_episodes, const offsim_evalmc_out *out,
+                           const offsim_td *td /* NULL: evalMC */, const offsim_latent_run *run, void *stream);
+int offsim_eval_env_latent_pop(const offsim_env_eval *env, const offsim_latent_encoder *enc, int32_t L, int32_t S, const offsim_td_pop *pop,
+                               const double *pi_stack, double gamma, const double *gamma_pow, int64_t n_gamma_pow, int64_t n_episodes,
+                               const offsim_evalmc_out *out, const offsim_latent_run *run, void *stream);
+
 /* offsim_ppo_advantages: GAE-lambda advantages and rewards-to-go over step-major [T,E] records, with the path rules of the reference's
  * agent, and spinup's advantage normalisation (spinup PPOBuffer.finish_path / get, driven by offsim4rl/agents/ppo.py:106-158; E
  * environments = E MPI processes of local_steps_per_epoch = T).  Per environment e, over its valid steps t (flags & OFFSIM_COLLECT_SERVED):

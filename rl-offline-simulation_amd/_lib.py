@@ -147,6 +147,21 @@ class EnvEvalOut(C.Structure):
                 ("trace_action", _vp), ("trace_state", _vp), ("trace_next_state", _vp)]
 
 
+LATENT_BOX, LATENT_MLP = 0, 1
+
+
+class LatentEncoder(C.Structure):
+    """struct offsim_latent_encoder"""
+    _fields_ = [("kind", _i32), ("nS", _i32), ("dO", _i32), ("H", _i32), ("nZ", _i32), ("W1", _vp), ("b1", _vp), ("W2", _vp), ("b2", _vp)]
+
+
+class LatentRun(C.Structure):
+    """struct offsim_latent_run"""
+    _fields_ = [("reseed", _i32), ("max_episode_steps", _i32), ("rec_max", _i32), ("tie_reseed_episode", _i32), ("episode0", _i64),
+                ("rng_act_end", _vp), ("rng_env_end", _vp), ("trace_cap", _i64), ("trace_z", _vp), ("trace_z_next", _vp), ("trace_reward", _vp),
+                ("trace_done", _vp), ("trace_state", _vp), ("trace_next_state", _vp)]
+
+
 GRID_PLAIN, GRID_NOISE, GRID_COUNTER = 0, 1, 2
 
 
@@ -371,6 +386,10 @@ SIGNATURES = {
     "offsim_env_collect_ppo_pop": (C.c_int, [C.POINTER(Env), C.POINTER(CollectPolicy), C.POINTER(CollectValue), _i32, _i32, _i64, _i32,
                                              C.POINTER(EnvOut), C.POINTER(CollectPPOOut), _vp]),
     "offsim_eval_env_obs": (C.c_int, [C.POINTER(EnvEval), C.POINTER(CollectPolicy), _i32, _i64, _i32, _vp, _i64, C.POINTER(EnvEvalOut), _vp]),
+    "offsim_eval_env_latent": (C.c_int, [C.POINTER(EnvEval), C.POINTER(LatentEncoder), _vp, C.c_double, _vp, _i64, _i64, C.POINTER(EvalMCOut),
+                                         C.POINTER(TD), C.POINTER(LatentRun), _vp]),
+    "offsim_eval_env_latent_pop": (C.c_int, [C.POINTER(EnvEval), C.POINTER(LatentEncoder), _i32, _i32, C.POINTER(TDPop), _vp, C.c_double, _vp, _i64,
+                                             _i64, C.POINTER(EvalMCOut), C.POINTER(LatentRun), _vp]),
     "offsim_ppo_advantages_pop": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, C.c_double, C.c_double, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "offsim_ppo_epoch_log": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "offsim_ppo_epoch_log_pop": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),

@@ -2582,6 +2582,9 @@ extern "C" int offsim_value_mlp(const void *x, int32_t x_dtype, int64_t n_x, int
 // ---- evalMC of MLP policies in those environments: L actors on S paired seeds, whole rollouts per launch (csrc/eval_env_obs.hpp) ----
 #include "eval_env_obs.hpp"
 
+// ---- the tabular drivers on the latent states of those environments: encoder, dynamics and learner in one loop (csrc/eval_env_latent.hpp) ----
+#include "eval_env_latent.hpp"
+
 // ---- the PPO buffer: GAE-lambda, rewards-to-go and spinup's normalisation over [T, E] records (csrc/ppo_buffer.hpp) ----
 #include "ppo_buffer.hpp"
 

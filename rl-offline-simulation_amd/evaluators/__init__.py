@@ -4,6 +4,8 @@ from .trivial_baselines import FollowObservationOnly, FollowActionOnly, ServeRan
 from .queue_evaluator import (QueueEvaluator, BatchedQueueEvaluator, evalmc_rollouts_queue, evalmc_rollouts_queue_population,  # noqa: F401
                               evalMC_queue, qlearn_queue, expSARSA_queue)
 from .true_env_drivers import (GridWorld, BatchedGridWorld, evalMC_env, qlearn_env, expSARSA_env, rollout_env, evalmc_rollouts_env)  # noqa: F401
+from .latent_env_drivers import (LatentEnv, BatchedLatentEnv, evalMC_latent_env, qlearn_latent_env, expSARSA_latent_env, z_expSARSA_env,  # noqa: F401
+                                 evalmc_rollouts_latent_env)
 from .psrs_exo import PSRS_Exo, BatchedPSRSExo, evalmc_rollouts_exo, tabulate_obs  # noqa: F401
 from .vector_env import VectorPSRS  # noqa: F401
 from .vector_queue import VectorQueueEvaluator  # noqa: F401

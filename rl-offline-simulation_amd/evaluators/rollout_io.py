@@ -3,6 +3,7 @@
   rollout_outputs     the output dict of a launch and its struct offsim_evalmc_out (the one place that states dtypes, fills, shapes)
   td_outputs          the learner kernels' extras: td_err, beh_arg, q_snap
   tie_stream          a caller's MT19937 states as the int32 tensor the kernels read
+  td_env_launch / td_driver_schedules   the learner struct and the schedule / tie preamble of the drivers on a true environment
   td_population_launch   the per-learner arguments of a population of learners as struct offsim_td_pop, with its outputs
   population_state / population_result   a population launch's copies of the sampler state, and its dict as [n, S, ...]
   seed_tiles / collect_host / host_result   the loop over tiles of sampler seeds and the host arrays it returns
@@ -104,6 +105,59 @@ def tie_stream(tie_mt, device=None):
     tensor that already is one comes back as itself, so a launch advances the caller's states in place."""
     mt = torch.as_tensor(np.ascontiguousarray(tie_mt).view(np.int32) if not isinstance(tie_mt, torch.Tensor) else tie_mt)
     return mt.to(device=device, dtype=torch.int32)
+
+
+def td_env_launch(td, R, rows, nA, device, o, trace_cap):
+    """The learner of a launch on a true environment (BatchedGridWorld.eval_td, BatchedLatentEnv.eval_td), from the dict `td` those methods
+    make of their arguments -- mode, alpha, q [R,rows,nA] or None (zeros), behaviour, epsilon, alpha_ep / epsilon_ep, snap_cap, snap_stride,
+    tie: None / "first" (the first maximum), "episode" (the stream restarts at every episode: a fresh [R,625] state), or MT19937 states
+    advanced in place.  Adds q, tie_mt and the learner extras to `o`; returns (struct offsim_td, what the launch must keep alive, the
+    tie_reseed_episode flag)."""
+    dev = device
+    q = td["q"]
+    q = torch.zeros((R, rows, nA), dtype=torch.float64, device=dev) if q is None else \
+        torch.as_tensor(q, dtype=torch.float64).to(dev).reshape(R, rows, nA).contiguous().clone()
+    behaviour = int(td["behaviour"])
+    td_outputs(o, q, trace_cap, td["snap_cap"], beh_arg=behaviour == L.BEHAVIOUR_EPS_GREEDY)
+    a_ep, e_ep = (None if x is None else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64)).to(dev) for x in (td["alpha_ep"], td["epsilon_ep"]))
+    n_sched = max(a_ep.numel() if a_ep is not None else 0, e_ep.numel() if e_ep is not None else 0)
+    assert all(x is None or x.numel() == n_sched for x in (a_ep, e_ep)), "alpha_ep and epsilon_ep cover the same episodes"
+    tie, mt, reseed = td["tie"], None, 0
+    if isinstance(tie, str) and tie == "episode":
+        reseed = 1
+        mt = torch.zeros((R, 625), dtype=torch.int32, device=dev)
+        mt[:, 624] = 624
+    elif tie is not None and not (isinstance(tie, str) and tie == "first"):
+        mt = tie_stream(tie, dev).reshape(R, 625).contiguous()
+    if mt is not None:
+        o["tie_mt"] = mt
+    tdc = L.TD(mode=int(td["mode"]), alpha=float(td["alpha"]), q=L.ptr(q), td_err=L.ptr(o.get("td_err")), td_cap=trace_cap, behaviour=behaviour,
+               epsilon=float(td["epsilon"]), alpha_ep=L.ptr(a_ep), epsilon_ep=L.ptr(e_ep), n_sched=n_sched, q_snap=L.ptr(o.get("q_snap")),
+               snap_cap=td["snap_cap"], snap_stride=max(int(td["snap_stride"]), 1), tie_mt=L.ptr(mt), beh_arg=L.ptr(o.get("beh_arg")))
+    o["q"] = q
+    return tdc, (a_ep, e_ep), reseed
+
+
+def td_driver_schedules(schedule, alpha, epsilon, kind, n_ep, tie):
+    """The preamble of a reference learner driver on a true environment (qlearn_env / expSARSA_env and their latent forms): the behaviour
+    code of `kind`, alpha(episode) / epsilon(episode) tabulated for n_ep episodes by `schedule` (the caller's psrs._schedule; each filled with its constant when only the other is a
+    schedule; "greedy" is epsilon 0), and tie = "global" turned into NumPy's global MT19937 state as it stands.  Returns (behaviour, a_tab,
+    e_tab, epsilon, tie, the global state before the call)."""
+    a_tab, e_tab = schedule(alpha, n_ep), schedule(epsilon, n_ep)
+    if kind == "greedy":
+        e_tab, epsilon = None, 0.0
+    behaviour = {"fixed": L.BEHAVIOUR_FIXED, "eps_greedy": L.BEHAVIOUR_EPS_GREEDY, "greedy": L.BEHAVIOUR_EPS_GREEDY,
+                 "soft_greedy": L.BEHAVIOUR_SOFT_GREEDY}[kind]
+    if a_tab is not None and e_tab is None:
+        e_tab = np.full(len(a_tab), float(epsilon) if not callable(epsilon) else 0.0)
+    if e_tab is not None and a_tab is None:
+        a_tab = np.full(len(e_tab), float(alpha))
+    st = np.random.get_state()
+    if tie == "global":  # _random_argmax draws from NumPy's global stream as it stands: the device continues it
+        if st[0] != "MT19937":
+            raise NotImplementedError("np.random's global bit generator is not MT19937")
+        tie = np.concatenate([np.asarray(st[1], dtype=np.uint32), np.array([st[2]], dtype=np.uint32)])[None, :]
+    return behaviour, a_tab, e_tab, epsilon, tie, st
 
 
 def td_population_launch(who, device, S, rows, nA, n_log, mode, alpha, gamma, behaviour, epsilon, pi, q, alpha_ep, epsilon_ep, tie_mt, n_gamma_pow,

@@ -348,6 +348,40 @@ class TDPopulation:
         return self._run_tiles("run_env", seeds, n_episodes, n_episodes, S if tile is None else tile, lambda n: BatchedGridWorld(env, n), launch,
                                lambda q: q, tie=tie, tie_out=tie is not None and not (isinstance(tie, str) and tie == "first"), trace_cap=trace_cap)
 
+    def run_latent_env(self, env, seeds, n_episodes, tie="episode", reseed="episode", episode0=0, tile=None, trace_cap=0):
+        """Every learner on every seed in the TRUE environment behind its encoder (a LatentEnv of evaluators/latent_env_drivers.py: CartPole
+        with the box or a HOMER encoder, the coordinate grid with a HOMER encoder; qlearn / expSARSA of offsim4rl/agents/tabular.py with the
+        tables indexed by z = encoder(observation)): the ground truth run() and run_queue() on a log encoded by the same encoder are judged
+        against.  pi / Q_init are [nS,nA] or [L,nS,nA] tables by latent row (pi None: uniform).  Rollout (l, j) draws its actions from
+        default_rng(seeds[j]) and runs n_episodes episodes; reseed = "episode" (the reference): episode e resets with default_rng(episode0 +
+        e); "none": seed j's own environment stream default_rng(seeds[j]) runs on.  Either way all learners of a seed see the same resets,
+        noise and action uniforms, so comparisons are paired.  One launch per tile of seeds (default: all;
+        BatchedLatentEnv.eval_td_population), then offsim_td_curves over all seeds.  tie as run_env's.  Returns a TDPopulationResult with
+        Q [L,S,nS,nA], tie_mt [L,S,625] whenever a stream ran, td_err with trace_cap.  OFFSIM_ST_KEYERROR does not raise: it is in
+        result.status."""
+        from .latent_env_drivers import BatchedLatentEnv, LatentEnv
+        if not isinstance(env, LatentEnv):
+            raise TypeError(f"TDPopulation.run_latent_env: `env` must be a LatentEnv, got {type(env).__name__}")
+        seeds, S = self._seeds("run_latent_env", seeds)
+        n_episodes = int(n_episodes)
+        if n_episodes < 1:
+            raise ValueError("TDPopulation.run_latent_env: n_episodes must be positive (an environment never runs dry)")
+        for k, x in (("pi", self.pi), ("Q_init", self.Q_init)):
+            if x is not None and x.shape[-2:] != (env.nS, env.nA):
+                raise ValueError(f"TDPopulation.run_latent_env: {k} [nS,nA] = {(env.nS, env.nA)} expected, got {x.shape}")
+        if isinstance(tie, str) and tie not in ("episode", "first"):
+            raise ValueError(f"TDPopulation.run_latent_env: tie must be 'episode', 'first' or MT19937 states, got {tie!r}")
+        if reseed not in ("episode", "none"):
+            raise ValueError(f"TDPopulation.run_latent_env: reseed must be 'episode' or 'none', got {reseed!r}")
+        Q0 = np.zeros((env.nS, env.nA)) if self.Q_init is None else self.Q_init
+
+        def launch(b, lo, sd, tie, hp):
+            b.set_seeds(sd)
+            return b.eval_td_population(pi=self.pi, q=Q0, tie=tie, episode0=episode0, reseed=reseed, **hp)
+
+        return self._run_tiles("run_latent_env", seeds, n_episodes, n_episodes, S if tile is None else tile, lambda n: BatchedLatentEnv(env, n), launch,
+                               lambda q: q, tie=tie, tie_out=tie is not None and not (isinstance(tie, str) and tie == "first"), trace_cap=trace_cap)
+
     def replay(self, log, orders=None, passes=1, td_cap=0, snap_stride=0, snap_cap=0):
         """Every learner on the logged memory itself, no simulator: qlearn(..., memory=...) of offsim4rl/agents/tabular.py:90-104 (and the
         same sweep with the expected-SARSA target) for all L learners in one launch (offsim_replay_td, evaluators/replay.py).

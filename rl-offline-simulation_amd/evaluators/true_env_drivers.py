@@ -25,8 +25,8 @@ import torch
 from .. import _lib as L
 from ..table import seed_streams, seeds_tensor
 from .psrs import _behaviour_kind, _schedule
-from .rollout_io import (HOST_KEYS, _gamma_pow, collect_host, host_result, population_host_result, population_result, rollout_outputs, td_outputs,
-                         td_population_launch, tie_stream)
+from .rollout_io import (HOST_KEYS, _gamma_pow, collect_host, host_result, population_host_result, population_result, rollout_outputs,
+                         td_driver_schedules, td_env_launch, td_population_launch)
 
 _KINDS = {"plain": L.GRID_PLAIN, "noise": L.GRID_NOISE, "counter": L.GRID_COUNTER}
 NA = 5  # noop, up, right, down, left
@@ -185,28 +185,7 @@ class BatchedGridWorld:
         o, oc = rollout_outputs(R, dev, ep_cap, trace_cap)
         tdc, keep, reseed = None, (), 0
         if td is not None:
-            q = td["q"]
-            q = torch.zeros((R, nS, nA), dtype=torch.float64, device=dev) if q is None else \
-                torch.as_tensor(q, dtype=torch.float64).to(dev).reshape(R, nS, nA).contiguous().clone()
-            behaviour = int(td["behaviour"])
-            td_outputs(o, q, trace_cap, td["snap_cap"], beh_arg=behaviour == L.BEHAVIOUR_EPS_GREEDY)
-            a_ep, e_ep = (None if x is None else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64)).to(dev) for x in (td["alpha_ep"], td["epsilon_ep"]))
-            n_sched = max(a_ep.numel() if a_ep is not None else 0, e_ep.numel() if e_ep is not None else 0)
-            assert all(x is None or x.numel() == n_sched for x in (a_ep, e_ep)), "alpha_ep and epsilon_ep cover the same episodes"
-            tie, mt = td["tie"], None
-            if isinstance(tie, str) and tie == "episode":
-                reseed = 1
-                mt = torch.zeros((R, 625), dtype=torch.int32, device=dev)
-                mt[:, 624] = 624
-            elif tie is not None and not (isinstance(tie, str) and tie == "first"):
-                mt = tie_stream(tie, dev).reshape(R, 625).contiguous()
-            if mt is not None:
-                o["tie_mt"] = mt
-            tdc = L.TD(mode=int(td["mode"]), alpha=float(td["alpha"]), q=L.ptr(q), td_err=L.ptr(o.get("td_err")), td_cap=trace_cap, behaviour=behaviour,
-                       epsilon=float(td["epsilon"]), alpha_ep=L.ptr(a_ep), epsilon_ep=L.ptr(e_ep), n_sched=n_sched, q_snap=L.ptr(o.get("q_snap")),
-                       snap_cap=td["snap_cap"], snap_stride=max(int(td["snap_stride"]), 1), tie_mt=L.ptr(mt), beh_arg=L.ptr(o.get("beh_arg")))
-            o["q"] = q
-            keep = (a_ep, e_ep)
+            tdc, keep, reseed = td_env_launch(td, R, nS, nA, dev, o, trace_cap)
         gp = self._gp(gamma)
         ro = self._ro(self.rng)
         L.check(L.load().offsim_eval_env(C.byref(self.c), C.byref(ro), L.ptr(pi_d), float(gamma), L.ptr(gp), gp.numel(), int(n_episodes), C.byref(oc),
@@ -429,20 +408,7 @@ def _td_env(env, what, n_episodes, gamma, alpha, epsilon, Q_init, save_Q, mode, 
         raise ValueError(f"{what}: tie must be 'episode', 'global' or 'first'")
     if n_ep <= 0:
         return Q0, {"Gs": np.array([]), "Qs": np.array([Q0]), "TD_errors": np.array([]), "memory": []}
-    a_tab, e_tab = _schedule(alpha, n_ep), _schedule(epsilon, n_ep)
-    if kind == "greedy":
-        e_tab, epsilon = None, 0.0
-    behaviour = {"fixed": L.BEHAVIOUR_FIXED, "eps_greedy": L.BEHAVIOUR_EPS_GREEDY, "greedy": L.BEHAVIOUR_EPS_GREEDY,
-                 "soft_greedy": L.BEHAVIOUR_SOFT_GREEDY}[kind]
-    if a_tab is not None and e_tab is None:
-        e_tab = np.full(len(a_tab), float(epsilon) if not callable(epsilon) else 0.0)
-    if e_tab is not None and a_tab is None:
-        a_tab = np.full(len(e_tab), float(alpha))
-    st = np.random.get_state()
-    if tie == "global":  # _random_argmax draws from NumPy's global stream as it stands: the device continues it
-        if st[0] != "MT19937":
-            raise NotImplementedError("np.random's global bit generator is not MT19937")
-        tie = np.concatenate([np.asarray(st[1], dtype=np.uint32), np.array([st[2]], dtype=np.uint32)])[None, :]
+    behaviour, a_tab, e_tab, epsilon, tie, st = td_driver_schedules(_schedule, alpha, epsilon, kind, n_ep, tie)
     cap = n_ep * env.num_steps + 1
     o = _one(env, seed).eval_td(pi_tab, gamma, mode, 0.0 if callable(alpha) else alpha, q=Q0[None], n_episodes=n_ep, ep_cap=n_ep, trace_cap=cap,
                                 behaviour=behaviour, epsilon=0.0 if callable(epsilon) else epsilon, alpha_ep=a_tab,
