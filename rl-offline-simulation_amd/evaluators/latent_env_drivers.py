@@ -49,9 +49,18 @@ def box_of(obs):
 
 
 def _fma32(a, b, c):
-    """fmaf(a, b, c) on f32 values: the product is exact in f64; the sum rounds to f64 and then to f32 (a double rounding differs from the
-    device's single one only when the f64 sum lands on an f32 tie)"""
-    return np.float32(np.float64(a) * np.float64(b) + np.float64(c))
+    """fmaf(a, b, c) on f32 values, rounded once: the product is exact in f64; TwoSum gives the error of the f64 sum, and an inexact sum is
+    moved to its odd neighbour on the error's side (round to odd), which the cast to f32 then rounds as it would the exact value (f64
+    carries more than two bits beyond f32)"""
+    p, c = np.float64(a) * np.float64(b), np.float64(c)
+    s = p + c
+    if not np.isfinite(s):
+        return np.float32(s)
+    t = s - p
+    err = (p - (s - t)) + (c - t)
+    if err != 0.0 and not int(s.view(np.int64)) & 1:
+        s = np.nextafter(s, np.float64(np.inf) if err > 0 else np.float64(-np.inf))
+    return np.float32(s)
 
 
 def mlp_latent(weights, obs):
